@@ -1,6 +1,6 @@
 """bench.py -- images/sec of the IWAE train step (forward + backward + Adam [+ RCCL all-reduce]).
 
-  python bench.py --gpus 1 --steps 100 --warmup 10 [--config c1]
+  python bench.py --gpus 1 --steps 100 --warmup 10 [--config c1] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -8,7 +8,12 @@ Default workload (BASELINE.json configs[1], --config c1): 1-layer IWAE, k=50, ba
 is configs[4], global batch 8192), bf16 GEMM operands with fp32 accumulation, objective iwae_elbo, synthetic binarised
 28x28 images already resident in HBM, Keras-style random-init weights.  The other BASELINE configs are selectable
 (--config c0 | c2 | c3: the reference's default regime B=20,k=1; the 2-layer model; the DReG step) and print the same
-line for their own workload.  Rank 0 prints ONE JSON line.  The oracle is used only for the cpu_baseline leg.
+line for their own workload.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs: set-up, the untimed settling steps, EXACTLY --steps timed steps, the line.
+--full adds what is measured or checked beyond it, all outside the timed region: the per-kernel event pass and the
+roofline object, the k = 5000 evaluator leg, the CPU baseline (the only use of the oracle) and the ELBO after the run.
+--dump-outputs DIR writes the model state the last timed step left (bench_outputs/ is the ignored place for it in the tree).
 """
 import argparse
 import json
@@ -188,6 +193,16 @@ def load_profile_traffic(kernel_match, config, build_id):
     return None, stale, None
 
 
+def dump_outputs(net, out_dir):
+    """What a caller of the timed train step gets back after its last step: the parameters it updated, the gradient it computed
+    and Adam's moments, each the flat float32 vector of include/iwae_amd.h's parameter order (4 x 1.8 MB for the 1-layer model).
+    The getters join the library's side streams first, so a deferred decoder update is in."""
+    os.makedirs(out_dir, exist_ok=True)
+    mom, vel, _ = net.get_adam_state()
+    for name, a in (("params", net.get_params()), ("grads", net.get_grads()), ("adam_m", mom), ("adam_v", vel)):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class _StdoutToStderr:
     """RCCL prints a version banner on STDOUT when its first communicator is made; the contract is ONE JSON line there.
     Everything before the result line runs with file descriptor 1 pointing at stderr."""
@@ -221,16 +236,22 @@ def run():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c1", help="BASELINE.json configs[0..3] (default c1 = configs[1], the headline)")
     ap.add_argument("--precision", choices=("bf16", "fp32"), default="bf16", help="GEMM arithmetic (iwae_config.precision); the headline is bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-llh-eval", action="store_true", help="skip the untimed k = 5000 evaluator run (profiling: keeps its kernels out of the statistics)")
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond the headline (per-kernel event pass + roofline, k = 5000 "
+                                                        "evaluator leg, CPU baseline, ELBO after the run); the --no-* switches below thin it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the parameters, gradient and Adam moments the last timed step "
+                                                                        "left as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-llh-eval", action="store_true", help="--full without the untimed k = 5000 evaluator run (profiling: keeps its kernels out of the statistics)")
     ap.add_argument("--settle", type=int, default=SETTLE_STEPS, help="untimed steps in front of the timed region in any case (profiling scripts pass 0: then exactly --warmup)")
-    ap.add_argument("--no-kernel-times", action="store_true", help="skip the per-kernel event pass behind the timed region (profiling)")
+    ap.add_argument("--no-kernel-times", action="store_true", help="--full without the per-kernel event pass behind the timed region (profiling)")
     ap.add_argument("--timing-every", type=int, default=TIMING_EVERY, help="the per-kernel event pass brackets the kernels of every n-th step")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="iwae_set_option switch for A/B measurements (repeatable; tools/README.md)")
     ap.add_argument("--lib", default=None, metavar="PATH", help="developer A/B only: load this build of libiwae_amd.so instead of the in-tree one (recorded in config.lib)")
     ap.add_argument("--force-dist", action="store_true", help="rehearse the data-parallel code path with ONE rank (trivial collectives)")
     ap.add_argument("--dp-torch", action="store_true", help="data-parallel exchange through torch.distributed.all_reduce instead of the library's own RCCL calls")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     force_dist = args.force_dist
     options = {}
     for kv in args.opt:
@@ -305,11 +326,13 @@ def run():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # per-kernel launch durations: a SEPARATE pass behind the timed region (HIP events on the stream each kernel runs on)
+    if args.dump_outputs and rank == 0:      # (before anything else runs a step: the state of the last TIMED step)
+        dump_outputs(net, args.dump_outputs)
+    # --full: per-kernel launch durations, a SEPARATE pass behind the timed region (HIP events on the stream each kernel runs on)
     models = kernel_models(cfg)
     ktimes = {k: (0.0, 0) for k in models}
     allreduce_us = None
-    if not args.no_kernel_times:
+    if args.full and not args.no_kernel_times:
         net.enable_timing(args.timing_every)
         for _ in range(TIMING_STEPS):
             step()
@@ -318,9 +341,9 @@ def run():
         if dp.in_library:      # the data-parallel step's two all-reduces (events around each ncclAllReduce on the stream that carries it)
             allreduce_us = {seg: round(net.kernel_time("allreduce_" + seg)[0], 2) for seg in ("enc", "dec")}
         net.enable_timing(0)
-    elbo = net.forward(x_np[lo:lo + B], K)["iwae_elbo"]
+    elbo = net.forward(x_np[lo:lo + B], K)["iwae_elbo"] if args.full else None
     llh_eval = None
-    if world == 1 and not args.no_llh_eval and cfg["layers"] == 1:      # the other half of BASELINE's metric: the test-LLH protocol of main.py:170-184 (k = 5000 per image), untimed extra
+    if args.full and world == 1 and not args.no_llh_eval and cfg["layers"] == 1:      # the other half of BASELINE's metric: the test-LLH protocol of main.py:170-184 (k = 5000 per image), untimed extra
         n_eval = 4190      # ten full launches of the evaluator (419 images x 5000 samples = 2^21 rows each at the reference's dims)
         xe = np.tile(x_np, (n_eval // x_np.shape[0] + 1, 1))[:n_eval]
         llh_eval = {"k": 5000, "images": n_eval}
@@ -364,9 +387,9 @@ def run():
                        # which exchange path ran, and over how many ranks RCCL itself says (ncclCommCount on the library's communicator)
                        "dp_path": dp.path, "rccl_ranks": rccl_ranks, "allreduce_us": allreduce_us, "settle_steps": settle, "options": options, "lib": args.lib,
                        "step_gemm_tflops": round(flop_step * world / (dt / args.steps) / 1e12, 1),
-                       "iwae_elbo_after": round(float(elbo), 3), "llh_eval_k5000": llh_eval},
+                       "iwae_elbo_after": round(float(elbo), 3) if elbo is not None else None, "llh_eval_k5000": llh_eval, "full": args.full},
         }
-        if dom:
+        if args.full and dom:
             dom_us, dom_n = launched[dom]
             km = models[dom]
             hbm_bound = km["flop"] / max(km["bytes"], 1) < RIDGE
@@ -394,12 +417,12 @@ def run():
                          "algorithmic_bytes": int(comp_b + act_b), "algorithmic_hbm_frac": round((comp_b + act_b) / (ms * 1e-3) / (PEAK_HBM_GBS * 1e9), 4),
                          "measured_hbm_bytes": step_hbm, "measured_hbm_frac": round(step_hbm / (ms * 1e-3) / (PEAK_HBM_GBS * 1e9), 4) if step_hbm else None},
             }
-        if not dom:      # float32 mode (one generic GEMM kernel, no per-kernel events): the step as a whole against the f32 MFMA peak
+        if args.full and not dom:      # float32 mode (one generic GEMM kernel, no per-kernel events): the step as a whole against the f32 MFMA peak
             out["roofline"] = {"bound": "mfma", "kernel": "gemm_f32_v2_kernel (every product of the step: v_mfma_f32_16x16x4_f32), whole step", "timed_as": "step",
                                "stream": "main + side (the decoder's weight gradients and its deferred update)", "achieved": round(flop_step / (ms * 1e-3) / 1e12, 2), "peak": peak_tf, "unit": "TFLOP/s",
                                "frac": round(flop_step / (ms * 1e-3) / (peak_tf * 1e12), 4), "traffic": None, "traffic_source": None,
                                "avg_launch_us": round(ms * 1e3, 2), "launches": args.steps, "flop_per_launch": flop_step}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         return out, dist
     return None, dist

@@ -3,6 +3,7 @@
 # An argument is a space-separated list of iwae_set_option switches: tools/dev/ab_bench.sh - no_bern_pipe=1 "wg16=160 no_side2=1" ...
 # (BENCH_ARGS: extra bench.py arguments, e.g. "--config c2")
 cd $GRAFT_REPO_ROOT
+BENCH_ARGS="--full $BENCH_ARGS"      # (the summary reads the roofline object and the ELBO after the run)
 for e in "$@"; do
   opts=""
   if [ "$e" != "-" ]; then for o in $e; do opts="$opts --opt $o"; done; fi

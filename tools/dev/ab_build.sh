@@ -7,7 +7,7 @@ REPS=${REPS:-3}
 for r in $(seq 1 $REPS); do
   for v in old new; do
     if [ $v = old ]; then cp $R/tools/dev/_old/libiwae_amd.so $R/iwae_amd/libiwae_amd.so; else cp /tmp/new.so $R/iwae_amd/libiwae_amd.so; fi
-    ms=$(python3 $R/bench.py --steps 150 --warmup 30 --no-cpu-baseline --no-llh-eval "$@" 2>/dev/null | python3 -c "
+    ms=$(python3 $R/bench.py --full --steps 150 --warmup 30 --no-cpu-baseline --no-llh-eval "$@" 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,13 +6,13 @@ set -u
 TAG=${1:-r05}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final_$TAG; mkdir -p "$O"
 cd $R
-python bench.py --steps 200 --warmup 5 > $O/bench_line_c1.json 2> $O/bench_c1.err; tail -c 300 $O/bench_line_c1.json; echo
-python bench.py --steps 20 --warmup 5 > $O/bench_line_driver_shape.json 2>> $O/bench_c1.err
-for c in c0 c2 c3; do python bench.py --config $c --steps 200 --warmup 5 --no-llh-eval > $O/bench_line_$c.json 2> $O/bench_$c.err; done
-python bench.py --precision fp32 --steps 60 --warmup 5 --no-llh-eval > $O/bench_line_c1_fp32.json 2> $O/bench_fp32.err
-python bench.py --config c0 --precision fp32 --steps 100 --warmup 5 --no-llh-eval --no-cpu-baseline > $O/bench_line_c0_fp32.json 2>> $O/bench_fp32.err
-for c in c2 c3; do python bench.py --config $c --precision fp32 --steps 60 --warmup 5 --no-llh-eval --no-cpu-baseline > $O/bench_line_${c}_fp32.json 2>> $O/bench_fp32.err; done
-python bench.py --force-dist --steps 200 --warmup 5 --no-llh-eval --no-cpu-baseline > $O/bench_line_c1_forcedist.json 2> $O/bench_forcedist.err
+python bench.py --full --steps 200 --warmup 5 > $O/bench_line_c1.json 2> $O/bench_c1.err; tail -c 300 $O/bench_line_c1.json; echo
+python bench.py --full --steps 20 --warmup 5 > $O/bench_line_driver_shape.json 2>> $O/bench_c1.err
+for c in c0 c2 c3; do python bench.py --full --config $c --steps 200 --warmup 5 --no-llh-eval > $O/bench_line_$c.json 2> $O/bench_$c.err; done
+python bench.py --full --precision fp32 --steps 60 --warmup 5 --no-llh-eval > $O/bench_line_c1_fp32.json 2> $O/bench_fp32.err
+python bench.py --full --config c0 --precision fp32 --steps 100 --warmup 5 --no-llh-eval --no-cpu-baseline > $O/bench_line_c0_fp32.json 2>> $O/bench_fp32.err
+for c in c2 c3; do python bench.py --full --config $c --precision fp32 --steps 60 --warmup 5 --no-llh-eval --no-cpu-baseline > $O/bench_line_${c}_fp32.json 2>> $O/bench_fp32.err; done
+python bench.py --full --force-dist --steps 200 --warmup 5 --no-llh-eval --no-cpu-baseline > $O/bench_line_c1_forcedist.json 2> $O/bench_forcedist.err
 for f in $O/bench_line_*.json; do python3 - "$f" <<'PY'
 import sys, json
 try:
