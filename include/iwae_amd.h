@@ -207,6 +207,28 @@ int iwae_set_eval_precision(iwae_handle h, int32_t precision);
  * src/iwae2.py:184-196, z = z2 [n,D2]: z1 ~ p(z1|z2) is drawn on the device (Philox), then decoded. */
 int iwae_decode(iwae_handle h, const float* z, int32_t n, float* probs);
 
+/* tasks/plot_task01.py:31-78 (true posterior on a latent grid) and the exact log p(x) of a low-dimensional latent model by quadrature.
+ * For image x_i and grid point z_g with log quadrature weight w_g (log_wq[g], or 0 when log_wq is NULL), l_g = decoder(z_g) in the eval
+ * precision (iwae_set_eval_precision) and
+ *   lj(i,g)   = sum_j [x_ij l_gj - softplus(l_gj)] + sum_d (-z_gd^2/2 - log(2 pi)/2)       (lpxz + lpz, src/iwae1.py:105-111)
+ *   log_px[i] = LSE_g (lj(i,g) + w_g)                                                      (merged in double)
+ *   post_mean, post_cov: mean and covariance of z under pi(i,g) = exp(lj + w_g - log_px[i])
+ *   q_mu, q_sigma: the encoder heads (src/iwae1.py:39-42); lq(i,g) = sum_d log N(z_gd; mu_id, sigma_id)
+ *   q_mass[i]    = sum_g exp(lq + w_g)               (near 1: the grid covers and resolves q(z|x_i))
+ *   kl_q_post[i] = sum_g exp(lq + w_g) (lq - lj + log_px[i])   = KL(q(z|x) || p(z|x)) on the grid (log p(x) = ELBO + KL)
+ *   log_joint    = lj [N, G], only materialised when asked.
+ * 1-layer unconditional models with n_latent <= 4 and x_dim <= 800 only; x must be binary (checked on the device); N, G > 0: otherwise
+ * IWAE_ERR_ARG.  G is processed in chunks (option grid_chunk, default 32 768 points, ~256 MB of chunk-sized buffers); an image's results
+ * depend on G, the grid and the chunk size only (not on N, its position or the other images) and are bitwise reproducible.
+ * x, z, log_wq: host or device; every output: host or device, [N], [N,D], [N,D,D] as named, or NULL (log_px is required). */
+int iwae_grid_posterior(iwae_handle h, const float* x, int32_t N,          /* [N, x_dim], values in {0,1}; host or device */
+                        const float* z, const float* log_wq, int32_t G,     /* grid [G, D]; log quadrature weight per point [G] or NULL (= 0) */
+                        double* log_px,                                     /* [N]            required */
+                        float* post_mean, float* post_cov,                  /* [N, D], [N, D, D]   or NULL */
+                        float* q_mu, float* q_sigma,                        /* [N, D] encoder heads (src/iwae1.py:39-42) or NULL */
+                        float* q_mass, float* kl_q_post,                    /* [N]            or NULL */
+                        float* log_joint);                                  /* [N, G] or NULL (only materialised when asked) */
+
 /* Data pipeline on the device (main.py:59-65,117-120 + src/utils.py:26-27): the grey-level training set
  * stays resident in HBM as uint8 [n, x_dim]; every epoch gets a visiting order (tf.data shuffle) and a
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),

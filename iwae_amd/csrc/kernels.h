@@ -396,4 +396,40 @@ void launch_sigmoid_f32(float* v, size_t n, hipStream_t st);
 void launch_export_mat(const float* in, int B, int k, int X, float* out, hipStream_t st);
 void launch_concat_f32(const float* a, int na, const float* b, int nb, int rows, float* out, hipStream_t st);
 
+// ---- latent-grid quadrature (grid_kernels.hip; iwae_grid_posterior): the true posterior p(z|x) of a model with a few latent
+// dimensions on a grid of points z_g with log weights w_g, and log p(x) = LSE_g (log p(x|z_g) + log p(z_g) + w_g)
+#define GRID_D_MAX 4            // latent dimensions
+#define GRID_XP_MAX 800         // padded pixels: the score kernel keeps an image's 25 k-steps of x in registers
+#define GRID_RANGE 1024         // grid rows per partial state: a chunk of Gc rows is cut into ceil(Gc / GRID_RANGE) ranges (depends on Gc only)
+// per-image partial state: [0] running max m, [1] sum s = sum exp(t - m), [2..5] S1_d = sum e (z - mu)_d, [6..15] S2 (packed upper
+// triangle, grid_tri(d, e)) = sum e (z - mu)_d (z - mu)_e, [16] Q = sum exp(lq + w), [17] A = sum exp(lq + w) (lq - lj)
+enum { GRID_ST = 18, GRID_S1 = 2, GRID_S2 = 6, GRID_Q = 16, GRID_A = 17 };
+__host__ __device__ inline int grid_tri(int d, int e) { return d * GRID_D_MAX - d * (d - 1) / 2 + (e - d); }
+struct GridPrepArgs {
+    const float* logits; int ldl;          // decoder logits of the chunk's points, fp32 [Gc][ldl]
+    const float* z; const float* lw;       // the chunk's points [Gc][D] and log weights [Gc] (null: 0)
+    int Gc, Gcp, X, Xp, D;                 // rows, rows written (a multiple of 16; rows >= Gc are zero), pixels, padded pixels, latent dims
+    uint16_t *Lhi, *Llo;                   // out: bf16(l), bf16(l - bf16(l)) [Gcp][Xp], pixels >= X zero
+    float* c; float4* zc; float* w;        // out: c_g = log p(z_g) - sum_j softplus(l_gj) + w_g, z_g padded to 4, w_g   [Gcp]
+};
+struct GridScoreArgs {
+    const uint16_t* XB; int Xp;            // images as bf16 [round_up(N, 64)][Xp] (exact: x in {0,1}), pad rows / pixels zero
+    const uint16_t *Lhi, *Llo; const float* c; const float4* zc; const float* w;      // grid_prep_kernel's outputs
+    const float* head; int ldh, soff;      // encoder heads: mu_id at head[i*ldh + d], sigma_id at head[i*ldh + soff + d]
+    int N, Gc, nsplit;
+    float* part;                           // out: [nsplit][N][GRID_ST]
+    float* log_joint; long ldlj; long lj_col;      // out (or null): log p(x_i|z_g) + log p(z_g) at [i*ldlj + lj_col + g]
+};
+struct GridMergeArgs {
+    const float* part; int nsplit, N, D;
+    double* run;                           // [N][GRID_ST] running state across the chunks of G
+    int first, last;                       // first chunk: start from the empty state; last chunk: finalise into the outputs
+    const float* head; int ldh;            // mu (the moments are taken about it)
+    double* log_px; float *mean, *cov, *qmass, *kl;     // [N], [N][D], [N][D][D], [N], [N]
+};
+void launch_grid_prep_x(const float* x, int N, int X, int Np, int Xp, uint16_t* XB, int* nonbinary, hipStream_t st);
+void launch_grid_prep(const GridPrepArgs& a, hipStream_t st);
+void launch_grid_score(const GridScoreArgs& a, int D, hipStream_t st);
+void launch_grid_merge(const GridMergeArgs& a, hipStream_t st);
+
 }  // namespace iwae

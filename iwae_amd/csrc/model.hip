@@ -152,7 +152,10 @@ struct iwae_model {
     bool in_eval_llh = false;                 // iwae_eval_llh's launches need log_w only: no second (DReG) density per sample (round 5: ~14 % of the sampling pass)
     DevBuf eval_x, eval_lme;                  // iwae_eval_llh: the images (uploaded once) and the per-image log-mean-exps of every launch
     int eval_rows = 0;                        // data rows per evaluator launch (option eval_rows): images x samples, k chunked beyond it; 0 = eval_rows_auto()
-    int eval_precision = IWAE_PREC_FP32;      // arithmetic of iwae_eval_llh (iwae_set_eval_precision)
+    int eval_precision = IWAE_PREC_FP32;      // arithmetic of iwae_eval_llh and iwae_grid_posterior (iwae_set_eval_precision)
+    // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT) and the call's buffers
+    int grid_chunk = 0;
+    struct GridWs { DevBuf x, xb, xP, flag, head, z, lw, zP, h1, h2, logits, lhi, llo, c, zc, w, part, run, lpx, mean, cov, qmass, kl, lj; } grid;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
@@ -2455,6 +2458,12 @@ void iwae_destroy(iwae_handle m) {
                       &m->dzdir, &m->scratch, &m->ds_data, &m->ds_order, &m->dstamps, &m->px_part, &m->dg2_part, &m->cond, &m->condP, &m->epsc[0][0], &m->epsc[0][1], &m->epsc[1][0], &m->epsc[1][1], &m->epsc[2][0], &m->epsc[2][1], &m->eval_x, &m->eval_lme,
                       &m->ds_labels, &m->epsm[0][0], &m->epsm[0][1], &m->epsm[1][0], &m->epsm[1][1]};
     for (DevBuf* b : bufs) free_buf(*b);
+    {
+        iwae_model::GridWs& g = m->grid;
+        DevBuf* bb[] = {&g.x, &g.xb, &g.xP, &g.flag, &g.head, &g.z, &g.lw, &g.zP, &g.h1, &g.h2, &g.logits, &g.lhi, &g.llo, &g.c, &g.zc, &g.w,
+                        &g.part, &g.run, &g.lpx, &g.mean, &g.cov, &g.qmass, &g.kl, &g.lj};
+        for (DevBuf* b : bb) free_buf(*b);
+    }
     BlockWs* bw[] = {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior};
     for (BlockWs* w : bw) {
         DevBuf* bb[] = {&w->h1P, &w->h2P, &w->head, &w->dheadP, &w->d2P, &w->d1P, &w->dx};
@@ -2711,6 +2720,7 @@ int iwae_set_option(iwae_handle m, const char* name, int64_t value) {
     else if (n == "dec_rows") m->dec_rows_max = iv;                   // dec_bwd_rows_kernel up to this many rows
     else if (n == "no_wg7") m->allow_wg7 = !on;                       // the 16-wave weight-gradient shapes everywhere
     else if (n == "wg9") m->wg_shape9 = iv;                           // bit mask: layers that take the 8 + 8-wave / 128-feature wgradws shape
+    else if (n == "grid_chunk") m->grid_chunk = iv > 0 ? std::max(16, iv) : 0;      // iwae_grid_posterior: grid points per chunk (0: the default)
     else if (n == "eval_rows") m->eval_rows = iv > 0 ? std::max(64, iv) : 0;       // data rows per evaluator launch
     else if (n == "no_bern_pipe") m->allow_bern_pipe = !on;           // the Bernoulli forward on dense_kernel<EPI_BERN>
     else if (n == "no_block_fused") m->allow_block_fused = !on;       // a BasicBlock on few rows as three dense_kernel launches
@@ -3007,6 +3017,140 @@ int iwae_decode(iwae_handle m, const float* z, int32_t n, float* probs) {
     CHK(dense_fwd(m, m->dec1[1], EPI_TANH, ptr<uint16_t>(w.g1P), n, ptr<uint16_t>(w.g2P), nullptr, 0));
     CHK(dense_fwd(m, m->dec1[2], EPI_SIGMOID, ptr<uint16_t>(w.g2P), n, nullptr, ptr<float>(m->scratch), Xp));
     HIPCHK(hipMemcpy2DAsync(probs, (size_t)m->X * 4, m->scratch.p, (size_t)Xp * 4, (size_t)m->X * 4, n, hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    m->have_forward = false;
+    return IWAE_OK;
+}
+
+// Grid points per chunk of iwae_grid_posterior: ~8 KB of chunk-sized buffers per point at 784 pixels (logits, L_hi + L_lo, two hidden layers
+// in float32), so 32 768 points keep them near 256 MB whatever G is.
+#define GRID_CHUNK_DEFAULT 32768
+
+int iwae_grid_posterior(iwae_handle m, const float* x, int32_t N, const float* z, const float* log_wq, int32_t G, double* log_px,
+                        float* post_mean, float* post_cov, float* q_mu, float* q_sigma, float* q_mass, float* kl_q_post, float* log_joint) {
+    if (!m || !x || !z || !log_px) return fail(IWAE_ERR_ARG, "grid_posterior: need x, z and log_px");
+    if (N <= 0 || G <= 0) return fail(IWAE_ERR_ARG, "grid_posterior: N and G must be positive");
+    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "grid_posterior: only the 1-layer model (the 2-layer model needs a nested integral over z1)");
+    if (m->C != 0) return fail(IWAE_ERR_ARG, "grid_posterior: only the unconditional model (cond_dim = 0)");
+    if (m->D[0] > GRID_D_MAX) return fail(IWAE_ERR_ARG, "grid_posterior: needs n_latent <= 4 (got " + std::to_string(m->D[0]) + ")");
+    if (m->Xp32 > GRID_XP_MAX) return fail(IWAE_ERR_ARG, "grid_posterior: needs x_dim <= " + std::to_string(GRID_XP_MAX));
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CHK(join_side(m));      // the parameters a deferred update may still be writing
+    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
+    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
+    hipStream_t st = m->stream;
+    iwae_model::GridWs& w = m->grid;
+    const int D = m->D[0], Dp = m->Dp[0], X = m->X, Xp = m->Xp32, Np = round_up(N, 64);
+    const bool f32 = m->eval_precision == IWAE_PREC_FP32;
+    // ---- images: bf16 copy for the score kernel + the binary check (the scores rely on x being exact in bf16)
+    const float* xd = x;
+    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * X * 4)); xd = ptr<float>(w.x); }
+    CHK(ensure(w.xb, (size_t)Np * Xp * 2, st));
+    CHK(ensure(w.flag, 4, st));
+    HIPCHK(hipMemsetAsync(w.flag.p, 0, 4, st));
+    launch_grid_prep_x(xd, N, X, Np, Xp, ptr<uint16_t>(w.xb), ptr<int>(w.flag), st);
+    HIPCHK(hipGetLastError());
+    int nonbinary = 0;
+    HIPCHK(hipMemcpyAsync(&nonbinary, w.flag.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nonbinary) return fail(IWAE_ERR_ARG, "grid_posterior: x must be binary (every value 0 or 1)");
+    // ---- encoder heads mu, sigma of the N images (src/iwae1.py:39-42), in the eval precision
+    const float* head;
+    int ldh;
+    if (f32) {
+        CHK(ensure(w.head, (size_t)N * 2 * Dp * 4, st));
+        m->in_eval_llh = true;      // (no K split of the few-row products: an image's heads must not depend on N)
+        const int rc = f32_block_fwd(m, m->enc1[0].sub[0], m->f32.enc1, xd, X, N, ptr<float>(w.head), Dp, false);
+        m->in_eval_llh = false;
+        CHK(rc);
+        head = ptr<float>(w.head); ldh = 2 * Dp;
+    } else {
+        const int Nbp = round_up(N, 128);
+        CHK(ensure(w.xP, (size_t)Nbp * Xp * 2, st));
+        launch_prep_rows(xd, nullptr, N, X, 0, Xp, Nbp, ptr<uint16_t>(w.xP), st);
+        CHK(block_alloc(m, m->enc1, m->wenc1, N, Nbp, false, false));
+        CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(w.xP), N));
+        head = ptr<float>(m->wenc1.head); ldh = m->enc1[2].Np32;
+    }
+    if (q_mu) HIPCHK(hipMemcpy2DAsync(q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
+    if (q_sigma) HIPCHK(hipMemcpy2DAsync(q_sigma, (size_t)D * 4, head + Dp, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
+    // ---- G in chunks: decoder logits -> prep -> score -> merge into the running per-image state
+    const int chunk = m->grid_chunk > 0 ? m->grid_chunk : GRID_CHUNK_DEFAULT;
+    const int gmax = std::min(chunk, (int)G), gmaxp = round_up(gmax, 128), H = m->H[0], Hp = m->dec1[0].Np32;
+    CHK(ensure(w.run, (size_t)N * GRID_ST * 8, st));
+    CHK(ensure(w.lpx, (size_t)N * 8, st));
+    CHK(ensure(w.mean, (size_t)N * D * 4, st));
+    CHK(ensure(w.cov, (size_t)N * D * D * 4, st));
+    CHK(ensure(w.qmass, (size_t)N * 4, st));
+    CHK(ensure(w.kl, (size_t)N * 4, st));
+    CHK(ensure(w.z, (size_t)gmax * D * 4, st));
+    if (log_wq) CHK(ensure(w.lw, (size_t)gmax * 4, st));
+    CHK(ensure(w.logits, (size_t)gmaxp * Xp * 4, st));
+    CHK(ensure(w.lhi, (size_t)gmaxp * Xp * 2, st));
+    CHK(ensure(w.llo, (size_t)gmaxp * Xp * 2, st));
+    CHK(ensure(w.c, (size_t)gmaxp * 4, st));
+    CHK(ensure(w.zc, (size_t)gmaxp * 16, st));
+    CHK(ensure(w.w, (size_t)gmaxp * 4, st));
+    if (f32) {
+        CHK(ensure(w.h1, (size_t)gmax * H * 4, st));
+        CHK(ensure(w.h2, (size_t)gmax * H * 4, st));
+    } else {
+        CHK(ensure(w.zP, (size_t)gmaxp * Dp * 2, st));
+        CHK(ensure(w.h1, (size_t)gmaxp * Hp * 2, st));
+        CHK(ensure(w.h2, (size_t)gmaxp * Hp * 2, st));
+    }
+    const int nsplit_max = (gmax + GRID_RANGE - 1) / GRID_RANGE;
+    CHK(ensure(w.part, (size_t)nsplit_max * N * GRID_ST * 4, st));
+    float* lj = nullptr;
+    if (log_joint) {
+        if (is_device_ptr(log_joint, m->cfg.device)) lj = log_joint;
+        else { CHK(ensure(w.lj, (size_t)N * G * 4, st)); lj = ptr<float>(w.lj); }
+    }
+    const KerasLayer* d1 = &m->klayers[m->dec1[0].sub[0]];
+    for (int c0 = 0; c0 < G; c0 += chunk) {
+        const int Gc = std::min(chunk, (int)G - c0), Gcp = round_up(Gc, 128);
+        HIPCHK(hipMemcpyAsync(w.z.p, z + (size_t)c0 * D, (size_t)Gc * D * 4, hipMemcpyDefault, st));
+        if (log_wq) HIPCHK(hipMemcpyAsync(w.lw.p, log_wq + c0, (size_t)Gc * 4, hipMemcpyDefault, st));
+        // decoder logits l_g (src/iwae1.py:72-75), as iwae_decode / forward_f32 compute them
+        if (f32) {
+            CHK(f32_fwd(m, d1[0], ptr<float>(w.z), D, Gc, ptr<float>(w.h1), H, GEMM_EPI_TANH));
+            CHK(f32_fwd(m, d1[1], ptr<float>(w.h1), H, Gc, ptr<float>(w.h2), H, GEMM_EPI_TANH));
+            CHK(f32_fwd(m, d1[2], ptr<float>(w.h2), H, Gc, ptr<float>(w.logits), Xp, GEMM_EPI_NONE));
+        } else {
+            launch_prep_rows(ptr<float>(w.z), nullptr, Gc, D, 0, Dp, Gcp, ptr<uint16_t>(w.zP), st);
+            CHK(dense_fwd(m, m->dec1[0], EPI_TANH, ptr<uint16_t>(w.zP), Gc, ptr<uint16_t>(w.h1), nullptr, 0));
+            CHK(dense_fwd(m, m->dec1[1], EPI_TANH, ptr<uint16_t>(w.h1), Gc, ptr<uint16_t>(w.h2), nullptr, 0));
+            // (EPI_HEAD on the output layer: fp32 logits with the bias -- its exp split lies beyond the one-sub-layer map; EPI_F32 adds no bias)
+            CHK(dense_fwd(m, m->dec1[2], EPI_HEAD, ptr<uint16_t>(w.h2), Gc, nullptr, ptr<float>(w.logits), Xp));
+        }
+        GridPrepArgs pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.logits = ptr<float>(w.logits); pa.ldl = Xp; pa.z = ptr<float>(w.z); pa.lw = log_wq ? ptr<float>(w.lw) : nullptr;
+        pa.Gc = Gc; pa.Gcp = round_up(Gc, 16); pa.X = X; pa.Xp = Xp; pa.D = D;
+        pa.Lhi = ptr<uint16_t>(w.lhi); pa.Llo = ptr<uint16_t>(w.llo); pa.c = ptr<float>(w.c); pa.zc = ptr<float4>(w.zc); pa.w = ptr<float>(w.w);
+        launch_grid_prep(pa, st);
+        HIPCHK(hipGetLastError());
+        GridScoreArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.XB = ptr<uint16_t>(w.xb); sa.Xp = Xp; sa.Lhi = pa.Lhi; sa.Llo = pa.Llo; sa.c = pa.c; sa.zc = pa.zc; sa.w = pa.w;
+        sa.head = head; sa.ldh = ldh; sa.soff = Dp; sa.N = N; sa.Gc = Gc; sa.nsplit = (Gc + GRID_RANGE - 1) / GRID_RANGE;
+        sa.part = ptr<float>(w.part); sa.log_joint = lj; sa.ldlj = G; sa.lj_col = c0;
+        launch_grid_score(sa, D, st);
+        HIPCHK(hipGetLastError());
+        GridMergeArgs ma;
+        memset(&ma, 0, sizeof(ma));
+        ma.part = sa.part; ma.nsplit = sa.nsplit; ma.N = N; ma.D = D; ma.run = ptr<double>(w.run);
+        ma.first = c0 == 0; ma.last = c0 + Gc >= G; ma.head = head; ma.ldh = ldh;
+        ma.log_px = ptr<double>(w.lpx); ma.mean = ptr<float>(w.mean); ma.cov = ptr<float>(w.cov); ma.qmass = ptr<float>(w.qmass); ma.kl = ptr<float>(w.kl);
+        launch_grid_merge(ma, st);
+        HIPCHK(hipGetLastError());
+    }
+    CHK(copy_out(m, log_px, w.lpx.p, (size_t)N * 8));
+    if (post_mean) CHK(copy_out(m, post_mean, w.mean.p, (size_t)N * D * 4));
+    if (post_cov) CHK(copy_out(m, post_cov, w.cov.p, (size_t)N * D * D * 4));
+    if (q_mass) CHK(copy_out(m, q_mass, w.qmass.p, (size_t)N * 4));
+    if (kl_q_post) CHK(copy_out(m, kl_q_post, w.kl.p, (size_t)N * 4));
+    if (log_joint && lj != log_joint) CHK(copy_out(m, log_joint, lj, (size_t)N * G * 4));
     HIPCHK(hipStreamSynchronize(st));
     m->have_forward = false;
     return IWAE_OK;

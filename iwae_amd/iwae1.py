@@ -2,6 +2,7 @@
 model(x, n_samples, beta), train_step, val_step, sample (src/iwae1.py:88-178)."""
 import numpy as np
 
+from . import utils
 from ._shim import BaseIWAE, _Sub, as_tensor
 
 
@@ -19,3 +20,41 @@ class IWAE(BaseIWAE):
         probs = self._net.decode(np.asarray(z, dtype=np.float32))
         x_sample = (np.random.random_sample(probs.shape) < probs).astype(np.float32)
         return as_tensor(x_sample), as_tensor(probs)
+
+    # ---- ground truth for low-dimensional latents (tasks/plot_task01.py:31-78): quadrature on a latent grid
+    def _grid_scope(self):
+        if self._net.cond_dim:
+            raise NotImplementedError("the grid posterior covers the unconditional 1-layer model only (a conditional model needs the label of "
+                                      "every image inside the decoder and the prior)")
+
+    def true_posterior(self, x, z_grid, log_wq=None):
+        """True posterior p(z|x) on the points z_grid [G, D] (log quadrature weights log_wq [G], None: 0) -- the arrays
+        tasks/plot_task01.py:61-72 draws.  Returns iwae_grid_posterior's dict (log_px, post_mean, post_cov, q_mu, q_sigma, q_mass,
+        kl_q_post, log_joint) plus log_posterior = log_joint - log_px, the log density of p(z|x) at the points (normalised: logsumexp
+        over the grid of log_posterior + w is 0; log_posterior + w is the posterior mass of each cell, what plot_task01.py:60-63 draws
+        on a uniform grid) and variational_posterior = log q(z_g|x) (the encoder's Normal, src/iwae1.py:39-42), both [N, G]."""
+        self._grid_scope()
+        x = np.asarray(x, dtype=np.float32).reshape(-1, self._net.x_dim)
+        z_grid = np.asarray(z_grid, dtype=np.float32)
+        res = self._net.grid_posterior(x, z_grid, log_wq, log_joint=True)
+        res["log_posterior"] = res["log_joint"].astype(np.float64) - res["log_px"][:, None]
+        zg = z_grid.reshape(z_grid.shape[0], -1).astype(np.float64)
+        mu, sg = res["q_mu"].astype(np.float64), res["q_sigma"].astype(np.float64)
+        u = (zg[None, :, :] - mu[:, None, :]) / sg[:, None, :]
+        res["variational_posterior"] = np.sum(-0.5 * u * u - np.log(sg)[:, None, :] - 0.5 * np.log(2 * np.pi), axis=-1)
+        return res
+
+    def true_log_likelihood(self, X, extent=(-5.0, 5.0), n_per_dim=None, batch=10000):
+        """Test-set log p(x) by quadrature on ONE uniform grid [extent]^D shared by every image (D <= 2; n_per_dim points per dimension,
+        default 1000 for D = 2, 20000 for D = 1), the images fed `batch` at a time.  Returns (mean, per_image float64 [N]).  Check the
+        grid with true_posterior's q_mass first: near 1 means the grid covers and resolves q(z|x)."""
+        self._grid_scope()
+        D = self._net.n_latent[0]
+        if D > 2:
+            raise NotImplementedError("true_log_likelihood: a shared uniform grid is for 1 or 2 latent dimensions (got %d); call "
+                                      "true_posterior with a grid of your own" % D)
+        n = n_per_dim or (1000 if D == 2 else 20000)
+        z, lw = utils.latent_grid([extent] * D, n)
+        X = np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim)
+        per = np.concatenate([self._net.grid_posterior(X[i:i + batch], z, lw)["log_px"] for i in range(0, X.shape[0], batch)])
+        return float(np.mean(per)), per

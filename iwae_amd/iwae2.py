@@ -21,3 +21,10 @@ class IWAE(BaseIWAE):
         probs = self._net.decode(np.asarray(z2, dtype=np.float32))
         x_sample = (np.random.random_sample(probs.shape) < probs).astype(np.float32)
         return as_tensor(x_sample), as_tensor(probs)
+
+    def true_posterior(self, x, z_grid, log_wq=None):
+        raise NotImplementedError("the grid posterior covers the 1-layer model only: p(x) of the 2-layer model needs a nested integral over z1 "
+                                  "for every z2 of the grid")
+
+    def true_log_likelihood(self, X, extent=(-5.0, 5.0), n_per_dim=None, batch=10000):
+        self.true_posterior(X, None)

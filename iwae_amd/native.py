@@ -264,6 +264,34 @@ class NativeModel:
         check(self.lib.iwae_decode(self.h, z.ctypes.data, z.shape[0], out.ctypes.data))
         return out
 
+    def grid_posterior(self, x, z, log_wq=None, log_joint=False):
+        """iwae_grid_posterior: the true posterior p(z|x) and log p(x) of each image on the grid z [G, D] with log quadrature weights
+        log_wq [G] (None: 0).  Returns log_px [N] (float64), post_mean [N, D], post_cov [N, D, D], q_mu, q_sigma [N, D], q_mass [N],
+        kl_q_post [N] and, with log_joint=True, log_joint [N, G] = log p(x|z_g) + log p(z_g)."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        N, D = x.shape[0], self.n_latent[0]
+        z = _f32(z)
+        if z.ndim == 1 and D == 1:
+            z = z.reshape(-1, 1)
+        if z.ndim != 2 or z.shape[1] != D:
+            raise ValueError("grid_posterior: z must be [G, %d] (the latent width), got %s" % (D, z.shape))
+        G = z.shape[0]
+        lw = None
+        if log_wq is not None:
+            lw = _f32(log_wq).ravel()
+            if lw.size != G:
+                raise ValueError("grid_posterior: log_wq must have one entry per grid point (%d), got %d" % (G, lw.size))
+        out = {"log_px": np.empty(N, dtype=np.float64), "post_mean": np.empty((N, D), dtype=np.float32),
+               "post_cov": np.empty((N, D, D), dtype=np.float32), "q_mu": np.empty((N, D), dtype=np.float32),
+               "q_sigma": np.empty((N, D), dtype=np.float32), "q_mass": np.empty(N, dtype=np.float32),
+               "kl_q_post": np.empty(N, dtype=np.float32)}
+        if log_joint:
+            out["log_joint"] = np.empty((N, G), dtype=np.float32)
+        ptrs = [out[k].ctypes.data for k in ("log_px", "post_mean", "post_cov", "q_mu", "q_sigma", "q_mass", "kl_q_post")]
+        check(self.lib.iwae_grid_posterior(self.h, x.ctypes.data, N, z.ctypes.data, lw.ctypes.data if lw is not None else None, G, *ptrs,
+                                           out["log_joint"].ctypes.data if log_joint else None))
+        return out
+
     # ---- resident dataset (device-side shuffle order + dynamic binarisation) -------------------
     def dataset_upload(self, gray_u8):
         g = np.ascontiguousarray(gray_u8, dtype=np.uint8).reshape(-1, self.x_dim)

@@ -16,6 +16,23 @@ def bernoullisample(x):
     return np.random.binomial(1, x, size=x.shape).astype('float32')
 
 
+def latent_grid(ranges, n):
+    """Uniform latent grid in the point order of tasks/plot_task01.py:22-29 (get_grid): a meshgrid of linspaces, so for two dimensions
+    the values of one point per grid cell reshape(n2, n1) into the image.  ranges: one (lo, hi) per latent dimension; n: points per
+    dimension (an int or one per dimension).  Returns (points [G, D] float32, log_cell_weight [G] float32): the log of the cell volume
+    prod_d (hi_d - lo_d) / (n_d - 1), the weight of a Riemann sum of the density over the box."""
+    ranges = [tuple(map(float, r)) for r in ranges]
+    D = len(ranges)
+    ns = [int(n)] * D if np.ndim(n) == 0 else [int(v) for v in n]
+    if len(ns) != D or min(ns) < 2:
+        raise ValueError("latent_grid: need at least 2 points in each of the %d dimensions" % D)
+    axes = [np.linspace(lo, hi, k) for (lo, hi), k in zip(ranges, ns)]
+    mesh = np.meshgrid(*axes)
+    points = np.stack([m.reshape(-1) for m in mesh], axis=1).astype(np.float32)
+    log_cell = float(np.sum([np.log((hi - lo) / (k - 1)) for (lo, hi), k in zip(ranges, ns)]))
+    return points, np.full(points.shape[0], log_cell, dtype=np.float32)
+
+
 class MyMetric():
     """src/utils.py:30-45: list-append mean."""
 
