@@ -229,6 +229,24 @@ int iwae_grid_posterior(iwae_handle h, const float* x, int32_t N,          /* [N
                         float* q_mass, float* kl_q_post,                    /* [N]            or NULL */
                         float* log_joint);                                  /* [N, G] or NULL (only materialised when asked) */
 
+/* Active units (Burda et al. section 5.2; the reference's README TODO): for unit u of stochastic layer l, A_u = Cov_x(E_q[u|x]), the
+ * population variance over the N images (divide by N), in double; the unit is active if A_u > 1e-2.
+ *   layer 1: E_q[z1|x] = mu1(x), the encoder head (src/iwae1.py:39-42, src/iwae2.py:58-60): no sampling.
+ *   layer 2: E_q[z2|x] = E_{z1 ~ q(z1|x)}[mu2(z1)] (mu2: the q(z2|z1) head, src/iwae2.py:61-65), estimated from k draws of
+ *            z1 = mu1 + sigma1 eps; z2 is never sampled (the Rao-Blackwellised estimate).  The Monte Carlo error adds about
+ *            E_x Var(mu2)/k to A_u, negligible at k = 5000.
+ * Arithmetic in the eval precision (iwae_set_eval_precision).  Device draws (eps == NULL) are exactly those iwae_eval_llh would use at
+ * the same step, offset, N and k (latent stream 0, row (batch_offset + i) k + s); a 2-layer call advances the noise step by one, a
+ * 1-layer call ignores k and eps, draws nothing and leaves the step alone.  No launch holds more than eval_rows per-sample rows.
+ * An image's post_mean depends only on the weights, the image, k and its draws (not on N, its position, eval_rows or the other
+ * images) and is bitwise reproducible; activity and data_mean come from the per-image means in an order fixed by N.
+ * Conditional models, N <= 0, k <= 0 (2-layer) or activity == NULL: IWAE_ERR_ARG. */
+int iwae_latent_activity(iwae_handle h, const float* x, int32_t N,   /* [N, x_dim], host or device, any values in [0,1] */
+                         int32_t k, const float* eps,                /* 2-layer: z1 draws per image; eps [k, N, D1] (reference order) or NULL */
+                         double* activity,                           /* [D1 (+ D2)] required: A_u, layer 1's units first */
+                         double* data_mean,                          /* [D1 (+ D2)] or NULL: mean over x of E_q[u|x] */
+                         float* post_mean);                          /* [N, D1 (+ D2)] or NULL: E_q[u|x] per image */
+
 /* Data pipeline on the device (main.py:59-65,117-120 + src/utils.py:26-27): the grey-level training set
  * stays resident in HBM as uint8 [n, x_dim]; every epoch gets a visiting order (tf.data shuffle) and a
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),

@@ -432,4 +432,32 @@ void launch_grid_prep(const GridPrepArgs& a, hipStream_t st);
 void launch_grid_score(const GridScoreArgs& a, int D, hipStream_t st);
 void launch_grid_merge(const GridMergeArgs& a, hipStream_t st);
 
+// ---- active units (activity_kernels.hip; iwae_latent_activity): per-unit Cov_x(E_q[u|x]).  An image's mu2 rows are summed per block of
+// ACT_BLOCK samples into a partial [image][block][D1]; the statistics kernel folds the partials and reduces over the images in double
+#define ACT_BLOCK 128
+struct ActChainArgs {                 // act_chain_kernel: the 2-layer model's q(z2|z1) mean on nb images x kn samples, summed per block
+    const char *img1, *img2, *imgh;   // MG-major forward images of encode_z1_to_z2: l1 (KT0 k-steps), l2, head (KTH k-steps each; mu groups first)
+    const float* head1; int ldH1;     // q(z1|x) heads of this launch's images [nb][ldH1] (mu1 | sigma1 at 32*KT0)
+    EpsSrc eps1;                      // the draws of z1 (user [k][B][D0] at this launch's first sample and image, or Philox with k_total set)
+    int kn, D0, D1;                   // samples per image in this launch, latent widths of z1 and z2
+    float* part; int nblk;            // out: [N][nblk][D1] partial sums of mu2, nblk = ceil(k / ACT_BLOCK)
+    int img0, blk0;                   // this launch's first image and first block
+};
+struct ActPartialArgs {               // act_partial_kernel: the same partials from mu2 rows [nb * kn][ldh] that composed launches made
+    const float* head; int ldh;
+    int nb, kn, D1;
+    float* part; int nblk, img0, blk0;
+};
+struct ActStatsArgs {                 // act_stats_kernel: one unit per workgroup
+    const float* src; long ld_img; int ld_blk, nblk;   // image i's partials of unit u at src[i*ld_img + j*ld_blk + u], j < nblk
+    double kdiv;                      // per-image mean = (sum of the partials, double) / kdiv
+    int N, D;                         // images, units of this layer
+    float* post_mean; int ldpm, col;  // out: [N][ldpm], this layer's units from column col
+    double *activity, *data_mean;     // out: [.] from index col
+};
+bool act_chain_ok(int KT0, int KTH, int KT1);
+void launch_act_chain(const ActChainArgs& a, int nb, hipStream_t st);
+void launch_act_partial(const ActPartialArgs& a, hipStream_t st);
+void launch_act_stats(const ActStatsArgs& a, hipStream_t st);
+
 }  // namespace iwae

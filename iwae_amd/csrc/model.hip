@@ -156,6 +156,9 @@ struct iwae_model {
     // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT) and the call's buffers
     int grid_chunk = 0;
     struct GridWs { DevBuf x, xb, xP, flag, head, z, lw, zP, h1, h2, logits, lhi, llo, c, zc, w, part, run, lpx, mean, cov, qmass, kl, lj; } grid;
+    // iwae_latent_activity's buffers: the images, the chunk's draws, z1 rows and q(z2|z1) activations of the composed paths, the block partials
+    // of mu2 [N][blocks][D2] and the outputs
+    struct ActWs { DevBuf x, xP, head, eps, z, rows, part, pm, act, dm; BlockWs blk; F32Block f32; } act;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
@@ -2464,6 +2467,12 @@ void iwae_destroy(iwae_handle m) {
                         &g.part, &g.run, &g.lpx, &g.mean, &g.cov, &g.qmass, &g.kl, &g.lj};
         for (DevBuf* b : bb) free_buf(*b);
     }
+    {
+        iwae_model::ActWs& a = m->act;
+        DevBuf* bb[] = {&a.x, &a.xP, &a.head, &a.eps, &a.z, &a.rows, &a.part, &a.pm, &a.act, &a.dm, &a.blk.h1P, &a.blk.h2P, &a.blk.head,
+                        &a.blk.dheadP, &a.blk.d2P, &a.blk.d1P, &a.blk.dx, &a.f32.h1, &a.f32.h2, &a.f32.dhead, &a.f32.d2, &a.f32.d1, &a.f32.dx};
+        for (DevBuf* b : bb) free_buf(*b);
+    }
     BlockWs* bw[] = {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior};
     for (BlockWs* w : bw) {
         DevBuf* bb[] = {&w->h1P, &w->h2P, &w->head, &w->dheadP, &w->d2P, &w->d1P, &w->dx};
@@ -3026,6 +3035,30 @@ int iwae_decode(iwae_handle m, const float* z, int32_t n, float* probs) {
 // in float32), so 32 768 points keep them near 256 MB whatever G is.
 #define GRID_CHUNK_DEFAULT 32768
 
+// Encoder heads mu | sigma (src/iwae1.py:39-42) of N images xd [N][x_dim] (device) in the eval precision, for iwae_grid_posterior and
+// iwae_latent_activity: mu_i at (*head)[i * ldh], sigma_i at Dp[0] further.  float32: f32_block_fwd into headbuf; bf16: block_fwd on the
+// bf16 rows xPbuf into the handle's encoder workspace.
+static int eval_enc_heads(iwae_model* m, const float* xd, int N, DevBuf& headbuf, DevBuf& xPbuf, const float** head, int* ldh) {
+    hipStream_t st = m->stream;
+    const int X = m->X, Xp = m->Xp32, Dp = m->Dp[0];
+    if (m->eval_precision == IWAE_PREC_FP32) {
+        CHK(ensure(headbuf, (size_t)N * 2 * Dp * 4, st));
+        m->in_eval_llh = true;      // (no K split of the few-row products: an image's heads must not depend on N)
+        const int rc = f32_block_fwd(m, m->enc1[0].sub[0], m->f32.enc1, xd, X, N, ptr<float>(headbuf), Dp, false);
+        m->in_eval_llh = false;
+        CHK(rc);
+        *head = ptr<float>(headbuf); *ldh = 2 * Dp;
+    } else {
+        const int Nbp = round_up(N, 128);
+        CHK(ensure(xPbuf, (size_t)Nbp * Xp * 2, st));
+        launch_prep_rows(xd, nullptr, N, X, 0, Xp, Nbp, ptr<uint16_t>(xPbuf), st);
+        CHK(block_alloc(m, m->enc1, m->wenc1, N, Nbp, false, false));
+        CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(xPbuf), N));
+        *head = ptr<float>(m->wenc1.head); *ldh = m->enc1[2].Np32;
+    }
+    return IWAE_OK;
+}
+
 int iwae_grid_posterior(iwae_handle m, const float* x, int32_t N, const float* z, const float* log_wq, int32_t G, double* log_px,
                         float* post_mean, float* post_cov, float* q_mu, float* q_sigma, float* q_mass, float* kl_q_post, float* log_joint) {
     if (!m || !x || !z || !log_px) return fail(IWAE_ERR_ARG, "grid_posterior: need x, z and log_px");
@@ -3057,21 +3090,7 @@ int iwae_grid_posterior(iwae_handle m, const float* x, int32_t N, const float* z
     // ---- encoder heads mu, sigma of the N images (src/iwae1.py:39-42), in the eval precision
     const float* head;
     int ldh;
-    if (f32) {
-        CHK(ensure(w.head, (size_t)N * 2 * Dp * 4, st));
-        m->in_eval_llh = true;      // (no K split of the few-row products: an image's heads must not depend on N)
-        const int rc = f32_block_fwd(m, m->enc1[0].sub[0], m->f32.enc1, xd, X, N, ptr<float>(w.head), Dp, false);
-        m->in_eval_llh = false;
-        CHK(rc);
-        head = ptr<float>(w.head); ldh = 2 * Dp;
-    } else {
-        const int Nbp = round_up(N, 128);
-        CHK(ensure(w.xP, (size_t)Nbp * Xp * 2, st));
-        launch_prep_rows(xd, nullptr, N, X, 0, Xp, Nbp, ptr<uint16_t>(w.xP), st);
-        CHK(block_alloc(m, m->enc1, m->wenc1, N, Nbp, false, false));
-        CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(w.xP), N));
-        head = ptr<float>(m->wenc1.head); ldh = m->enc1[2].Np32;
-    }
+    CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
     if (q_mu) HIPCHK(hipMemcpy2DAsync(q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
     if (q_sigma) HIPCHK(hipMemcpy2DAsync(q_sigma, (size_t)D * 4, head + Dp, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
     // ---- G in chunks: decoder logits -> prep -> score -> merge into the running per-image state
@@ -3151,6 +3170,138 @@ int iwae_grid_posterior(iwae_handle m, const float* x, int32_t N, const float* z
     if (q_mass) CHK(copy_out(m, q_mass, w.qmass.p, (size_t)N * 4));
     if (kl_q_post) CHK(copy_out(m, kl_q_post, w.kl.p, (size_t)N * 4));
     if (log_joint && lj != log_joint) CHK(copy_out(m, log_joint, lj, (size_t)N * G * 4));
+    HIPCHK(hipStreamSynchronize(st));
+    m->have_forward = false;
+    return IWAE_OK;
+}
+
+int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, const float* eps, double* activity, double* data_mean, float* post_mean) {
+    if (!m || !x) return fail(IWAE_ERR_ARG, "latent_activity: need x");
+    if (!activity) return fail(IWAE_ERR_ARG, "latent_activity: activity is required");
+    if (N <= 0) return fail(IWAE_ERR_ARG, "latent_activity: N must be positive");
+    if (m->C != 0) return fail(IWAE_ERR_ARG, "latent_activity: only the unconditional models (cond_dim = 0)");
+    const bool two = m->cfg.n_layers == 2;
+    if (two && k <= 0) return fail(IWAE_ERR_ARG, "latent_activity: k must be positive for the 2-layer model");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CHK(join_side(m));      // the parameters a deferred update may still be writing
+    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
+    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
+    hipStream_t st = m->stream;
+    iwae_model::ActWs& w = m->act;
+    const bool f32 = m->eval_precision == IWAE_PREC_FP32;
+    const int D0 = m->D[0], Dp0 = m->Dp[0], D1 = two ? m->D[1] : 0, Dt = D0 + D1;
+    const float* xd = x;
+    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * m->X * 4)); xd = ptr<float>(w.x); }
+    // ---- layer 1: E_q[z1|x] = mu1(x), the encoder head
+    const float* head;
+    int ldh;
+    CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
+    CHK(ensure(w.pm, (size_t)N * Dt * 4, st));
+    CHK(ensure(w.act, (size_t)Dt * 8, st));
+    CHK(ensure(w.dm, (size_t)Dt * 8, st));
+    ActStatsArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.src = head; sa.ld_img = ldh; sa.ld_blk = 0; sa.nblk = 1; sa.kdiv = 1.0; sa.N = N; sa.D = D0;
+    sa.post_mean = ptr<float>(w.pm); sa.ldpm = Dt; sa.col = 0; sa.activity = ptr<double>(w.act); sa.data_mean = ptr<double>(w.dm);
+    launch_act_stats(sa, st);
+    HIPCHK(hipGetLastError());
+    if (two) {
+        // ---- layer 2: E_q[z2|x] = E_{z1 ~ q(z1|x)}[mu2(z1)], summed per (image, ACT_BLOCK-sample block), launches of at most eval_rows rows:
+        // whole images while k fits (kc = k), else one image at a time in sample chunks of a multiple of ACT_BLOCK -- so a block never
+        // straddles two launches and an image's partials do not depend on the chunking.
+        const Linear* e2 = m->enc2;
+        const bool fused = !f32 && act_chain_ok(e2[0].KT, e2[1].KT, m->Dp[1] / 32) && e2[0].Kp32 == Dp0 && e2[0].Np32 == 32 * e2[1].KT &&
+                           e2[1].Np32 == e2[0].Np32 && e2[2].KT == e2[1].KT && e2[2].Np32 == 2 * m->Dp[1] && ldh == 2 * Dp0;
+        const int eval_rows = m->eval_rows > 0 ? m->eval_rows : 1 << 19;
+        // (bf16 composed path: at most 4096 rows, where block_fwd is one block_fwd_kernel launch on any row count -- a row's mu2 does not
+        // depend on how many rows share its launch)
+        const int cap = (!f32 && !fused) ? std::min(eval_rows, 4096) : eval_rows;
+        const int kc = k <= cap ? k : std::max(ACT_BLOCK, cap / ACT_BLOCK * ACT_BLOCK);
+        const int nbmax = kc == k ? std::max(1, std::min(32768, cap / k)) : 1;
+        const int nblk = (k + ACT_BLOCK - 1) / ACT_BLOCK;
+        CHK(ensure(w.part, (size_t)N * nblk * D1 * 4, st));
+        const size_t rows_max = (size_t)std::min(nbmax, (int)N) * kc, rows_maxp = round_up((int)rows_max, 128);
+        CHK(ensure(w.eps, rows_max * D0 * 4, st));
+        if (!fused) {
+            CHK(ensure(w.rows, rows_maxp * 4, st));
+            if (f32) {
+                const int H = m->klayers[e2[0].sub[0]].Nout;
+                CHK(ensure(w.z, rows_maxp * D0 * 4, st));
+                CHK(ensure(w.f32.h1, rows_maxp * H * 4, st));
+                CHK(ensure(w.f32.h2, rows_maxp * H * 4, st));
+                CHK(ensure(w.blk.head, rows_maxp * D1 * 4, st));
+            } else {
+                CHK(ensure(w.z, rows_maxp * Dp0 * 2, st));
+                CHK(block_alloc(m, m->enc2, w.blk, (int)rows_max, (int)rows_maxp, false, false));
+            }
+        }
+        const uint32_t step = m->noise_step;
+        m->in_eval_llh = true;      // (float32: no K split of few-row products)
+        int rc = IWAE_OK;
+        for (int i0 = 0; i0 < N && rc == IWAE_OK; i0 += nbmax) {
+            const int nb = std::min(nbmax, (int)N - i0);
+            for (int s0 = 0; s0 < k && rc == IWAE_OK; s0 += kc) {
+                const int kn = std::min(kc, (int)k - s0), M = nb * kn, Mp = round_up(M, 128);
+                EpsSrc e;
+                e.seed = m->cfg.seed; e.step = step; e.stream = 0;
+                e.row_offset = (uint64_t)(m->batch_offset + (uint32_t)i0) * (uint64_t)k;     // iwae_eval_llh's Philox rows: (offset + i) k + s
+                e.k_total = k; e.s_off = s0; e.kc = kn;
+                if (eps) {      // the caller's [k][N][D0] draws of this chunk -> [kn][nb][D0]
+                    if (hipMemcpy2DAsync(w.eps.p, (size_t)nb * D0 * 4, eps + ((size_t)s0 * N + i0) * D0, (size_t)N * D0 * 4, (size_t)nb * D0 * 4, kn,
+                                         hipMemcpyDefault, st) != hipSuccess) { rc = fail(IWAE_ERR_HIP, "latent_activity: copying eps failed"); break; }
+                    e.user = ptr<float>(w.eps);
+                }
+                e.B = nb;
+                const float* hd = head + (size_t)i0 * ldh;
+                if (fused) {
+                    ActChainArgs c;
+                    memset(&c, 0, sizeof(c));
+                    c.img1 = e2[0].imgF; c.img2 = e2[1].imgF; c.imgh = e2[2].imgF;
+                    c.head1 = hd; c.ldH1 = ldh; c.eps1 = e; c.kn = kn; c.D0 = D0; c.D1 = D1;
+                    c.part = ptr<float>(w.part); c.nblk = nblk; c.img0 = i0; c.blk0 = s0 / ACT_BLOCK;
+                    launch_act_chain(c, nb, st);
+                } else {
+                    SampleArgs sm;
+                    memset(&sm, 0, sizeof(sm));
+                    sm.head = hd; sm.ldH = ldh; sm.Dp = Dp0; sm.D = D0; sm.head_per_row = 0;
+                    sm.M = M; sm.Mp = Mp; sm.k = kn; sm.B = nb; sm.eps = e;
+                    sm.lq = ptr<float>(w.rows);
+                    const float* mu2;
+                    int ldm;
+                    if (f32) {      // z1 rows in float32 -> the q(z2|z1) block's two tanh layers and its mu head (the sigma head is not needed)
+                        sm.ZF = ptr<float>(w.z); sm.ldZF = D0;
+                        launch_sample(sm, st);
+                        const KerasLayer* l1 = &m->klayers[e2[0].sub[0]];
+                        const int H = l1->Nout;
+                        if ((rc = f32_fwd(m, l1[0], ptr<float>(w.z), D0, M, ptr<float>(w.f32.h1), H, GEMM_EPI_TANH)) != IWAE_OK) break;
+                        if ((rc = f32_fwd(m, l1[1], ptr<float>(w.f32.h1), H, M, ptr<float>(w.f32.h2), H, GEMM_EPI_TANH)) != IWAE_OK) break;
+                        if ((rc = f32_fwd(m, l1[2], ptr<float>(w.f32.h2), H, M, ptr<float>(w.blk.head), D1, GEMM_EPI_NONE)) != IWAE_OK) break;
+                        mu2 = ptr<float>(w.blk.head); ldm = D1;
+                    } else {
+                        sm.ZP = ptr<uint16_t>(w.z);
+                        launch_sample(sm, st);
+                        if ((rc = block_fwd(m, m->enc2, w.blk, ptr<uint16_t>(w.z), M)) != IWAE_OK) break;
+                        mu2 = ptr<float>(w.blk.head); ldm = e2[2].Np32;
+                    }
+                    ActPartialArgs pa;
+                    memset(&pa, 0, sizeof(pa));
+                    pa.head = mu2; pa.ldh = ldm; pa.nb = nb; pa.kn = kn; pa.D1 = D1;
+                    pa.part = ptr<float>(w.part); pa.nblk = nblk; pa.img0 = i0; pa.blk0 = s0 / ACT_BLOCK;
+                    launch_act_partial(pa, st);
+                }
+                if (hipGetLastError() != hipSuccess) { rc = fail(IWAE_ERR_HIP, "latent_activity: a launch failed"); break; }
+            }
+        }
+        m->in_eval_llh = false;
+        if (rc != IWAE_OK) { (void)hipStreamSynchronize(st); return rc; }
+        sa.src = ptr<float>(w.part); sa.ld_img = (long)nblk * D1; sa.ld_blk = D1; sa.nblk = nblk; sa.kdiv = (double)k; sa.D = D1; sa.col = D0;
+        launch_act_stats(sa, st);
+        HIPCHK(hipGetLastError());
+        m->noise_step += 1;
+    }
+    CHK(copy_out(m, activity, w.act.p, (size_t)Dt * 8));
+    if (data_mean) CHK(copy_out(m, data_mean, w.dm.p, (size_t)Dt * 8));
+    if (post_mean) CHK(copy_out(m, post_mean, w.pm.p, (size_t)N * Dt * 4));
     HIPCHK(hipStreamSynchronize(st));
     m->have_forward = false;
     return IWAE_OK;

@@ -58,3 +58,10 @@ class IWAE(BaseIWAE):
         X = np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim)
         per = np.concatenate([self._net.grid_posterior(X[i:i + batch], z, lw)["log_px"] for i in range(0, X.shape[0], batch)])
         return float(np.mean(per)), per
+
+    # ---- active units (Burda et al. section 5.2; the reference's README TODO)
+    def active_units(self, X, threshold=1e-2):
+        """Units of the latent layer with A_u = Cov_x(E_q[u|x]) > threshold over the images X (E_q[z|x] = mu(x), the encoder head).
+        Returns (counts per layer, activity per layer): ([count], [A float64 [D]])."""
+        act = self._net.latent_activity(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim))["activity"]
+        return [utils.count_active(a, threshold) for a in act], act

@@ -1,6 +1,7 @@
 """Reference API of src/iwae2.py (two stochastic layers, src/iwae2.py:99-182)."""
 import numpy as np
 
+from . import utils
 from ._shim import BaseIWAE, _Sub, as_tensor
 
 
@@ -28,3 +29,9 @@ class IWAE(BaseIWAE):
 
     def true_log_likelihood(self, X, extent=(-5.0, 5.0), n_per_dim=None, batch=10000):
         self.true_posterior(X, None)
+
+    def active_units(self, X, n_samples=5000, threshold=1e-2):
+        """Units of each stochastic layer with A_u = Cov_x(E_q[u|x]) > threshold over the images X: E_q[z1|x] = mu1(x),
+        E_q[z2|x] = the mean of mu2(z1) over n_samples draws of z1 ~ q(z1|x).  Returns ([count z1, count z2], [A z1, A z2])."""
+        act = self._net.latent_activity(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), k=n_samples)["activity"]
+        return [utils.count_active(a, threshold) for a in act], act

@@ -292,6 +292,32 @@ class NativeModel:
                                            out["log_joint"].ctypes.data if log_joint else None))
         return out
 
+    def latent_activity(self, x, k=5000, eps=None, per_image=False):
+        """iwae_latent_activity: the activity A_u = Cov_x(E_q[u|x]) of every latent unit over the images x [N, x_dim] (Burda et al.
+        section 5.2).  Layer 1: E_q[z1|x] = mu1(x); layer 2 (2-layer model): the mean of mu2(z1) over k draws of z1 ~ q(z1|x), the
+        device's (eps=None) or eps [k, N, D1].  Returns {"activity": [A per layer], "data_mean": [mean over x per layer]} (float64)
+        and, with per_image=True, "post_mean": [[N, D_l] per layer] (float32)."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        N = x.shape[0]
+        dims = list(self.n_latent)
+        Dt = sum(dims)
+        e = None
+        if eps is not None and self.n_layers == 2:
+            e = _f32(eps)
+            if e.shape != (int(k), N, dims[0]):
+                raise ValueError("latent_activity: eps must be [k, N, %d] = %s, got %s" % (dims[0], (int(k), N, dims[0]), e.shape))
+        act = np.empty(Dt, dtype=np.float64)
+        dm = np.empty(Dt, dtype=np.float64)
+        pm = np.empty((N, Dt), dtype=np.float32) if per_image else None
+        check(self.lib.iwae_latent_activity(self.h, x.ctypes.data, N, int(k), e.ctypes.data if e is not None else None,
+                                            act.ctypes.data_as(C.POINTER(C.c_double)), dm.ctypes.data_as(C.POINTER(C.c_double)),
+                                            pm.ctypes.data if per_image else None))
+        cut = np.cumsum([0] + dims)
+        out = {"activity": [act[cut[i]:cut[i + 1]] for i in range(len(dims))], "data_mean": [dm[cut[i]:cut[i + 1]] for i in range(len(dims))]}
+        if per_image:
+            out["post_mean"] = [np.ascontiguousarray(pm[:, cut[i]:cut[i + 1]]) for i in range(len(dims))]
+        return out
+
     # ---- resident dataset (device-side shuffle order + dynamic binarisation) -------------------
     def dataset_upload(self, gray_u8):
         g = np.ascontiguousarray(gray_u8, dtype=np.uint8).reshape(-1, self.x_dim)

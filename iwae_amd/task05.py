@@ -53,6 +53,9 @@ class CIWAE(IWAE):
         self._net.set_condition(one_hot(y))
         return self._net.eval_llh(np.asarray(x, dtype=np.float32), n_samples, chunk)
 
+    def active_units(self, X, threshold=1e-2):
+        raise NotImplementedError("active units cover the unconditional models only (E_q[z|x, y] of a conditional model needs a label per image)")
+
     def sample(self, z, y):
         """tasks/task05.py:185-198: one label for all rows of z (tf.repeat(y, z.shape[0]))."""
         z = np.asarray(z, dtype=np.float32)

@@ -56,6 +56,11 @@ class MyMetric():
 _MNIST_CANDIDATES = ("IWAE_MNIST_PATH", "~/.keras/datasets/mnist.npz", "./mnist.npz", "./data/mnist.npz")
 
 
+def count_active(activity, threshold=1e-2):
+    """Active units (Burda et al. section 5.2): the number of units whose activity A_u = Cov_x(E_q[u|x]) is strictly above threshold."""
+    return int(np.count_nonzero(np.asarray(activity, dtype=np.float64) > threshold))
+
+
 def find_mnist():
     for c in _MNIST_CANDIDATES:
         p = os.environ.get(c) if c.isupper() else os.path.expanduser(c)
