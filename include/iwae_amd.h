@@ -247,6 +247,19 @@ int iwae_latent_activity(iwae_handle h, const float* x, int32_t N,   /* [N, x_di
                          double* data_mean,                          /* [D1 (+ D2)] or NULL: mean over x of E_q[u|x] */
                          float* post_mean);                          /* [N, D1 (+ D2)] or NULL: E_q[u|x] per image */
 
+/* Gradient moments of the training estimator (Rainforth et al. 2018, arXiv 1802.04537; Tucker et al. 2019, arXiv 1810.04152): the
+ * per-parameter mean and unbiased (M - 1) variance, in double, of M draws of the flat float32 gradient.  Draw j (0 <= j < M) is exactly
+ * the gradient iwae_forward_backward(h, x, B, k, beta, objective, NULL, ...) leaves after iwae_set_step(s0 + j, batch_offset), s0 the
+ * handle's current step: the gradient of the handle's loss, the mean over the B images (IWAE_OBJ_DREG: the encoder's part is the
+ * gradient of inference_loss, tasks/task02.py:88-99).  The call advances the noise step by M, leaves the parameters and the Adam state
+ * (m, v, t) bitwise unchanged and the last draw's gradient in the gradient buffer, uploads x once, uses the condition of
+ * iwae_set_condition for every draw and never communicates (also on a data-parallel handle).  Welford fold per draw on the device, no
+ * host sync between draws; mean and var bitwise reproducible.  Same objectives as iwae_forward_backward.
+ * M < 2, B <= 0, k <= 0, x, mean or var NULL, or a rejected objective: IWAE_ERR_ARG, nothing launched, the step unchanged. */
+int iwae_grad_moments(iwae_handle h, const float* x, int32_t B, int32_t k, float beta, int32_t objective,   /* x [B, x_dim], host or device */
+                      int32_t M,                                         /* draws, >= 2 */
+                      double* mean, double* var);                        /* [P] each, host or device */
+
 /* Data pipeline on the device (main.py:59-65,117-120 + src/utils.py:26-27): the grey-level training set
  * stays resident in HBM as uint8 [n, x_dim]; every epoch gets a visiting order (tf.data shuffle) and a
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),

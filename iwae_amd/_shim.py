@@ -1,6 +1,7 @@
 """Shared machinery of the reference-API shims (iwae1.IWAE, iwae2.IWAE, task02.IWAEDReG)."""
 import numpy as np
 
+from . import utils
 from .native import NativeModel
 
 
@@ -133,6 +134,16 @@ class BaseIWAE:
                                    float(optimizer.learning_rate), objective, eps=eps, want=self._want(outputs))
         optimizer.iterations += 1
         return self._result(raw)
+
+    # ---- signal-to-noise ratio of the gradient estimator (Rainforth et al. 2018; Tucker et al. 2019) ----------------------------
+    def gradient_snr(self, x, n_samples, n_draws=1000, beta=1.0, objective="iwae_elbo"):
+        """Per-parameter mean and variance of n_draws draws of the training gradient on the images x (iwae_grad_moments) and their
+        summary (utils.gradient_snr_summary): {"encoder", "decoder", "tensors", "mean", "var"}.  Advances the noise step by n_draws;
+        the weights and the optimizer state stay as they are."""
+        mean, var = self._net.grad_moments(np.asarray(x, dtype=np.float32), int(n_samples), int(n_draws), float(beta), objective)
+        out = utils.gradient_snr_summary(mean, var, self._table)
+        out["mean"], out["var"] = mean, var
+        return out
 
     # ---- device-resident data pipeline (main.py:59-65,117-120 on the GPU) -----------------------
     def set_dataset(self, X_gray):

@@ -460,4 +460,20 @@ void launch_act_chain(const ActChainArgs& a, int nb, hipStream_t st);
 void launch_act_partial(const ActPartialArgs& a, hipStream_t st);
 void launch_act_stats(const ActStatsArgs& a, hipStream_t st);
 
+// ---- gradient moments (moments_kernels.hip; iwae_grad_moments): per-parameter Welford fold of M gradient draws, in double
+struct MomentsFoldArgs {              // moments_fold_kernel: draw j (1-based) of the flat gradient g [n] into mean [n] and M2 [n]
+    const float* g;
+    double *mean, *m2;
+    size_t n;
+    int j;
+};
+struct MomentsFinalizeArgs {          // moments_finalize_kernel: out_var = M2 / (M - 1); out_mean = mean unless null (mean already in place)
+    const double *mean, *m2;
+    double *out_mean, *out_var;
+    size_t n;
+    int M;
+};
+void launch_moments_fold(const MomentsFoldArgs& a, hipStream_t st);
+void launch_moments_finalize(const MomentsFinalizeArgs& a, hipStream_t st);
+
 }  // namespace iwae

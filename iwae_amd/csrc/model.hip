@@ -159,6 +159,8 @@ struct iwae_model {
     // iwae_latent_activity's buffers: the images, the chunk's draws, z1 rows and q(z2|z1) activations of the composed paths, the block partials
     // of mu2 [N][blocks][D2] and the outputs
     struct ActWs { DevBuf x, xP, head, eps, z, rows, part, pm, act, dm; BlockWs blk; F32Block f32; } act;
+    // iwae_grad_moments' buffers: the images (uploaded once per call), the Welford mean and M2 [nparam] in double
+    struct MomWs { DevBuf x, mean, m2; } mom_ws;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
@@ -2473,6 +2475,10 @@ void iwae_destroy(iwae_handle m) {
                         &a.blk.dheadP, &a.blk.d2P, &a.blk.d1P, &a.blk.dx, &a.f32.h1, &a.f32.h2, &a.f32.dhead, &a.f32.d2, &a.f32.d1, &a.f32.dx};
         for (DevBuf* b : bb) free_buf(*b);
     }
+    {
+        DevBuf* bb[] = {&m->mom_ws.x, &m->mom_ws.mean, &m->mom_ws.m2};
+        for (DevBuf* b : bb) free_buf(*b);
+    }
     BlockWs* bw[] = {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior};
     for (BlockWs* w : bw) {
         DevBuf* bb[] = {&w->h1P, &w->h2P, &w->head, &w->dheadP, &w->d2P, &w->d1P, &w->dx};
@@ -3304,6 +3310,53 @@ int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, co
     if (post_mean) CHK(copy_out(m, post_mean, w.pm.p, (size_t)N * Dt * 4));
     HIPCHK(hipStreamSynchronize(st));
     m->have_forward = false;
+    return IWAE_OK;
+}
+
+// M draws of the training gradient (Rainforth et al. 2018): draw j is what iwae_forward_backward leaves after iwae_set_step(s0 + j, offset),
+// folded into a per-parameter mean and M2 by moments_fold_kernel after each draw, in stream order; one host sync at the end
+int iwae_grad_moments(iwae_handle m, const float* x, int32_t B, int32_t k, float beta, int32_t objective, int32_t M, double* mean, double* var) {
+    if (!m || !x || !mean || !var || B <= 0 || k <= 0 || M < 2) return fail(IWAE_ERR_ARG, "grad_moments: need x, mean, var, B > 0, k > 0, M >= 2");
+    if ((int64_t)B * k > (int64_t)1 << 30) return fail(IWAE_ERR_ARG, "grad_moments: B*k too large");
+    CHK(check_objective(m, objective));
+    HIPCHK(hipSetDevice(m->cfg.device));
+    const bool f32 = m->cfg.precision == IWAE_PREC_FP32;
+    const int dev = m->cfg.device;
+    const size_t n = m->nparam;
+    hipStream_t st = m->stream;
+    iwae_model::MomWs& w = m->mom_ws;
+    const float* xd = x;
+    if (!is_device_ptr(x, dev)) {        // uploaded once: every draw reads the images in place
+        CHK(copy_in(m, w.x, x, (size_t)B * m->X * 4));
+        xd = ptr<float>(w.x);
+    }
+    CHK(ensure(w.mean, n * 8, st));
+    CHK(ensure(w.m2, n * 8, st));
+    for (int j = 0; j < M; ++j) {
+        if (f32) {
+            CHK(forward_f32(m, xd, B, k, beta, nullptr, objective, true, nullptr));
+            CHK(backward_f32(m, objective));
+        } else {
+            CHK(forward_impl(m, xd, B, k, beta, nullptr, objective, true, nullptr));
+            CHK(backward_impl(m, objective));
+        }
+        m->noise_step += 1;
+        CHK(join_side(m));               // the fold reads the whole gradient: behind every stream that wrote part of it
+        MomentsFoldArgs a;
+        a.g = m->grad; a.mean = ptr<double>(w.mean); a.m2 = ptr<double>(w.m2); a.n = n; a.j = j + 1;
+        launch_moments_fold(a, st);
+    }
+    // var replaces M2 in the workspace unless the caller's buffer is on the device; the mean is copied only to a device buffer
+    const bool mean_dev = is_device_ptr(mean, dev), var_dev = is_device_ptr(var, dev);
+    MomentsFinalizeArgs f;
+    f.mean = ptr<double>(w.mean); f.m2 = ptr<double>(w.m2); f.n = n; f.M = M;
+    f.out_mean = mean_dev ? mean : nullptr;
+    f.out_var = var_dev ? var : ptr<double>(w.m2);
+    launch_moments_finalize(f, st);
+    HIPCHK(hipGetLastError());
+    if (!mean_dev) CHK(copy_out(m, mean, w.mean.p, n * 8));
+    if (!var_dev) CHK(copy_out(m, var, w.m2.p, n * 8));
+    HIPCHK(hipStreamSynchronize(st));
     return IWAE_OK;
 }
 

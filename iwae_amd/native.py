@@ -318,6 +318,22 @@ class NativeModel:
             out["post_mean"] = [np.ascontiguousarray(pm[:, cut[i]:cut[i + 1]]) for i in range(len(dims))]
         return out
 
+    def grad_moments(self, x, k, draws, beta=1.0, objective="iwae_elbo"):
+        """iwae_grad_moments: the per-parameter mean and unbiased variance (float64 [P] each) of `draws` gradient draws of the training
+        estimator on the images x [B, x_dim].  Draw j is the gradient forward_backward(x, k, beta, objective) leaves after
+        set_step(s0 + j), s0 the current step; the step advances by `draws`, parameters and Adam state stay as they are."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        mean = np.empty(self.n_params, dtype=np.float64)
+        var = np.empty(self.n_params, dtype=np.float64)
+        check(self.lib.iwae_grad_moments(self.h, x.ctypes.data, x.shape[0], int(k), float(beta), OBJECTIVES[objective], int(draws),
+                                         mean.ctypes.data_as(C.POINTER(C.c_double)), var.ctypes.data_as(C.POINTER(C.c_double))))
+        return mean, var
+
+    def grad_moments_devptr(self, x_ptr, B, k, draws, beta, objective_id, mean_ptr, var_ptr):
+        """iwae_grad_moments on raw pointers (host or device: x [B, x_dim] float32, mean / var [P] float64)."""
+        check(self.lib.iwae_grad_moments(self.h, C.c_void_p(x_ptr), int(B), int(k), float(beta), int(objective_id), int(draws),
+                                         C.cast(C.c_void_p(mean_ptr), C.POINTER(C.c_double)), C.cast(C.c_void_p(var_ptr), C.POINTER(C.c_double))))
+
     # ---- resident dataset (device-side shuffle order + dynamic binarisation) -------------------
     def dataset_upload(self, gray_u8):
         g = np.ascontiguousarray(gray_u8, dtype=np.uint8).reshape(-1, self.x_dim)

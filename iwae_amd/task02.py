@@ -17,6 +17,9 @@ class IWAEDReG(IWAE):
         optimizer.iterations += 1
         return self._result(raw)
 
+    def gradient_snr(self, x, n_samples, n_draws=1000, beta=1.0, objective="dreg"):
+        return super().gradient_snr(x, n_samples, n_draws, beta, objective)
+
     @staticmethod
     def write_to_tensorboard(res, step):          # tasks/task02.py:103-108
         out = {"step": int(step), "iwae_elbo": float(res["iwae_elbo"])}

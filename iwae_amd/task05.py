@@ -53,6 +53,10 @@ class CIWAE(IWAE):
         self._net.set_condition(one_hot(y))
         return self._net.eval_llh(np.asarray(x, dtype=np.float32), n_samples, chunk)
 
+    def gradient_snr(self, x, y, n_samples, n_draws=1000, beta=1.0, objective="iwae_elbo"):
+        self._net.set_condition(one_hot(y))
+        return super().gradient_snr(x, n_samples, n_draws, beta, objective)
+
     def active_units(self, X, threshold=1e-2):
         raise NotImplementedError("active units cover the unconditional models only (E_q[z|x, y] of a conditional model needs a label per image)")
 

@@ -61,6 +61,39 @@ def count_active(activity, threshold=1e-2):
     return int(np.count_nonzero(np.asarray(activity, dtype=np.float64) > threshold))
 
 
+def _snr_stats(mean, var):
+    nz = var > 0
+    snr = float(np.mean(np.abs(mean[nz]) / np.sqrt(var[nz]))) if np.any(nz) else float("nan")
+    return {"snr": snr, "signal": float(np.sum(mean * mean)), "variance": float(np.sum(var)), "n": int(mean.size)}
+
+
+def gradient_snr_summary(mean, var, table):
+    """Signal-to-noise ratio of a gradient estimator from its per-parameter moments (NativeModel.grad_moments), per tensor of
+    `table` (NativeModel.tensor_table(): (name, shape, offset)) and per group: "encoder" = every enc* tensor, "decoder" = every dec*
+    tensor.  For each: snr = the mean over the parameters with var > 0 of |mean| / sqrt(var) (Rainforth et al. 2018, averaged; NaN if
+    there is none), signal = sum of mean^2, variance = sum of var, n = the parameter count.
+    Returns {"encoder": stats, "decoder": stats, "tensors": {name: stats}}."""
+    mean = np.asarray(mean, dtype=np.float64).ravel()
+    var = np.asarray(var, dtype=np.float64).ravel()
+    if mean.shape != var.shape:
+        raise ValueError("gradient_snr_summary: mean and var differ in size (%d vs %d)" % (mean.size, var.size))
+    tensors, groups = {}, {"encoder": [], "decoder": []}
+    for name, shape, off in table:
+        sl = slice(int(off), int(off) + int(np.prod(shape)))
+        if sl.stop > mean.size:
+            raise ValueError("gradient_snr_summary: tensor %s ends at %d, past the %d parameters" % (name, sl.stop, mean.size))
+        tensors[name] = _snr_stats(mean[sl], var[sl])
+        group = "encoder" if name.startswith("enc") else "decoder" if name.startswith("dec") else None
+        if group:
+            groups[group].append(sl)
+    out = {}
+    for group, sls in groups.items():
+        idx = np.concatenate([np.arange(sl.start, sl.stop) for sl in sls]) if sls else np.zeros(0, dtype=np.int64)
+        out[group] = _snr_stats(mean[idx], var[idx])
+    out["tensors"] = tensors
+    return out
+
+
 def find_mnist():
     for c in _MNIST_CANDIDATES:
         p = os.environ.get(c) if c.isupper() else os.path.expanduser(c)
