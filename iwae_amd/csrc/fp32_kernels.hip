@@ -1123,18 +1123,11 @@ void launch_concat_f32(const float* a, int na, const float* b, int nb, int rows,
     hipLaunchKernelGGL(concat_f32_kernel, dim3((unsigned)(((size_t)rows * (na + nb) + 255) / 256)), dim3(256), 0, st, a, na, b, nb, rows, out);
 }
 
-int g_gemm_f32_dbg = 0;
-bool g_gemm_f32_v2 = true;
-int g_gemm_f32_ksplit_min_tiles = 1;    // (option f32_ksplit_min_tiles: 8 = round-5 first version: B >= 100 images only)
-bool g_gemm_f32_ksplit = true;        // (option f32_no_ksplit = 1: few-row products as one 64-tile launch walking K alone)
-int g_gemm_f32_v2_small_min = 1;        // (option f32_gemm_small_min: workgroups from which the 64 x 64 launch takes the v2 loop)
-bool g_gemm_f32_v2_small = true;      // (option f32_gemm_small_v1 = 1)
-bool g_gemm_f32_w8 = true;       // (iwae_set_option f32_gemm_w4 = 1: no 8-wave tiles)      // (iwae_set_option f32_gemm_v1 = 1: the round-3 loop, for A/B measurements; process-wide)
 // Tile choice of the big kernels.  4-wave tiles (1 024 workgroup slots on the chip): 128 x 128, 64 x 224, 224 x 64 -- the candidate with the least padded
 // area (ties: 128 x 128).  8-wave tiles (512 slots; 39 % fewer operand bytes per FLOP): 128 x 224 where the 64 x 224 tile won and the rows fill the
 // machine, 224 x 128 where 224 x 64 won and the wider tile pads <= 10 % more (N = 784: 7 x 128 = 896 against 13 x 64 = 832).
 struct GemmF32Tile { int bm, bn, waves; long tm, tn; };
-static GemmF32Tile gemm_f32_pick(int M, int N, bool allow8 = true) {
+static GemmF32Tile gemm_f32_pick(int M, int N, bool allow8) {
     const int cand[3][2] = {{128, 128}, {64, 224}, {224, 64}};
     long best = -1;
     GemmF32Tile t = {128, 128, 4, 0, 0};
@@ -1143,7 +1136,7 @@ static GemmF32Tile gemm_f32_pick(int M, int N, bool allow8 = true) {
         const long area = tm * cand[c][0] * tn * cand[c][1];
         if (best < 0 || area < best) { best = area; t = {cand[c][0], cand[c][1], 4, tm, tn}; }
     }
-    if (allow8 && g_gemm_f32_v2 && g_gemm_f32_w8) {
+    if (allow8) {
         if (t.bm == 64 && t.bn == 224 && M >= 128 * 256) { t.bm = 128; t.waves = 8; t.tm = (M + 127) / 128; }
         else if (t.bm == 224 && t.bn == 64) {
             const long tn8 = (N + 127) / 128;
@@ -1152,13 +1145,13 @@ static GemmF32Tile gemm_f32_pick(int M, int N, bool allow8 = true) {
     }
     return t;
 }
-long gemm_f32_tiles(int M, int N, int tile_mode) {      // output tiles of the kernel launch_gemm_f32 would take (f32_dw sizes its row splits from it)
-    if (M > 64 && N > 64) { const GemmF32Tile t = gemm_f32_pick(M, N, tile_mode == 0); return t.tm * t.tn; }
+long gemm_f32_tiles(const GemmF32Opts& o, int M, int N, int tile_mode) {      // output tiles of the kernel launch_gemm_f32 would take (f32_dw sizes its row splits from it)
+    if (M > 64 && N > 64) { const GemmF32Tile t = gemm_f32_pick(M, N, o.v2 && o.w8 && tile_mode == 0); return t.tm * t.tn; }
     return (long)((M + 63) / 64) * ((N + 63) / 64);
 }
-int gemm_f32_slots(int M, int N, int tile_mode) {       // workgroups of that kernel the chip holds at once
+int gemm_f32_slots(const GemmF32Opts& o, int M, int N, int tile_mode) {       // workgroups of that kernel the chip holds at once
     if (tile_mode == 2) return 768;
-    if (M > 64 && N > 64) return gemm_f32_pick(M, N, tile_mode == 0).waves == 8 ? 512 : 1024;
+    if (M > 64 && N > 64) return gemm_f32_pick(M, N, o.v2 && o.w8 && tile_mode == 0).waves == 8 ? 512 : 1024;
     return 1024;
 }
 bool gemm_f32_takes_big(int M, int N, int nsplit) {
@@ -1166,9 +1159,9 @@ bool gemm_f32_takes_big(int M, int N, int nsplit) {
     const GemmF32Tile t = gemm_f32_pick(M, N, false);
     return t.tm * t.tn * nsplit >= 512;      // (448, which lets the 100 x 200 weight gradient in -- 2 tiles x 247 row splits -- measured slower: 79 vs 59 us)
 }
-void launch_gemm_f32(const GemmF32Args& a0, int nsplit, hipStream_t st) {
+void launch_gemm_f32(const GemmF32Opts& o, const GemmF32Args& a0, int nsplit, hipStream_t st) {
     GemmF32Args a = a0;
-    a.dbg = g_gemm_f32_dbg;
+    a.dbg = o.dbg;
     // float4 fetches where every quad is 16-byte aligned: base pointer, the non-unit stride and the k-chunk offsets
     const long a_str = a.sak == 1 ? a.sam : a.sak, b_str = a.sbn == 1 ? a.sbk : a.sbn;
     a.avec = (((uintptr_t)a.A & 15) == 0 && a_str % 4 == 0 && (a.sak == 1 || a.sam == 1) && (nsplit == 1 || a.kchunk % 4 == 0)) ? 1 : 0;
@@ -1182,8 +1175,8 @@ void launch_gemm_f32(const GemmF32Args& a0, int nsplit, hipStream_t st) {
     const int Mg = a.M + (a.Cones ? 1 : 0);      // (the row of ones)
     if (gemm_f32_takes_big(a.M, a.N, nsplit)) {
         // (the v2 loop wants unit strides on the fast index of each operand -- every caller's are -- and falls back to the old kernel otherwise)
-        const bool v2 = g_gemm_f32_v2 && (a.sak == 1 || a.sam == 1) && (a.sbn == 1 || a.sbk == 1);
-        GemmF32Tile t = gemm_f32_pick(a.M, a.N, v2 && a.tile_mode == 0);
+        const bool v2 = o.v2 && (a.sak == 1 || a.sam == 1) && (a.sbn == 1 || a.sbk == 1);
+        GemmF32Tile t = gemm_f32_pick(a.M, a.N, v2 && o.w8 && a.tile_mode == 0);
         if (a.epi == GEMM_EPI_BERN) t = {128, 128, 4, 0, 0};      // (the Bernoulli epilogue's partial sums are per 64-column half of a 128-tile)
         const bool ak = a.sak == 1, bnf = a.sbn == 1;
         if (v2 && a.tile_mode == 2 && t.bm == 224 && !ak && bnf) {      // a weight gradient that shares the CUs with few-row kernels: 3 waves per SIMD, one slot left to them
@@ -1222,7 +1215,7 @@ void launch_gemm_f32(const GemmF32Args& a0, int nsplit, hipStream_t st) {
         const dim3 grid((a.N + 63) / 64, (Mg + 63) / 64, nsplit);
         const bool ak = a.sak == 1, bnf = a.sbn == 1;
         // many 64 x 64 tiles (the 50-wide latent layer on all rows, its weight gradient's row splits): the v2 loop on that tile
-        if (g_gemm_f32_v2 && g_gemm_f32_v2_small && (long)grid.x * grid.y * grid.z >= g_gemm_f32_v2_small_min && (a.sak == 1 || a.sam == 1) && (a.sbn == 1 || a.sbk == 1)) {
+        if (o.v2 && o.v2_small && (long)grid.x * grid.y * grid.z >= o.v2_small_min && (a.sak == 1 || a.sam == 1) && (a.sbn == 1 || a.sbk == 1)) {
             if (ak && bnf) hipLaunchKernelGGL((gemm_f32_v2_kernel<2, 2, 2, 2, true, true>), grid, dim3(256), 0, st, a);
             else if (ak) hipLaunchKernelGGL((gemm_f32_v2_kernel<2, 2, 2, 2, true, false>), grid, dim3(256), 0, st, a);
             else if (bnf) hipLaunchKernelGGL((gemm_f32_v2_kernel<2, 2, 2, 2, false, true>), grid, dim3(256), 0, st, a);
@@ -1257,23 +1250,23 @@ __global__ __launch_bounds__(256) void reduce_epi_f32_kernel(GemmF32Args a, cons
     }
 }
 // the K split launch_gemm_f32_fewrows would take (1: none)
-int gemm_f32_fewrows_split(int M, int N, int K) {
-    if (!g_gemm_f32_v2 || !g_gemm_f32_ksplit || M > 4096 || (N & 3) || K < 96) return 1;
+int gemm_f32_fewrows_split(const GemmF32Opts& o, int M, int N, int K) {
+    if (!o.v2 || !o.ksplit || M > 4096 || (N & 3) || K < 96) return 1;
     const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-    if (tiles >= 256 || tiles < g_gemm_f32_ksplit_min_tiles) return 1;
+    if (tiles >= 256 || tiles < o.ksplit_min_tiles) return 1;
     int ns = (int)std::min<long>(std::min<long>(tiles < 8 ? 16 : 8, (256 + tiles - 1) / tiles), K / 48);
     if (ns < 2) return 1;
     const int kchunk = ((K + ns - 1) / ns + 15) / 16 * 16;
     return (K + kchunk - 1) / kchunk;
 }
 // slabs: >= split * M * N floats of scratch (16-byte aligned)
-void launch_gemm_f32_fewrows(const GemmF32Args& a0, float* slabs, hipStream_t st) {
-    const int ns0 = gemm_f32_fewrows_split(a0.M, a0.N, a0.K);
+void launch_gemm_f32_fewrows(const GemmF32Opts& o, const GemmF32Args& a0, float* slabs, hipStream_t st) {
+    const int ns0 = gemm_f32_fewrows_split(o, a0.M, a0.N, a0.K);
     GemmF32Args g = a0;
     g.kchunk = ((a0.K + ns0 - 1) / ns0 + 15) / 16 * 16;
     const int ns = (a0.K + g.kchunk - 1) / g.kchunk;
     g.C = slabs; g.ldc = a0.N; g.slab_stride = (size_t)a0.M * a0.N; g.bias = nullptr; g.epi = GEMM_EPI_NONE; g.ACT = nullptr; g.accumulate = 0; g.orow_scale = nullptr;
-    launch_gemm_f32(g, ns, st);
+    launch_gemm_f32(o, g, ns, st);
     GemmF32Args e = a0;
     e.slab_stride = g.slab_stride;
     hipLaunchKernelGGL(reduce_epi_f32_kernel, dim3((unsigned)(((size_t)a0.M * (a0.N >> 2) + 255) / 256)), dim3(256), 0, st, e, slabs, ns);

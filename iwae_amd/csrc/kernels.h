@@ -61,7 +61,7 @@ struct DenseArgs {
     float* zlq_dreg;                  // DReG (tasks/task02.py:63-65): log q(z|x) with sigma + 1e-6 as the scale, or null (bern_pipe_kernel's prologue only)
     float* lpxz; size_t lpxz_stride;  // log p(x|z) per row; stride > 0: block row y of the grid writes its partial sum to lpxz[y*stride + row]
     float* logits_out;
-    int pipe;                         // EPI_BERN: take bern_pipe_kernel where it exists (IWAE_NO_BERN_PIPE=1 clears it)
+    int pipe;                         // EPI_BERN: take bern_pipe_kernel where it exists (option no_bern_pipe clears it)
     // bern_pipe_kernel<.., PRE>: the two tanh layers in front of the output layer run inside the same launch (pre_img1 != null)
     const char* pre_img1; int pre_KT1;   // first decoder layer: forward image, k-steps of its input (latent, <= 4)
     const char* pre_img2;                // second decoder layer (KT k-steps in and out)
@@ -374,16 +374,22 @@ struct DecFwdF32Args {
 };
 bool dec_fwd_f32_ok(const DecFwdF32Args& a);
 void launch_dec_fwd_f32(const DecFwdF32Args& a, hipStream_t st);
-long gemm_f32_tiles(int M, int N, int tile_mode = 0);                       // output tiles of the kernel launch_gemm_f32 takes for an M x N product
+// kernel choice of the float32 GEMM launchers: one per handle (iwae_set_option f32_*), handed to every launcher that reads it
+struct GemmF32Opts {
+    bool v2 = true;                  // false (option f32_gemm_v1 = 1): gemm_f32_big_kernel (the round-3 k loop) instead of gemm_f32_v2_kernel, for A/B measurements
+    bool w8 = true;                  // false (option f32_gemm_w4 = 1): no 8-wave tiles
+    bool v2_small = true;            // false (option f32_gemm_small_v1 = 1): the round-3 64-tile kernel for every 64 x 64-tiled product
+    bool ksplit = true;              // false (option f32_no_ksplit = 1): few-row products as one 64-tile launch walking K alone
+    int ksplit_min_tiles = 1;        // option f32_ksplit_min_tiles: 8 = round-5 first version: B >= 100 images only
+    int v2_small_min = 1;            // option f32_gemm_small_min: workgroups from which the 64 x 64 launch takes the v2 loop
+    int dbg = 0;                     // option f32_gemm_dbg (DIAG builds): timing ablations of gemm_f32_v2_kernel
+};
+long gemm_f32_tiles(const GemmF32Opts& o, int M, int N, int tile_mode = 0);      // output tiles of the kernel launch_gemm_f32 takes for an M x N product
 bool gemm_f32_takes_big(int M, int N, int nsplit);      // launch_gemm_f32's kernel choice (GEMM_EPI_BERN needs the 128-tile kernel)
-void launch_gemm_f32(const GemmF32Args& a, int nsplit, hipStream_t st);
-extern int g_gemm_f32_dbg;
-extern int g_gemm_f32_ksplit_min_tiles, g_gemm_f32_v2_small_min;
-extern bool g_gemm_f32_w8, g_gemm_f32_v2_small, g_gemm_f32_ksplit;
-int gemm_f32_fewrows_split(int M, int N, int K);        // > 1: launch_gemm_f32_fewrows splits K that many ways (scratch: split * M * N floats)
-void launch_gemm_f32_fewrows(const GemmF32Args& a, float* slabs, hipStream_t st);
-int gemm_f32_slots(int M, int N, int tile_mode = 0);                       // workgroups of launch_gemm_f32's kernel for an M x N product the chip holds at once
-extern bool g_gemm_f32_v2;                               // false: gemm_f32_big_kernel (the round-3 k loop) instead of gemm_f32_v2_kernel
+void launch_gemm_f32(const GemmF32Opts& o, const GemmF32Args& a, int nsplit, hipStream_t st);
+int gemm_f32_fewrows_split(const GemmF32Opts& o, int M, int N, int K);      // > 1: launch_gemm_f32_fewrows splits K that many ways (scratch: split * M * N floats)
+void launch_gemm_f32_fewrows(const GemmF32Opts& o, const GemmF32Args& a, float* slabs, hipStream_t st);
+int gemm_f32_slots(const GemmF32Opts& o, int M, int N, int tile_mode = 0);       // workgroups of launch_gemm_f32's kernel for an M x N product the chip holds at once
 void launch_reduce_slabs_f32(const float* slabs, size_t stride, int nsplit, size_t n, float* out, hipStream_t st);
 // every slab sum of a float32 step in one launch (round 5): out[i] = sum over the job's slabs, i < n; block_begin is filled by the launcher
 #define REDUCE_SLABS_MAX_JOBS 40

@@ -117,12 +117,21 @@ static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgra
                                                  "latent_bwd", "encoder_fwd", "reduce_adam", "decoder_bwd",
                                                  "allreduce_enc", "allreduce_dec"};      // (the data-parallel step's two ncclAllReduce calls, each on its own stream)
 
+// What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
+// images and samples in chunks and needs log_w only.
+struct FwdCall {
+    uint32_t batch_offset = 0;        // Philox row offset of the call's first image (iwae_set_step, plus the chunk's first image)
+    int cond_row0 = 0;                // first row of iwae_model::cond the call's images use
+    int k_total = 0, s_off = 0;       // k_total > 0: the call holds samples [s_off, s_off + k) of k_total per image and draws the unchunked call's Philox rows
+    bool log_w_only = false;          // forward-only call: no second (DReG) density per sample (round 5: ~14 % of the sampling pass); the log-mean-exp alone when no tensor is wanted
+    bool no_ksplit = false;           // float32: no K split of few-row products (an image's result must not depend on how many images share the launch)
+};
+
 struct iwae_model {
     iwae_config cfg;
     int X, Xp32;
     int C = 0, Xinp = 0;       // conditional model: condition width; row width of the encoder input concat(x, y) (= Xp32 without)
     DevBuf cond; int cond_n = 0;   // y [cond_n][C] fp32 for the next call (iwae_set_condition)
-    int cond_row0 = 0;         // first row of `cond` the current forward uses (eval_llh walks chunks)
     int H[2], D[2], Hp[2], Dp[2];
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -147,9 +156,7 @@ struct iwae_model {
     int f32_dw_last = 0;
     bool bf16_side_used = false;      // a bf16 call may have left a speculative draw on a side stream (forward_f32 waits for it on the host)
     size_t f32_slab_want = 0, f32_slab_want_step = 0;      // floats of slabs the last whole step asked for (the buffer's target size) / this step so far
-    int eval_tag_kill = -1;
-    int eval_k_total = 0, eval_s_off = 0;     // > 0 while iwae_eval_llh walks an image's samples in chunks (eps_src)
-    bool in_eval_llh = false;                 // iwae_eval_llh's launches need log_w only: no second (DReG) density per sample (round 5: ~14 % of the sampling pass)
+    GemmF32Opts gemm_f32;                     // kernel choice of the float32 GEMM launchers (options f32_gemm_*, f32_no_ksplit, f32_ksplit_min_tiles)
     DevBuf eval_x, eval_lme;                  // iwae_eval_llh: the images (uploaded once) and the per-image log-mean-exps of every launch
     int eval_rows = 0;                        // data rows per evaluator launch (option eval_rows): images x samples, k chunked beyond it; 0 = eval_rows_auto()
     int eval_precision = IWAE_PREC_FP32;      // arithmetic of iwae_eval_llh and iwae_grid_posterior (iwae_set_eval_precision)
@@ -173,12 +180,13 @@ struct iwae_model {
     LayerDesc* d_descs = nullptr;
     int elem_blocks = 0, reduce_blocks = 0;
     bool descs_dirty = true;
-    // per-call state
+    // per-call state: written by begin_forward only (the backward pass and eps_src read the forward's copy)
+    FwdCall call;
     int B = 0, k = 0, M = 0, Mp = 0, Bp = 0;
     float beta = 1.0f;
     bool have_forward = false, user_eps = false;
-    unsigned dense_g1_mask = IWAE_DENSE_G1_DEFAULT;   // IWAE_DENSE_G1=<mask> (tuning aid, kernels.h)
-    bool allow_s_mode = true;   // IWAE_OUT_RECOMPUTE=1 switches back to recomputing the logits in out_bwd (A/B measurements)
+    unsigned dense_g1_mask = IWAE_DENSE_G1_DEFAULT;   // option dense_g1 = <mask> (tuning aid, kernels.h)
+    bool allow_s_mode = true;   // option out_recompute switches back to recomputing the logits in out_bwd (A/B measurements)
     DevBuf dg2_part;            // small row counts: out_bwd_s_kernel's per-pixel-group partial sums
     int px_parts = 1;           // > 1: log p(x|z) of this forward arrives in px_part as that many partial sums per row
     DevBuf px_part;
@@ -210,7 +218,7 @@ struct iwae_model {
     bool allow_lat_in_block = true;                  // few images: latent_bwd_kernel's sums inside the encoder's block_bwd_kernel (option no_lat_in_block)
     bool lse_pending = false, allow_lse_in_bwd = true;      // few rows: this step's lse_kernel work was left to dec_bwd_rows_kernel (lse_saved; option no_lse_in_bwd)
     LseArgs lse_saved;
-    bool lse_dup = false, allow_lse_dup = true;      // IWAE_NO_LSE_DUP=1: one lse_kernel, the side stream forks behind it (A/B measurements)
+    bool lse_dup = false, allow_lse_dup = true;      // option no_lse_dup: one lse_kernel, the side stream forks behind it (A/B measurements)
     BlockWs wenc1, wenc2, wdec2, wprior;
     MlpWs wdec1;
     DevBuf scratch;            // exports
@@ -218,10 +226,10 @@ struct iwae_model {
     DevBuf ds_data, ds_order;
     DevBuf ds_labels; bool ds_has_labels = false;   // class id per image of the resident set (iwae_dataset_set_labels; conditional models)
     int ds_N = 0;
-    int wg_target16_1 = 64;    // same, for layers that are a single block wide (IWAE_WG16_1): the hidden layers' gradients -- with the specialised-wave kernel 64 row splits (12.8 MB of slabs each) beat 128 (0.259 -> 0.249-0.254 ms/step); 48 and 32 are slower again
-    int eps_blocks = 512;      // blocks of the ahead-of-time noise draw (IWAE_EPS_BLOCKS; 0 = one block per 256 threads of work)
+    int wg_target16_1 = 64;    // same, for layers that are a single block wide (option wg16_1): the hidden layers' gradients -- with the specialised-wave kernel 64 row splits (12.8 MB of slabs each) beat 128 (0.259 -> 0.249-0.254 ms/step); 48 and 32 are slower again
+    int eps_blocks = 512;      // blocks of the ahead-of-time noise draw (option eps_blocks; 0 = one block per 256 threads of work)
     int wg_target8 = 128;      // same for the 8-wave launches on many rows (narrow layers of the 2-layer model; option wg8): 128 row splits halve the 109 MB of fp32 slabs 256 wrote per step (c2: 0.4193 -> 0.4176 ms; 64: 0.462)
-    int wg_target8_few = 32;   // 8-wave launches on < 8 192 rows (the encoder's layers on the batch's images; IWAE_WG8_FEW): the 784-wide first layer in 4 row
+    int wg_target8_few = 32;   // 8-wave launches on < 8 192 rows (the encoder's layers on the batch's images; option wg8_few): the 784-wide first layer in 4 row
                                // splits instead of 16 (10.6 -> 2.7 MB of slabs each way): 0.2439 -> 0.2351 ms/step at B = 1 024; 8 / 16 / 48: 0.2374 / 0.2374 / 0.2360
     int wg_target16 = 0;       // workgroups aimed at per 16-wave weight-gradient launch (option wg16; 0 = the model's default: 96 for the 1-layer model, 64 (round 5; 128 before) for
                                // the 2-layer one -- round 3, with the output layer's gradient starting right behind the decoder kernel: 80 / 88 / 96 / 104 / 112 / 128
@@ -248,15 +256,15 @@ struct iwae_model {
     char* d_zero = nullptr;    // 1 KiB of zeros (wgradp_kernel's source for rows >= M)
     uint32_t ds_epoch = 0;
     int ds_start = -1;         // >= 0: the next forward gathers + binarises rows ds_start.. from the dataset instead of reading x
-    DevBuf stamps;             // diagnostic (IWAE_STAMPS=1)
-    DevBuf dstamps; int dstamp_epi = -1, dstamp_kt = -1, dstamp_waves = 0;   // diagnostic (IWAE_DENSE_STAMPS)
+    DevBuf stamps;             // diagnostic (option stamps, DIAG builds)
+    DevBuf dstamps; int dstamp_epi = -1, dstamp_kt = -1, dstamp_waves = 0;   // diagnostic (options dense_stamps_epi / dense_stamps_kt, STAMPS builds)
     // optional HIP-event timing of the dominant kernels (iwae_enable_timing): pairs recorded on m->stream
     // fork/join of the decoder weight-gradient GEMMs (independent of the dz -> encoder chain) onto a side stream
     hipStream_t side = nullptr;
     hipStream_t tail = nullptr;        // this step's side stream that finishes last (carries the decoder's reduction / exchange / update)
-    bool allow_wg_group = false;       // IWAE_WG_GROUP=1: the hidden layers' gradients as ONE grouped launch (measured: 0.2450 vs 0.2384 ms/step as two launches --
+    bool allow_wg_group = false;       // option wg_group: the hidden layers' gradients as ONE grouped launch (measured: 0.2450 vs 0.2384 ms/step as two launches --
                                        // both at once take more of the machine from the output layer's gradient, which is what the step waits for)
-    hipStream_t side2 = nullptr;       // the hidden layers' weight gradients beside the output layer's (IWAE_NO_SIDE2=1: behind it on `side`)
+    hipStream_t side2 = nullptr;       // the hidden layers' weight gradients beside the output layer's (option no_side2: behind it on `side`)
     hipEvent_t ev_s2 = nullptr;
     hipEvent_t ev_ar = nullptr;        // data-parallel step: recorded behind the encoder segment's all-reduce (dp_finish)
     bool early_held = false;           // in-library data-parallel step: backward_impl left the decoder's slab reduction to dp_finish
@@ -264,7 +272,7 @@ struct iwae_model {
     bool use_side2 = true;
     int dec_bwd_nw = 8;         // option dec_bwd_nw: dec_bwd_kernel's shape (8 waves x 16 rows, round 4 | 4 waves x 32 rows)
     hipEvent_t ev_lse = nullptr;
-    bool early_wout = false, allow_early_wout = true;    // IWAE_NO_EARLY_WOUT=1: the output layer's weight gradient forks behind out_bwd with the others (A/B measurements)
+    bool early_wout = false, allow_early_wout = true;    // option no_early_wout: the output layer's weight gradient forks behind out_bwd with the others (A/B measurements)
     hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_blk = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_dec = nullptr;
     // Single-GPU train step: the decoder's slab reduction + Adam (90 % of the slab bytes) stays on the side stream and is
     // NOT joined at the end of the step -- nothing needs the decoder's new weights before the next step's d1 layer, so it
@@ -272,31 +280,31 @@ struct iwae_model {
     // join_side() does that, and every entry point that touches parameters, gradients or the decoder calls it.
     bool dec_pending = false;
     size_t split_offset = 0;    // iwae_forward_backward_split: first float of the flat gradient that was left on the side stream
-    int wg_shape9 = 0;          // IWAE_WG9 (bit mask, see wgradp_plan): layers that take the 8 + 8-wave / 128-feature shape of wgradws_kernel
+    int wg_shape9 = 0;          // option wg9 (bit mask, see wgradp_plan): layers that take the 8 + 8-wave / 128-feature shape of wgradws_kernel
     int fake_s = 0;             // DIAG builds: byte ablations of s (option fake_s)
     int abl_skip = 0;           // DIAG builds: launch ablations of the full-size step (option abl_skip; timing only, results wrong): 1 no output-layer weight gradient,
                                 // 2 no hidden-layer weight gradients, 4 no deferred decoder reduction + update, 8 no latent_bwd_kernel, 16 no noise draw ahead
-    int wg_debug = 0;           // IWAE_WG_DEBUG: diagnostic ablations of wgradp_kernel (kernels.h)
-    bool allow_wg7 = true;      // IWAE_NO_WG7=1: the 16-wave weight-gradient shapes also where the 8-wave 7 x 4 shape exists (A/B measurements)
-    int dec_rows_max = 1024;    // dec_bwd_rows_kernel up to this many rows (IWAE_DEC_ROWS), dec_bwd_kernel beyond
-    bool small_dec_bwd = true; int small_rows = 8191;   // the one-launch dX chain also below 8 192 rows (IWAE_NO_SMALL_DEC_BWD=1: the per-pixel-group out_bwd + finish + two dX launches
+    int wg_debug = 0;           // option wg_debug (DIAG builds): diagnostic ablations of wgradp_kernel (kernels.h)
+    bool allow_wg7 = true;      // option no_wg7: the 16-wave weight-gradient shapes also where the 8-wave 7 x 4 shape exists (A/B measurements)
+    int dec_rows_max = 1024;    // dec_bwd_rows_kernel up to this many rows (option dec_rows), dec_bwd_kernel beyond
+    bool small_dec_bwd = true; int small_rows = 8191;   // the one-launch dX chain also below 8 192 rows (option no_small_dec_bwd: the per-pixel-group out_bwd + finish + two dX launches
                                                         // there).  Measured: B=20,k=1 0.1417 -> 0.1383 ms/step, B=100,k=5 150.7 -> 144.6 us, B=160,k=50 189.1 -> 165.7 us
-    bool allow_dz_half = true;  // IWAE_DZ_F32=1: dec_bwd_kernel leaves dz as float32 (A/B measurements)
+    bool allow_dz_half = true;  // option dz_f32: dec_bwd_kernel leaves dz as float32 (A/B measurements)
     bool allow_chain2_bwd = true, chain2_bwd = false;      // option no_chain2_bwd: the per-sample blocks' backward as gauss_bwd_kernel + dense_kernel launches; chain2_bwd: this step takes gblock_bwd_kernel
     bool allow_chain2 = true;   // option no_chain2: the 2-layer model's per-sample blocks as dense_kernel launches + sample_kernel + gauss_lp_kernel (A/B measurements, variant tests)
-    bool allow_dec_bwd = true;  // IWAE_NO_DEC_BWD=1: out_bwd_s + the two dX kernels stay three launches (A/B measurements)
-    bool allow_zin = true;      // IWAE_NO_ZIN=1: always the separate sampling kernel (A/B measurements)
+    bool allow_dec_bwd = true;  // option no_dec_bwd: out_bwd_s + the two dX kernels stay three launches (A/B measurements)
+    bool allow_zin = true;      // option no_zin: always the separate sampling kernel (A/B measurements)
     bool allow_zin_eval = false; // option zin_eval (round 4, measured and NOT the default): forward-only calls on many rows take their draws from eps_gen_kernel and let the decoder
                                  // kernel make z in its prologue instead of sample_kernel (inline Philox) in front of it -- bf16 evaluator 146 k vs 158 k images/s: the prologue's 20 MB of
                                  // float32 draws cost the vector-issue-bound kernel more than the separate pass
-    bool allow_out_in_block = true;  // IWAE_NO_OUT_IN_BLOCK=1: the output layer of a few-row decoder stays a dense_kernel<EPI_BERN> launch (A/B measurements)
-    bool allow_block_fused = true;   // IWAE_NO_BLOCK_FUSED=1: a BasicBlock on few rows stays three dense_kernel launches (A/B measurements)
+    bool allow_out_in_block = true;  // option no_out_in_block: the output layer of a few-row decoder stays a dense_kernel<EPI_BERN> launch (A/B measurements)
+    bool allow_block_fused = true;   // option no_block_fused: a BasicBlock on few rows stays three dense_kernel launches (A/B measurements)
     int num_cus = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    bool bern_qw_force = false;      // IWAE_BERN_QW_FORCE=1: that shape at every row count it exists for (tests)
-    bool bern_qw = true;             // IWAE_NO_BERN_QW=1: the decoder kernel's 8-wave / 128-row shape instead of 16 waves / 200 rows (A/B measurements)
-    bool allow_dec_fused = true;     // IWAE_NO_DEC_FUSED=1: the two tanh layers of the decoder stay dense_kernel launches (A/B measurements)
-    bool allow_bern_pipe = true;   // IWAE_NO_BERN_PIPE=1: the Bernoulli forward stays on dense_kernel<EPI_BERN> (A/B measurements)
-    bool allow_defer = true;    // IWAE_NO_DEFER=1: always join at the end of the step (A/B measurements)
+    bool bern_qw_force = false;      // option bern_qw_force: that shape at every row count it exists for (tests)
+    bool bern_qw = true;             // option no_bern_qw: the decoder kernel's 8-wave / 128-row shape instead of 16 waves / 200 rows (A/B measurements)
+    bool allow_dec_fused = true;     // option no_dec_fused: the two tanh layers of the decoder stay dense_kernel launches (A/B measurements)
+    bool allow_bern_pipe = true;   // option no_bern_pipe: the Bernoulli forward stays on dense_kernel<EPI_BERN> (A/B measurements)
+    bool allow_defer = true;    // option no_defer: always join at the end of the step (A/B measurements)
     int wout_split = 0, wout_wg1 = 56, wout_wg2 = 128;      // option wout_split (percent of the rows, 0 = off; round 5): the output layer's weight gradient as an EARLY launch on few
                                 // workgroups beside dec_bwd_kernel (rows [0, R1)) and a LATE one behind it (the rest, beside the hidden layers' gradients)
     bool defer_split = false;   // option defer_split (round 5): 1-layer step, each side stream sums + updates the decoder layers whose gradients IT carried
@@ -520,17 +528,17 @@ EpsSrc eps_src(iwae_model* m, int layer) {
     if (m->user_eps) e.user = ptr<float>(m->epsbuf) + (layer == 0 ? 0 : (size_t)m->k * m->B * m->D[0]);
     e.B = m->B;
     e.seed = m->cfg.seed;
-    e.row_offset = (uint64_t)m->batch_offset * (uint64_t)m->k;
+    e.row_offset = (uint64_t)m->call.batch_offset * (uint64_t)m->k;
     e.step = m->noise_step;
     e.stream = (uint32_t)layer;
-    if (m->eval_k_total > 0) {      // k-chunked evaluation: the unchunked call's Philox rows
-        e.k_total = m->eval_k_total; e.s_off = m->eval_s_off; e.kc = m->k;
-        e.row_offset = (uint64_t)m->batch_offset * (uint64_t)m->eval_k_total;
+    if (m->call.k_total > 0) {      // k-chunked evaluation: the unchunked call's Philox rows
+        e.k_total = m->call.k_total; e.s_off = m->call.s_off; e.kc = m->k;
+        e.row_offset = (uint64_t)m->call.batch_offset * (uint64_t)m->call.k_total;
     }
     return e;
 }
 
-// diagnostic (STAMPS=1 build + IWAE_DENSE_STAMPS="<epi>:<KT>"): record the phase stamps of the matching dense launch
+// diagnostic (STAMPS=1 build + options dense_stamps_epi / dense_stamps_kt): record the phase stamps of the matching dense launch
 int attach_dense_stamps(iwae_model* m, int epi, DenseArgs& a) {
     if (m->dstamp_epi != epi || m->dstamp_kt != a.KT || (a.M < 4096 && a.KT <= 8)) return IWAE_OK;
     m->dstamp_waves = std::max(((a.M + 127) / 128) * ((a.MG + a.mg_per_block - 1) / a.mg_per_block) * 4, epi == EPI_BERN ? ((a.M + 127) / 128) * 16 : 0);      // (bern_pipe_kernel: <= 16 waves per 128+ rows)
@@ -618,7 +626,7 @@ int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R,
 int wgradp_plan(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP, int rows, WgradPArgs& a, int& nsplit, int& nw) {
     const int chunks = (rows + 63) / 64;
     nw = (L.JT > 8 && chunks >= 128) ? 16 : 8;
-    if (nw == 16 && L.IT <= 14 && m->allow_wg7) nw = (m->wg_shape9 & (L.JT > 16 ? 1 : 2)) ? 9 : 7;      // IWAE_WG9: bit 0 the output layer, bit 1 the hidden layers
+    if (nw == 16 && L.IT <= 14 && m->allow_wg7) nw = (m->wg_shape9 & (L.JT > 16 ? 1 : 2)) ? 9 : 7;      // option wg9: bit 0 the output layer, bit 1 the hidden layers
     const int blocks = ((L.JT + wgradp_strip(nw) - 1) / wgradp_strip(nw)) * ((L.IT + 15) / 16);
     // Workgroup targets (measured at k=50, B=1024).  Early builds, the weight gradients alone on the machine: 64 -> 0.501,
     // 128 -> 0.425, 256 -> 0.406, 384 -> 0.443 ms/step (fewer leaves CUs idle, more pays a full fp32 slab per extra split).
@@ -835,7 +843,7 @@ int draw_eps(iwae_model* m, int par, uint32_t step, int M, hipStream_t gs, int m
         if (!(m->abl_skip & 16)) launch_eps_gen(e, M, m->D[l], eps_ld(m, l), ptr<float>(m->epsc[par][l]), gs, max_blocks);
     }
     HIPCHK(hipGetLastError());
-    tg.valid = true; tg.step = step; tg.row_offset = (uint64_t)m->batch_offset * (uint64_t)m->k; tg.M = M;
+    tg.valid = true; tg.step = step; tg.row_offset = (uint64_t)m->call.batch_offset * (uint64_t)m->k; tg.M = M;
     return IWAE_OK;
 }
 
@@ -853,12 +861,12 @@ int draw_eps_multi(iwae_model* m, int buf, uint32_t step0, int M, hipStream_t gs
         launch_eps_gen_multi(e, M, m->D[l], eps_ld(m, l), ptr<float>(m->epsm[buf][l]), EPSM_STEPS, stride, gs);
     }
     HIPCHK(hipGetLastError());
-    tg.valid = true; tg.step0 = step0; tg.row_offset = (uint64_t)m->batch_offset * (uint64_t)m->k; tg.M = M;
+    tg.valid = true; tg.step0 = step0; tg.row_offset = (uint64_t)m->call.batch_offset * (uint64_t)m->k; tg.M = M;
     return IWAE_OK;
 }
 // the multi-step buffer that holds the draws of `step` for this batch shape, or -1
 int epsm_find(const iwae_model* m, uint32_t step, int M) {
-    const uint64_t ro = (uint64_t)m->batch_offset * (uint64_t)m->k;
+    const uint64_t ro = (uint64_t)m->call.batch_offset * (uint64_t)m->k;
     for (int i = 0; i < 2; ++i) {
         const iwae_model::EpsMTag& t = m->epsm_tag[i];
         if (t.valid && t.M == M && t.row_offset == ro && step - t.step0 < (uint32_t)EPSM_STEPS) return i;      // (unsigned: step >= step0)
@@ -883,30 +891,60 @@ bool dec_bwd_rows_planned(const iwae_model* m, int M) {
     return M <= m->dec_rows_max && m->allow_block_fused && m->cfg.n_layers == 1;
 }
 
-int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd,
-                 const iwae_tensors* want) {
+// What both forward passes start with: the argument checks, the conditional model's y rows of these images (*cond, null without) and the
+// handle's per-call state.  A call that is refused leaves that state as it was.
+int begin_forward(iwae_model* m, const float* x, int B, int k, float beta, const FwdCall& call, const float** cond) {
     const bool from_ds = m->ds_start >= 0;
     if ((!x && !from_ds) || B <= 0 || k <= 0) return fail(IWAE_ERR_ARG, "forward: need x, B > 0, k > 0");
     if ((int64_t)B * k > (int64_t)1 << 30) return fail(IWAE_ERR_ARG, "forward: B*k too large");
-    const bool two = m->cfg.n_layers == 2;
-    m->B = B; m->k = k; m->M = B * k; m->beta = beta;
-    m->bf16_side_used = true;
-    if (m->f32_z_pending) { HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->f32_z_pending = false; }      // (ev_join is this path's too)
-    m->lse_pending = false;      // (set again below if this step leaves its log-mean-exp to the backward pass)
-    m->time_this = m->timing > 0 && (m->timing_calls++ % m->timing) == 0;
-    m->Mp = round_up(m->M, 128); m->Bp = round_up(B, 128);
-    const int M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X, Xp = m->Xp32, Xinp = m->Xinp;
-    hipStream_t st = m->stream;
-    const float* cond = nullptr;
+    const int row0 = from_ds ? 0 : call.cond_row0;
+    *cond = nullptr;
     if (m->C > 0) {
         if (from_ds) {      // (x, y) from the resident set: the input kernel writes onehot(y) of the batch's images into m->cond (tasks/task05.py:296-322)
             if (!m->ds_has_labels) return fail(IWAE_ERR_STATE, "conditional model on the resident dataset: call iwae_dataset_set_labels first");
             CHK(ensure(m->cond, (size_t)B * m->C * 4, m->stream));
-            m->cond_n = B; m->cond_row0 = 0;
+            m->cond_n = B;
         }
-        if (m->cond_row0 + B > m->cond_n) return fail(IWAE_ERR_STATE, "conditional model: call iwae_set_condition with y for these images first");
-        cond = ptr<float>(m->cond) + (size_t)m->cond_row0 * m->C;
+        if (row0 + B > m->cond_n) return fail(IWAE_ERR_STATE, "conditional model: call iwae_set_condition with y for these images first");
+        *cond = ptr<float>(m->cond) + (size_t)row0 * m->C;
     }
+    m->call = call; m->call.cond_row0 = row0;
+    m->B = B; m->k = k; m->M = B * k; m->beta = beta;
+    m->Mp = round_up(m->M, 128); m->Bp = round_up(B, 128);
+    return IWAE_OK;
+}
+
+// The batch on the device: rows ds_start.. of the resident set, gathered by the epoch's order and binarised on the fly (main.py:117-120) into the
+// bf16 rows m->xP -- and, keep_f32, into the float32 rows m->xin -- or the caller's x (host batches are staged in m->xin, device batches read in
+// place).  *xd: the float32 rows, null where none were kept.
+int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float** xd) {
+    *xd = x;
+    if (m->ds_start >= 0) {
+        CHK(ensure(m->xP, (size_t)m->Bp * m->Xinp * 2, m->stream));
+        if (keep_f32) CHK(ensure(m->xin, (size_t)B * m->X * 4, m->stream));
+        float* xf = keep_f32 ? ptr<float>(m->xin) : nullptr;
+        launch_gather_binarize(ptr<uint8_t>(m->ds_data), ptr<int32_t>(m->ds_order), m->ds_start, m->ds_N, B, m->X, m->Xinp, m->Bp, m->cfg.seed, m->ds_epoch,
+                               ptr<uint16_t>(m->xP), xf, m->stream, m->C > 0 ? ptr<uint8_t>(m->ds_labels) : nullptr, m->C, m->C > 0 ? ptr<float>(m->cond) : nullptr);
+        m->ds_start = -1;
+        *xd = xf;
+    } else if (!is_device_ptr(x, m->cfg.device)) {
+        CHK(copy_in(m, m->xin, x, (size_t)B * m->X * 4));
+        *xd = ptr<float>(m->xin);
+    }
+    return IWAE_OK;
+}
+
+int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd,
+                 const iwae_tensors* want, const FwdCall& call) {
+    const float* cond;
+    CHK(begin_forward(m, x, B, k, beta, call, &cond));
+    const bool two = m->cfg.n_layers == 2;
+    m->bf16_side_used = true;
+    if (m->f32_z_pending) { HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->f32_z_pending = false; }      // (ev_join is this path's too)
+    m->lse_pending = false;      // (set again below if this step leaves its log-mean-exp to the backward pass)
+    m->time_this = m->timing > 0 && (m->timing_calls++ % m->timing) == 0;
+    const int M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X, Xp = m->Xp32, Xinp = m->Xinp;
+    hipStream_t st = m->stream;
     m->user_eps = eps != nullptr;
     // ---- the step's N(0,1) draws: normally already there (prefetched by the previous training step), else drawn now
     // (round 4: a forward-only call on many rows -- the k = 5000 evaluator on bf16 operands -- also takes its draws from eps_gen_kernel, so that the
@@ -915,7 +953,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     const bool keep_eps = !eps && (bwd || two || zin_eval);
     m->epsc_ptr[0] = m->epsc_ptr[1] = nullptr;
     // few data rows, training step, single-stream backward (dec_rows_step): the draws come from the multi-step buffers (one launch per EPSM_STEPS steps)
-    const bool eps_multi = keep_eps && bwd && !two && m->allow_eps_multi && m->eval_k_total == 0 && dec_rows_step(m, M, B);
+    const bool eps_multi = keep_eps && bwd && !two && m->allow_eps_multi && call.k_total == 0 && dec_rows_step(m, M, B);
     if (eps_multi) {
         int bi = epsm_find(m, m->noise_step, M);
         if (bi < 0) {      // (first step, another batch shape, a jump of iwae_set_step: drawn now, in stream order)
@@ -927,33 +965,23 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     } else
     if (keep_eps) {
         const int np = (m->epsc_par + 1) % 3;
-        const uint64_t ro = (uint64_t)m->batch_offset * (uint64_t)k;
+        const uint64_t ro = (uint64_t)call.batch_offset * (uint64_t)k;
         iwae_model::EpsTag& tg = m->eps_tag[np];
-        if (m->eval_k_total > 0 || !(tg.valid && tg.step == m->noise_step && tg.row_offset == ro && tg.M == M)) {
+        if (call.k_total > 0 || !(tg.valid && tg.step == m->noise_step && tg.row_offset == ro && tg.M == M)) {
             CHK(join_side(m));          // a speculative draw into this slot may still be on a side stream
             if (m->side) HIPCHK(hipStreamSynchronize(m->side));
             if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
             CHK(draw_eps(m, np, m->noise_step, M, st));
-            if (m->eval_k_total > 0) m->eval_tag_kill = np;      // (a k-chunk's draws: the tag does not describe them)
+            if (call.k_total > 0) tg.valid = false;      // (a k-chunk's draws: the tag does not describe them)
         }
-        if (m->eval_tag_kill >= 0) { m->eps_tag[m->eval_tag_kill].valid = false; m->eval_tag_kill = -1; }
         if (bwd) m->epsc_par = np;      // (forward-only calls -- the evaluator's launches -- reuse ONE slot: stream order protects it, and three slots of 2^21 rows are 2.5 GB grown inside the first calls)
         for (int l = 0; l < m->cfg.n_layers; ++l) m->epsc_ptr[l] = ptr<float>(m->epsc[np][l]);
     }
     if (eps) CHK(copy_in(m, m->epsbuf, eps, (size_t)M * (m->D[0] + (two ? m->D[1] : 0)) * 4));
     CHK(ensure(m->xP, (size_t)Bp * Xinp * 2, st));
-    const float* xf_pending = nullptr;
-    if (from_ds) {
-        // main.py:117-120 on the device: gather the batch by the epoch's order and binarise it on the fly
-        launch_gather_binarize(ptr<uint8_t>(m->ds_data), ptr<int32_t>(m->ds_order), m->ds_start, m->ds_N, B, X, Xinp, Bp, m->cfg.seed,
-                               m->ds_epoch, ptr<uint16_t>(m->xP), nullptr, st, m->C > 0 ? ptr<uint8_t>(m->ds_labels) : nullptr, m->C, m->C > 0 ? ptr<float>(m->cond) : nullptr);
-        m->ds_start = -1;
-    } else {
-        const float* xd = x;
-        if (!is_device_ptr(x, m->cfg.device)) {       // host batches are staged; device batches are read in place
-            CHK(copy_in(m, m->xin, x, (size_t)B * X * 4));
-            xd = ptr<float>(m->xin);
-        }
+    const float *xd, *xf_pending = nullptr;
+    CHK(stage_input(m, x, B, false, &xd));
+    if (xd) {      // (the resident set's rows are in m->xP already)
         if (m->C == 0 && m->allow_block_fused) xf_pending = xd;      // the fused encoder kernel converts the rows itself
         else launch_prep_rows(xd, cond, B, X, m->C, Xinp, Bp, ptr<uint16_t>(m->xP), st);
     }
@@ -1006,7 +1034,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         s.prior_head = m->has_prior ? ptr<float>(m->wprior.head) : nullptr;
         s.lp_prior = two ? nullptr : t1;
         s.lq = two ? t3 : t2;
-        const bool want_dreg = !two && (objective == OBJ_DREG || (!bwd && !m->in_eval_llh));    // tasks/task02.py:63-65
+        const bool want_dreg = !two && (objective == OBJ_DREG || (!bwd && !call.log_w_only));    // tasks/task02.py:63-65
         s.lq_dreg = want_dreg ? lqd : nullptr;
         // 1-layer training step on the device's own noise: the first decoder layer makes z itself (dense_kernel ZIN mode)
         // (the DReG step too: the decoder kernel's prologue also sums the second log q; if that kernel turns out not to apply, sample_kernel runs after all)
@@ -1099,9 +1127,9 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
             a.head = nullptr;
             a.cz_on = 0.f;
         }
-        a.lq_dreg = (!two && (objective == OBJ_DREG || (!bwd && !m->in_eval_llh))) ? lqd : nullptr;
+        a.lq_dreg = (!two && (objective == OBJ_DREG || (!bwd && !call.log_w_only))) ? lqd : nullptr;
         a.B = B; a.k = k; a.beta = two ? 1.f : beta; a.objective = objective;
-        a.lme_only = (!bwd && m->in_eval_llh && !want) ? 1 : 0;
+        a.lme_only = (!bwd && call.log_w_only && !want) ? 1 : 0;
         a.logw = ptr<float>(m->logw); a.wn = ptr<float>(m->wn); a.gx = ptr<float>(m->gx);
         a.cf = ptr<float4>(m->cf); a.per_b = ptr<float>(m->per_b);
         a.n_px_part = 1; a.px_stride = (size_t)Mp; a.term0_out = lpxz;
@@ -1375,7 +1403,7 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
                 dz_half = !two && m->allow_dz_half;
                 if (dz_half) d.DZH = (uint16_t*)w.dz.p;
                 d.nw = m->dec_bwd_nw;
-                if (m->dstamp_epi == 9) {      // diagnostic (STAMPS=1 build, IWAE_DENSE_STAMPS=9:0): phase stamps of dec_bwd_kernel
+                if (m->dstamp_epi == 9) {      // diagnostic (STAMPS=1 build, option dense_stamps_epi = 9): phase stamps of dec_bwd_kernel
                     m->dstamp_waves = ((M + 127) / 128) * (L.KT == 7 ? m->dec_bwd_nw : 4);
                     CHK(ensure(m->dstamps, (size_t)m->dstamp_waves * 64, st));
                     d.o.stamps = ptr<unsigned long long>(m->dstamps);
@@ -1781,7 +1809,7 @@ int adam_impl(iwae_model* m, float lr, float gscale) {
 // work in float32 (sampling + densities, lse_kernel, latent_bwd_kernel, gauss_*_kernel, Adam) are shared.
 int f32_gemm(iwae_model* m, const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc, int M, int N, int K,
              const float* bias, int epi, const float* ACT, long ldact, bool accumulate, const float* brow_scale = nullptr, const float* orow_scale = nullptr,
-             hipStream_t st = nullptr) {
+             hipStream_t st = nullptr, bool no_ksplit = false) {
     GemmF32Args a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.sam = sam; a.sak = sak; a.B = B; a.sbk = sbk; a.sbn = sbn; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
@@ -1789,13 +1817,13 @@ int f32_gemm(iwae_model* m, const float* A, long sam, long sak, const float* B, 
     a.brow_scale = brow_scale; a.orow_scale = orow_scale;
     {   // few rows (the encoder on the batch's images): K split + one reduction pass that carries the epilogue
         hipStream_t s_ = st ? st : m->stream;
-        // (not inside iwae_eval_llh: the split depends on how many images a launch holds, and an image's estimate must not -- the evaluator's
+        // (no_ksplit, iwae_eval_llh: the split depends on how many images a launch holds, and an image's estimate must not -- the evaluator's
         // encoder is 419 rows beside 2^21 decoder rows, nothing to gain there: test_eval_llh_images_per_launch_are_invisible)
-        const int ns = m->in_eval_llh ? 1 : gemm_f32_fewrows_split(M, N, K);
+        const int ns = no_ksplit ? 1 : gemm_f32_fewrows_split(m->gemm_f32, M, N, K);
         if (ns > 1 && !brow_scale) {
             a.avec = a.bvec = 0;
             CHK(ensure(m->f32.kslab, (size_t)ns * M * N * 4, s_));
-            launch_gemm_f32_fewrows(a, ptr<float>(m->f32.kslab), s_);
+            launch_gemm_f32_fewrows(m->gemm_f32, a, ptr<float>(m->f32.kslab), s_);
             HIPCHK(hipGetLastError());
             return IWAE_OK;
         }
@@ -1807,13 +1835,13 @@ int f32_gemm(iwae_model* m, const float* A, long sam, long sak, const float* B, 
         a.stamps = ptr<unsigned long long>(m->dstamps);
     }
 #endif
-    launch_gemm_f32(a, 1, st ? st : m->stream);
+    launch_gemm_f32(m->gemm_f32, a, 1, st ? st : m->stream);
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
 // Y = epi(X W + b), W = the Keras kernel [in, out] of layer kl inside the flat float32 parameters
-int f32_fwd(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, int rows, float* Y, long ldy, int epi) {
-    return f32_gemm(m, X, ldx, 1, m->param + kl.offW, kl.Nout, 1, Y, ldy, rows, kl.Nout, kl.Kin, m->param + kl.offb, epi, nullptr, 0, false);
+int f32_fwd(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, int rows, float* Y, long ldy, int epi, bool no_ksplit) {
+    return f32_gemm(m, X, ldx, 1, m->param + kl.offW, kl.Nout, 1, Y, ldy, rows, kl.Nout, kl.Kin, m->param + kl.offb, epi, nullptr, 0, false, nullptr, nullptr, nullptr, no_ksplit);
 }
 // DX (+)= (G W^T) * (1 - ACT^2)   (ACT = the stored tanh output of the layer below, or null)
 // (rowscale: row r of G counts with weight rowscale[r] -- applied to the product's rows, in front of the tanh' factor)
@@ -1849,8 +1877,8 @@ int f32_flush_reductions(iwae_model* m, int seg = -1) {
 int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const float* G, long ldg, int rows, const float* rowscale = nullptr, int seg = 0, int tile_mode = 0) {
     hipStream_t st = seg == 1 ? m->side : m->stream;
     // row splits: enough workgroups to fill the machine (~1 000 tiles of 64 x 64 or 128 x 128), at least 64 rows per split
-    const int tiles = (int)gemm_f32_tiles(kl.Kin + 1, kl.Nout, tile_mode);      // (+ 1: the row of ones whose product row is the bias gradient)
-    const int slots = std::min(m->f32_dw_tiles, gemm_f32_slots(kl.Kin + 1, kl.Nout, tile_mode));
+    const int tiles = (int)gemm_f32_tiles(m->gemm_f32, kl.Kin + 1, kl.Nout, tile_mode);      // (+ 1: the row of ones whose product row is the bias gradient)
+    const int slots = std::min(m->f32_dw_tiles, gemm_f32_slots(m->gemm_f32, kl.Kin + 1, kl.Nout, tile_mode));
     int nsplit = std::max(1, std::min(std::min(256, rows / m->f32_dw_min_rows), slots / tiles));      // (rounded DOWN: 1 027 workgroups on 1 024 slots are a second round of 3)
     while (nsplit > 8 && (tiles * nsplit) % 8 != 0) --nsplit;      // (a multiple of 8 workgroups: gemm_f32_v2_kernel then keeps a split's tiles on one XCD)
     const size_t nW = (size_t)kl.Kin * kl.Nout;
@@ -1875,7 +1903,7 @@ int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const 
     // the bias gradient = the column sums of (weighted) G = the product row of a row of ONES appended to X^T (GemmF32Args.Cones): no pass of its own
     if (ns == 1) {
         a.C = m->grad + kl.offW; a.ldc = kl.Nout; a.slab_stride = 0; a.Cones = m->grad + kl.offb; a.cones_stride = 0;
-        launch_gemm_f32(a, 1, st);
+        launch_gemm_f32(m->gemm_f32, a, 1, st);
     } else {
         a.C = slabW; a.ldc = kl.Nout; a.slab_stride = nW; a.Cones = slabB; a.cones_stride = (size_t)kl.Nout;
 #ifdef IWAE_DENSE_STAMPS
@@ -1885,7 +1913,7 @@ int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const 
             a.stamps = ptr<unsigned long long>(m->dstamps);
         }
 #endif
-        launch_gemm_f32(a, ns, st);
+        launch_gemm_f32(m->gemm_f32, a, ns, st);
         if (queue) {
             m->f32_pending.push_back({(size_t)(slabW - ptr<float>(m->f32.slab)), nW, nW, m->grad + kl.offW, ns, seg});
             m->f32_pending.push_back({(size_t)(slabB - ptr<float>(m->f32.slab)), (size_t)kl.Nout, (size_t)kl.Nout, m->grad + kl.offb, ns, seg});
@@ -1900,16 +1928,15 @@ int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const 
     return IWAE_OK;
 }
 // BasicBlock (iwae1.py:36-44) on R rows: X [R][ldx] -> h1, h2 [R][H], head [R][2Dp] (mu at 0.., sigma = exp(.)+1e-6 at Dp..)
-int f32_block_fwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, float* head, int Dp, bool bwd) {
+int f32_block_fwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, float* head, int Dp, bool no_ksplit) {
     const KerasLayer *l1 = &m->klayers[base], *l2 = l1 + 1, *lmu = l1 + 2, *lsd = l1 + 3;
-    const int H = l1->Nout, D = lmu->Nout;
+    const int H = l1->Nout;
     CHK(ensure(w.h1, (size_t)R * H * 4, m->stream));
     CHK(ensure(w.h2, (size_t)R * H * 4, m->stream));
-    CHK(f32_fwd(m, *l1, X, ldx, R, ptr<float>(w.h1), H, GEMM_EPI_TANH));
-    CHK(f32_fwd(m, *l2, ptr<float>(w.h1), H, R, ptr<float>(w.h2), H, GEMM_EPI_TANH));
-    CHK(f32_fwd(m, *lmu, ptr<float>(w.h2), H, R, head, 2 * Dp, GEMM_EPI_NONE));
-    CHK(f32_fwd(m, *lsd, ptr<float>(w.h2), H, R, head + Dp, 2 * Dp, GEMM_EPI_EXP));
-    (void)D; (void)bwd;
+    CHK(f32_fwd(m, *l1, X, ldx, R, ptr<float>(w.h1), H, GEMM_EPI_TANH, no_ksplit));
+    CHK(f32_fwd(m, *l2, ptr<float>(w.h1), H, R, ptr<float>(w.h2), H, GEMM_EPI_TANH, no_ksplit));
+    CHK(f32_fwd(m, *lmu, ptr<float>(w.h2), H, R, head, 2 * Dp, GEMM_EPI_NONE, no_ksplit));
+    CHK(f32_fwd(m, *lsd, ptr<float>(w.h2), H, R, head + Dp, 2 * Dp, GEMM_EPI_EXP, no_ksplit));
     return IWAE_OK;
 }
 // backward of a BasicBlock from dhead [R][2Dp] (d mu | d pre-exp): all four weight gradients, optionally dX [R][lddx]
@@ -1930,23 +1957,11 @@ int f32_block_bwd(iwae_model* m, int base, iwae_model::F32Block& w, const float*
     return IWAE_OK;
 }
 
-int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd, const iwae_tensors* want) {
-    const bool from_ds = m->ds_start >= 0;
-    if ((!x && !from_ds) || B <= 0 || k <= 0) return fail(IWAE_ERR_ARG, "forward: need x, B > 0, k > 0");
-    if ((int64_t)B * k > (int64_t)1 << 30) return fail(IWAE_ERR_ARG, "forward: B*k too large");
-    const float* cond = nullptr;      // conditional models (tasks/task05.py, tasks/task04.py): y of these images
-    if (m->C > 0) {
-        if (from_ds) {      // (x, y) from the resident set: the input kernel writes onehot(y) of the batch's images into m->cond (tasks/task05.py:296-322)
-            if (!m->ds_has_labels) return fail(IWAE_ERR_STATE, "conditional model on the resident dataset: call iwae_dataset_set_labels first");
-            CHK(ensure(m->cond, (size_t)B * m->C * 4, m->stream));
-            m->cond_n = B; m->cond_row0 = 0;
-        }
-        if (m->cond_row0 + B > m->cond_n) return fail(IWAE_ERR_STATE, "conditional model: call iwae_set_condition with y for these images first");
-        cond = ptr<float>(m->cond) + (size_t)m->cond_row0 * m->C;
-    }
-    const bool two = m->cfg.n_layers == 2;
-    m->B = B; m->k = k; m->M = B * k; m->beta = beta;
-    m->Mp = round_up(m->M, 128); m->Bp = round_up(B, 128);
+int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd, const iwae_tensors* want,
+                const FwdCall& call) {
+    const float* cond;      // conditional models (tasks/task05.py, tasks/task04.py): y of these images
+    CHK(begin_forward(m, x, B, k, beta, call, &cond));
+    const bool two = m->cfg.n_layers == 2, nks = call.no_ksplit;
     m->time_this = false;
     const int M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X;
     hipStream_t st = m->stream;
@@ -1962,21 +1977,14 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
     if (!eps) {       // the step's draws, kept for the backward pass and the 2-layer densities (same generator as the bf16 path)
         const int np = (m->epsc_par + 1) % 3;
         CHK(draw_eps(m, np, m->noise_step, M, st));
-        if (m->eval_k_total > 0) m->eps_tag[np].valid = false;      // a k-chunk's draws: the tag (step, offset, rows) does not describe them
+        if (call.k_total > 0) m->eps_tag[np].valid = false;      // a k-chunk's draws: the tag (step, offset, rows) does not describe them
         if (bwd) m->epsc_par = np;      // (forward-only calls reuse one slot, as in forward_impl)
         for (int l = 0; l < m->cfg.n_layers; ++l) m->epsc_ptr[l] = ptr<float>(m->epsc[np][l]);
     } else {
         CHK(copy_in(m, m->epsbuf, eps, (size_t)M * (m->D[0] + (two ? m->D[1] : 0)) * 4));
     }
-    const float* xd = x;
-    if (from_ds) {      // main.py:117-120 on the device: gather + binarise, keeping the float32 copy of the batch
-        CHK(ensure(m->xP, (size_t)Bp * m->Xinp * 2, st));
-        CHK(ensure(m->xin, (size_t)B * X * 4, st));
-        launch_gather_binarize(ptr<uint8_t>(m->ds_data), ptr<int32_t>(m->ds_order), m->ds_start, m->ds_N, B, X, m->Xinp, Bp, m->cfg.seed,
-                               m->ds_epoch, ptr<uint16_t>(m->xP), ptr<float>(m->xin), st, m->C > 0 ? ptr<uint8_t>(m->ds_labels) : nullptr, m->C, m->C > 0 ? ptr<float>(m->cond) : nullptr);
-        m->ds_start = -1;
-        xd = ptr<float>(m->xin);
-    } else if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, m->xin, x, (size_t)B * X * 4)); xd = ptr<float>(m->xin); }
+    const float* xd;
+    CHK(stage_input(m, x, B, true, &xd));
     m->f32_x = xd;
     // ---- encoder on the images (conditional models: on concat(x, y), tasks/task05.py:113-118)
     const int b_enc1 = m->enc1[0].sub[0];
@@ -1987,10 +1995,10 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
         launch_concat_f32(xd, X, cond, m->C, B, ptr<float>(m->f32.xcat), st);
         xenc = ptr<float>(m->f32.xcat);
     }
-    CHK(f32_block_fwd(m, b_enc1, m->f32.enc1, xenc, X + m->C, B, ptr<float>(m->wenc1.head), m->Dp[0], bwd));
+    CHK(f32_block_fwd(m, b_enc1, m->f32.enc1, xenc, X + m->C, B, ptr<float>(m->wenc1.head), m->Dp[0], nks));
     if (m->has_prior) {     // p(z|y) = N(mu_p(y), sigma_p(y)): the prior block on the B condition rows (tasks/task04.py:108,124)
         CHK(ensure(m->wprior.head, (size_t)Bp * 2 * m->Dp[0] * 4, st));
-        CHK(f32_block_fwd(m, m->prior[0].sub[0], m->f32.prior, cond, m->C, B, ptr<float>(m->wprior.head), m->Dp[0], bwd));
+        CHK(f32_block_fwd(m, m->prior[0].sub[0], m->f32.prior, cond, m->C, B, ptr<float>(m->wprior.head), m->Dp[0], nks));
     }
     for (int i = 0; i < 6; ++i) CHK(ensure(m->rows[i], (size_t)Mp * 4, st));
     float* lpxz = ptr<float>(m->rows[0]);
@@ -2016,14 +2024,14 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
         s.prior_head = m->has_prior ? ptr<float>(m->wprior.head) : nullptr;
         s.lp_prior = two ? nullptr : t1;
         s.lq = two ? t3 : t2;
-        const bool want_dreg = !two && (objective == OBJ_DREG || (!bwd && !m->in_eval_llh));
+        const bool want_dreg = !two && (objective == OBJ_DREG || (!bwd && !call.log_w_only));
         s.lq_dreg = want_dreg ? lqd : nullptr;
         launch_sample(s, st);
     }
     if (two) {       // q(z2|z1), z2, p(z1|z2)  (iwae2.py:63-65, :90, :118-124)
         const int b_enc2 = m->enc2[0].sub[0], b_dec2 = m->dec2[0].sub[0];
         CHK(ensure(m->wenc2.head, (size_t)Mp * 2 * m->Dp[1] * 4, st));
-        CHK(f32_block_fwd(m, b_enc2, m->f32.enc2, ptr<float>(m->f32.z[0]), m->D[0], M, ptr<float>(m->wenc2.head), m->Dp[1], bwd));
+        CHK(f32_block_fwd(m, b_enc2, m->f32.enc2, ptr<float>(m->f32.z[0]), m->D[0], M, ptr<float>(m->wenc2.head), m->Dp[1], nks));
         CHK(ensure(m->f32.z[1], (size_t)Mp * m->D[1] * 4, st));
         SampleArgs s;
         memset(&s, 0, sizeof(s));
@@ -2033,7 +2041,7 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
         s.lp_prior = t2; s.lq = t4; s.lq_dreg = nullptr;
         launch_sample(s, st);
         CHK(ensure(m->wdec2.head, (size_t)Mp * 2 * m->Dp[0] * 4, st));
-        CHK(f32_block_fwd(m, b_dec2, m->f32.dec2, ptr<float>(m->f32.z[1]), m->D[1], M, ptr<float>(m->wdec2.head), m->Dp[0], bwd));
+        CHK(f32_block_fwd(m, b_dec2, m->f32.dec2, ptr<float>(m->f32.z[1]), m->D[1], M, ptr<float>(m->wdec2.head), m->Dp[0], nks));
         GaussLpArgs g;
         memset(&g, 0, sizeof(g));
         g.zhead = ptr<float>(m->wenc1.head); g.ldZH = 2 * m->Dp[0]; g.Dzp = m->Dp[0];
@@ -2079,8 +2087,8 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
 #endif
         launch_dec_fwd_f32(df, st);
     } else {
-    CHK(f32_fwd(m, *d1, ptr<float>(m->f32.z[0]), Dz, M, ptr<float>(m->f32.g1), H, GEMM_EPI_TANH));
-    CHK(f32_fwd(m, *d2, ptr<float>(m->f32.g1), H, M, ptr<float>(m->f32.g2), H, GEMM_EPI_TANH));
+    CHK(f32_fwd(m, *d1, ptr<float>(m->f32.z[0]), Dz, M, ptr<float>(m->f32.g1), H, GEMM_EPI_TANH, nks));
+    CHK(f32_fwd(m, *d2, ptr<float>(m->f32.g1), H, M, ptr<float>(m->f32.g2), H, GEMM_EPI_TANH, nks));
     // forward-only calls at large row counts (the k = 5000 evaluator): log p(x|z) in the epilogue of the output layer's GEMM -- the float32
     // logits (1.6 GB per launch of 2^19 rows) are neither written nor read back; per 64-column half tile a partial sum that lse_kernel adds
     // Round 3, training step: the same epilogue also leaves s = x - sigmoid(l) where the logits would have gone -- the backward pass reads s and
@@ -2101,10 +2109,10 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
             m->f32_keeps_s = true;
         }
         ga.XB = xd; ga.bern_k = k; ga.bern_X = X; ga.part = ptr<float>(m->px_part); ga.part_stride = (size_t)Mp;
-        launch_gemm_f32(ga, 1, st);
+        launch_gemm_f32(m->gemm_f32, ga, 1, st);
     } else {
     CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
-    CHK(f32_fwd(m, *d3, ptr<float>(m->f32.g2), H, M, ptr<float>(m->f32.logits), X, GEMM_EPI_NONE));
+    CHK(f32_fwd(m, *d3, ptr<float>(m->f32.g2), H, M, ptr<float>(m->f32.logits), X, GEMM_EPI_NONE, nks));
     launch_bern_f32(ptr<float>(m->f32.logits), X, xd, X, M, k, lpxz, st);
     }
     }      // (!fused_dec)
@@ -2133,9 +2141,9 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
             a.term[0] = lpxz; a.coef[0] = 1.f; a.term[1] = t1; a.coef[1] = 1.f; a.term[2] = t2; a.coef[2] = 1.f;
             a.term[3] = t3; a.coef[3] = -1.f; a.term[4] = t4; a.coef[4] = -1.f; a.head = nullptr; a.cz_on = 0.f;
         }
-        a.lq_dreg = (!two && (objective == OBJ_DREG || (!bwd && !m->in_eval_llh))) ? lqd : nullptr;
+        a.lq_dreg = (!two && (objective == OBJ_DREG || (!bwd && !call.log_w_only))) ? lqd : nullptr;
         a.B = B; a.k = k; a.beta = two ? 1.f : beta; a.objective = objective;
-        a.lme_only = (!bwd && m->in_eval_llh && !want) ? 1 : 0;
+        a.lme_only = (!bwd && call.log_w_only && !want) ? 1 : 0;
         a.logw = ptr<float>(m->logw); a.wn = ptr<float>(m->wn); a.gx = ptr<float>(m->gx);
         a.cf = ptr<float4>(m->cf); a.per_b = ptr<float>(m->per_b);
         a.n_px_part = m->px_parts; a.px_stride = (size_t)Mp; a.term0_out = lpxz;
@@ -2256,7 +2264,7 @@ int backward_f32(iwae_model* m, int objective, float fused_lr = -1.0f) {
         launch_latent_bwd(a, st);
     }
     if (m->has_prior)
-        CHK(f32_block_bwd(m, m->prior[0].sub[0], m->f32.prior, ptr<float>(m->cond) + (size_t)m->cond_row0 * m->C, m->C, B, Dp0, nullptr, 0));
+        CHK(f32_block_bwd(m, m->prior[0].sub[0], m->f32.prior, ptr<float>(m->cond) + (size_t)m->call.cond_row0 * m->C, m->C, B, Dp0, nullptr, 0));
     CHK(f32_block_bwd(m, m->enc1[0].sub[0], m->f32.enc1, m->C > 0 ? ptr<float>(m->f32.xcat) : m->f32_x, X + m->C, B, Dp0, nullptr, 0));
     m->f32_slab_want = std::max(m->f32_slab_want, m->f32_slab_want_step);
     m->split_offset = m->nparam;       // (data-parallel step: one all-reduce of the whole gradient)
@@ -2618,8 +2626,8 @@ int iwae_forward(iwae_handle m, const float* x, int32_t B, int32_t k, float beta
                  const iwae_tensors* want) {
     if (!m) return fail(IWAE_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(m->cfg.device));
-    if (m->cfg.precision == IWAE_PREC_FP32) CHK(forward_f32(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want));
-    else CHK(forward_impl(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want));
+    if (m->cfg.precision == IWAE_PREC_FP32) CHK(forward_f32(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want, FwdCall{m->batch_offset}));
+    else CHK(forward_impl(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want, FwdCall{m->batch_offset}));
     CHK(fetch_outputs(m, scalars, want));
     m->noise_step += 1;
     return IWAE_OK;
@@ -2631,10 +2639,10 @@ int iwae_forward_backward(iwae_handle m, const float* x, int32_t B, int32_t k, f
     HIPCHK(hipSetDevice(m->cfg.device));
     CHK(check_objective(m, objective));
     if (m->cfg.precision == IWAE_PREC_FP32) {
-        CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want));
+        CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
         CHK(backward_f32(m, objective));
     } else {
-        CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want));
+        CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
         CHK(backward_impl(m, objective));
     }
     CHK(fetch_outputs(m, scalars, want));
@@ -2648,11 +2656,11 @@ int iwae_forward_backward_split(iwae_handle m, const float* x, int32_t B, int32_
     HIPCHK(hipSetDevice(m->cfg.device));
     CHK(check_objective(m, objective));
     if (m->cfg.precision == IWAE_PREC_FP32) {       // float32 mode: nothing is left on the side stream (*side_offset = n)
-        CHK(forward_f32(m, x, B, k, beta, eps, objective, true, nullptr));
+        CHK(forward_f32(m, x, B, k, beta, eps, objective, true, nullptr, FwdCall{m->batch_offset}));
         CHK(backward_f32(m, objective));
         CHK(join_side(m));
     } else {
-        CHK(forward_impl(m, x, B, k, beta, eps, objective, true, nullptr));
+        CHK(forward_impl(m, x, B, k, beta, eps, objective, true, nullptr, FwdCall{m->batch_offset}));
         CHK(backward_impl(m, objective, -1.0f, true));
     }
     *side_stream = (void*)m->tail;
@@ -2706,13 +2714,13 @@ int iwae_set_option(iwae_handle m, const char* name, int64_t value) {
     else if (n == "no_defer2") m->allow_defer2 = !on;                 // 2-layer step: one reduction + update of all layers on the main stream
     else if (n == "f32_dw_tiles") m->f32_dw_tiles = std::max(1, iv);
     else if (n == "f32_dw_min_rows") m->f32_dw_min_rows = std::max(16, iv);
-    else if (n == "f32_gemm_dbg") g_gemm_f32_dbg = (int)value;         // DIAG builds: timing ablations of gemm_f32_v2_kernel (1 no fetch, 2 no stash, 4 no MFMAs, 16 no barrier)
-    else if (n == "f32_gemm_small_min") g_gemm_f32_v2_small_min = std::max(1, iv);
-    else if (n == "f32_ksplit_min_tiles") g_gemm_f32_ksplit_min_tiles = std::max(1, iv);      // ... only from that many 64 x 64 output tiles on
-    else if (n == "f32_no_ksplit") g_gemm_f32_ksplit = !on;            // ... few-row products as one 64-tile launch
-    else if (n == "f32_gemm_small_v1") g_gemm_f32_v2_small = !on;      // ... the round-3 64-tile kernel for every 64 x 64-tiled product
-    else if (n == "f32_gemm_w4") g_gemm_f32_w8 = !on;                  // ... without the 8-wave tiles (process-wide, A/B only)
-    else if (n == "f32_gemm_v1") g_gemm_f32_v2 = !on;                  // float32 GEMMs with the round-3 k loop (process-wide switch, A/B only)
+    else if (n == "f32_gemm_dbg") m->gemm_f32.dbg = iv;                // DIAG builds: timing ablations of gemm_f32_v2_kernel (1 no fetch, 2 no stash, 4 no MFMAs, 16 no barrier)
+    else if (n == "f32_gemm_small_min") m->gemm_f32.v2_small_min = std::max(1, iv);
+    else if (n == "f32_ksplit_min_tiles") m->gemm_f32.ksplit_min_tiles = std::max(1, iv);     // ... only from that many 64 x 64 output tiles on
+    else if (n == "f32_no_ksplit") m->gemm_f32.ksplit = !on;           // ... few-row products as one 64-tile launch
+    else if (n == "f32_gemm_small_v1") m->gemm_f32.v2_small = !on;     // ... the round-3 64-tile kernel for every 64 x 64-tiled product
+    else if (n == "f32_gemm_w4") m->gemm_f32.w8 = !on;                 // ... without the 8-wave tiles (A/B only)
+    else if (n == "f32_gemm_v1") m->gemm_f32.v2 = !on;                 // float32 GEMMs with the round-3 k loop (A/B only)
     else if (n == "no_f32_side") m->allow_f32_side = !on;             // float32 step on one stream (no side-stream weight gradients, no deferred decoder update)
     else if (n == "f32_dw_last") m->f32_dw_last = iv;                 // float32 step: all decoder weight gradients behind the dX chain (1: tiles as picked, 2: 4-wave tiles, 3: ... at 3 waves per SIMD)
     else if (n == "f32_wout_last") m->f32_wout_first = !on;           // ... with the output layer's gradient last on the side stream (beside the encoder's few-row kernels) instead of first (beside the dX chain)
@@ -2787,7 +2795,7 @@ int iwae_train_step(iwae_handle m, const float* x, int32_t B, int32_t k, float b
     HIPCHK(hipSetDevice(m->cfg.device));
     CHK(check_objective(m, objective));
     if (m->cfg.precision == IWAE_PREC_FP32) {   // float32 mode: forward, closed-form backward, [exchange,] Adam -- all in float32
-        CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want));
+        CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
         if (m->comm_main || want) {
             CHK(backward_f32(m, objective));
             if (want) CHK(fetch_outputs(m, nullptr, want));      // tensors refer to the pre-update forward (src/iwae1.py:162)
@@ -2800,7 +2808,7 @@ int iwae_train_step(iwae_handle m, const float* x, int32_t B, int32_t k, float b
         m->noise_step += 1;
         return IWAE_OK;
     }
-    CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want));
+    CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
     if (m->comm_main) {                         // data-parallel step: exchange between gradient and update (iwae_comm_init)
         CHK(backward_impl(m, objective, -1.0f, true, true));
         if (want) CHK(fetch_outputs(m, nullptr, want));
@@ -2931,28 +2939,21 @@ int iwae_eval_llh(iwae_handle m, const float* x, int32_t N, int32_t k, int32_t c
     const size_t xbytes = (size_t)N * m->X * 4;
     if (!is_device_ptr(x, m->cfg.device) && xbytes <= ((size_t)1 << 31)) { CHK(copy_in(m, m->eval_x, x, xbytes)); xd = ptr<float>(m->eval_x); }
     CHK(ensure(m->eval_lme, (size_t)ns * N * 4, m->stream));
-    const uint32_t saved_off = m->batch_offset;
     int rc = IWAE_OK;
     for (int i0 = 0; i0 < N && rc == IWAE_OK; i0 += chunk) {
         const int nb = std::min(chunk, N - i0);
-        m->batch_offset = saved_off + (uint32_t)i0;
-        m->cond_row0 = i0;
+        FwdCall call{m->batch_offset + (uint32_t)i0, i0};
+        call.log_w_only = call.no_ksplit = true;
         for (int si = 0; si < ns && rc == IWAE_OK; ++si) {
             const int s0 = si * kc, kn = std::min(kc, k - s0);
-            m->eval_k_total = (kc < k) ? k : 0;
-            m->eval_s_off = s0;
-            const bool f32 = m->eval_precision == IWAE_PREC_FP32;
-            m->in_eval_llh = true;
-            rc = f32 ? forward_f32(m, xd + (size_t)i0 * m->X, nb, kn, 1.0f, nullptr, OBJ_IWAE_ELBO, false, nullptr)
-                     : forward_impl(m, xd + (size_t)i0 * m->X, nb, kn, 1.0f, nullptr, OBJ_IWAE_ELBO, false, nullptr);
-            m->eval_k_total = 0; m->eval_s_off = 0; m->in_eval_llh = false;
-            if (rc != IWAE_OK) break;
-            if (hipMemcpyAsync(ptr<float>(m->eval_lme) + (size_t)si * N + i0, ptr<float>(m->per_b) + (size_t)PB_LME * nb, (size_t)nb * 4, hipMemcpyDeviceToDevice,
-                               m->stream) != hipSuccess) { rc = fail(IWAE_ERR_HIP, "eval_llh: keeping the per-image estimates failed"); break; }
+            call.k_total = kc < k ? k : 0; call.s_off = s0;
+            rc = eval_f32 ? forward_f32(m, xd + (size_t)i0 * m->X, nb, kn, 1.0f, nullptr, OBJ_IWAE_ELBO, false, nullptr, call)
+                          : forward_impl(m, xd + (size_t)i0 * m->X, nb, kn, 1.0f, nullptr, OBJ_IWAE_ELBO, false, nullptr, call);
+            if (rc == IWAE_OK && hipMemcpyAsync(ptr<float>(m->eval_lme) + (size_t)si * N + i0, ptr<float>(m->per_b) + (size_t)PB_LME * nb, (size_t)nb * 4,
+                                                hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
+                rc = fail(IWAE_ERR_HIP, "eval_llh: keeping the per-image estimates failed");
         }
-        m->cond_row0 = 0;
     }
-    m->batch_offset = saved_off;
     if (rc != IWAE_OK) { (void)hipStreamSynchronize(m->stream); return rc; }
     std::vector<float> lme((size_t)ns * N);
     if (hipMemcpyAsync(lme.data(), m->eval_lme.p, lme.size() * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
@@ -3049,10 +3050,7 @@ static int eval_enc_heads(iwae_model* m, const float* xd, int N, DevBuf& headbuf
     const int X = m->X, Xp = m->Xp32, Dp = m->Dp[0];
     if (m->eval_precision == IWAE_PREC_FP32) {
         CHK(ensure(headbuf, (size_t)N * 2 * Dp * 4, st));
-        m->in_eval_llh = true;      // (no K split of the few-row products: an image's heads must not depend on N)
-        const int rc = f32_block_fwd(m, m->enc1[0].sub[0], m->f32.enc1, xd, X, N, ptr<float>(headbuf), Dp, false);
-        m->in_eval_llh = false;
-        CHK(rc);
+        CHK(f32_block_fwd(m, m->enc1[0].sub[0], m->f32.enc1, xd, X, N, ptr<float>(headbuf), Dp, true));      // (no K split of the few-row products: an image's heads must not depend on N)
         *head = ptr<float>(headbuf); *ldh = 2 * Dp;
     } else {
         const int Nbp = round_up(N, 128);
@@ -3138,9 +3136,9 @@ int iwae_grid_posterior(iwae_handle m, const float* x, int32_t N, const float* z
         if (log_wq) HIPCHK(hipMemcpyAsync(w.lw.p, log_wq + c0, (size_t)Gc * 4, hipMemcpyDefault, st));
         // decoder logits l_g (src/iwae1.py:72-75), as iwae_decode / forward_f32 compute them
         if (f32) {
-            CHK(f32_fwd(m, d1[0], ptr<float>(w.z), D, Gc, ptr<float>(w.h1), H, GEMM_EPI_TANH));
-            CHK(f32_fwd(m, d1[1], ptr<float>(w.h1), H, Gc, ptr<float>(w.h2), H, GEMM_EPI_TANH));
-            CHK(f32_fwd(m, d1[2], ptr<float>(w.h2), H, Gc, ptr<float>(w.logits), Xp, GEMM_EPI_NONE));
+            CHK(f32_fwd(m, d1[0], ptr<float>(w.z), D, Gc, ptr<float>(w.h1), H, GEMM_EPI_TANH, false));
+            CHK(f32_fwd(m, d1[1], ptr<float>(w.h1), H, Gc, ptr<float>(w.h2), H, GEMM_EPI_TANH, false));
+            CHK(f32_fwd(m, d1[2], ptr<float>(w.h2), H, Gc, ptr<float>(w.logits), Xp, GEMM_EPI_NONE, false));
         } else {
             launch_prep_rows(ptr<float>(w.z), nullptr, Gc, D, 0, Dp, Gcp, ptr<uint16_t>(w.zP), st);
             CHK(dense_fwd(m, m->dec1[0], EPI_TANH, ptr<uint16_t>(w.zP), Gc, ptr<uint16_t>(w.h1), nullptr, 0));
@@ -3242,19 +3240,16 @@ int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, co
             }
         }
         const uint32_t step = m->noise_step;
-        m->in_eval_llh = true;      // (float32: no K split of few-row products)
-        int rc = IWAE_OK;
-        for (int i0 = 0; i0 < N && rc == IWAE_OK; i0 += nbmax) {
+        for (int i0 = 0; i0 < N; i0 += nbmax) {
             const int nb = std::min(nbmax, (int)N - i0);
-            for (int s0 = 0; s0 < k && rc == IWAE_OK; s0 += kc) {
+            for (int s0 = 0; s0 < k; s0 += kc) {
                 const int kn = std::min(kc, (int)k - s0), M = nb * kn, Mp = round_up(M, 128);
                 EpsSrc e;
                 e.seed = m->cfg.seed; e.step = step; e.stream = 0;
                 e.row_offset = (uint64_t)(m->batch_offset + (uint32_t)i0) * (uint64_t)k;     // iwae_eval_llh's Philox rows: (offset + i) k + s
                 e.k_total = k; e.s_off = s0; e.kc = kn;
                 if (eps) {      // the caller's [k][N][D0] draws of this chunk -> [kn][nb][D0]
-                    if (hipMemcpy2DAsync(w.eps.p, (size_t)nb * D0 * 4, eps + ((size_t)s0 * N + i0) * D0, (size_t)N * D0 * 4, (size_t)nb * D0 * 4, kn,
-                                         hipMemcpyDefault, st) != hipSuccess) { rc = fail(IWAE_ERR_HIP, "latent_activity: copying eps failed"); break; }
+                    HIPCHK(hipMemcpy2DAsync(w.eps.p, (size_t)nb * D0 * 4, eps + ((size_t)s0 * N + i0) * D0, (size_t)N * D0 * 4, (size_t)nb * D0 * 4, kn, hipMemcpyDefault, st));
                     e.user = ptr<float>(w.eps);
                 }
                 e.B = nb;
@@ -3279,14 +3274,15 @@ int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, co
                         launch_sample(sm, st);
                         const KerasLayer* l1 = &m->klayers[e2[0].sub[0]];
                         const int H = l1->Nout;
-                        if ((rc = f32_fwd(m, l1[0], ptr<float>(w.z), D0, M, ptr<float>(w.f32.h1), H, GEMM_EPI_TANH)) != IWAE_OK) break;
-                        if ((rc = f32_fwd(m, l1[1], ptr<float>(w.f32.h1), H, M, ptr<float>(w.f32.h2), H, GEMM_EPI_TANH)) != IWAE_OK) break;
-                        if ((rc = f32_fwd(m, l1[2], ptr<float>(w.f32.h2), H, M, ptr<float>(w.blk.head), D1, GEMM_EPI_NONE)) != IWAE_OK) break;
+                        // (no K split of few-row products: an image's mu2 must not depend on how many share the launch)
+                        CHK(f32_fwd(m, l1[0], ptr<float>(w.z), D0, M, ptr<float>(w.f32.h1), H, GEMM_EPI_TANH, true));
+                        CHK(f32_fwd(m, l1[1], ptr<float>(w.f32.h1), H, M, ptr<float>(w.f32.h2), H, GEMM_EPI_TANH, true));
+                        CHK(f32_fwd(m, l1[2], ptr<float>(w.f32.h2), H, M, ptr<float>(w.blk.head), D1, GEMM_EPI_NONE, true));
                         mu2 = ptr<float>(w.blk.head); ldm = D1;
                     } else {
                         sm.ZP = ptr<uint16_t>(w.z);
                         launch_sample(sm, st);
-                        if ((rc = block_fwd(m, m->enc2, w.blk, ptr<uint16_t>(w.z), M)) != IWAE_OK) break;
+                        CHK(block_fwd(m, m->enc2, w.blk, ptr<uint16_t>(w.z), M));
                         mu2 = ptr<float>(w.blk.head); ldm = e2[2].Np32;
                     }
                     ActPartialArgs pa;
@@ -3295,11 +3291,9 @@ int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, co
                     pa.part = ptr<float>(w.part); pa.nblk = nblk; pa.img0 = i0; pa.blk0 = s0 / ACT_BLOCK;
                     launch_act_partial(pa, st);
                 }
-                if (hipGetLastError() != hipSuccess) { rc = fail(IWAE_ERR_HIP, "latent_activity: a launch failed"); break; }
+                HIPCHK(hipGetLastError());
             }
         }
-        m->in_eval_llh = false;
-        if (rc != IWAE_OK) { (void)hipStreamSynchronize(st); return rc; }
         sa.src = ptr<float>(w.part); sa.ld_img = (long)nblk * D1; sa.ld_blk = D1; sa.nblk = nblk; sa.kdiv = (double)k; sa.D = D1; sa.col = D0;
         launch_act_stats(sa, st);
         HIPCHK(hipGetLastError());
@@ -3334,10 +3328,10 @@ int iwae_grad_moments(iwae_handle m, const float* x, int32_t B, int32_t k, float
     CHK(ensure(w.m2, n * 8, st));
     for (int j = 0; j < M; ++j) {
         if (f32) {
-            CHK(forward_f32(m, xd, B, k, beta, nullptr, objective, true, nullptr));
+            CHK(forward_f32(m, xd, B, k, beta, nullptr, objective, true, nullptr, FwdCall{m->batch_offset}));
             CHK(backward_f32(m, objective));
         } else {
-            CHK(forward_impl(m, xd, B, k, beta, nullptr, objective, true, nullptr));
+            CHK(forward_impl(m, xd, B, k, beta, nullptr, objective, true, nullptr, FwdCall{m->batch_offset}));
             CHK(backward_impl(m, objective));
         }
         m->noise_step += 1;
@@ -3537,7 +3531,7 @@ int iwae_debug_tensor(iwae_handle m, const char* name, float* out, size_t cap, i
         if (rows) *rows = m->dstamp_waves;
         if (cols) *cols = 8;
         if (!out) return IWAE_OK;
-        if (!m->dstamps.p) return fail(IWAE_ERR_STATE, "dense stamps not enabled (STAMPS=1 build + IWAE_DENSE_STAMPS=epi:KT)");
+        if (!m->dstamps.p) return fail(IWAE_ERR_STATE, "dense stamps not enabled (STAMPS=1 build + options dense_stamps_epi / dense_stamps_kt)");
         std::vector<unsigned long long> h((size_t)m->dstamp_waves * 8);
         HIPCHK(hipStreamSynchronize(m->stream));
         HIPCHK(hipMemcpy(h.data(), m->dstamps.p, h.size() * 8, hipMemcpyDeviceToHost));
@@ -3549,7 +3543,7 @@ int iwae_debug_tensor(iwae_handle m, const char* name, float* out, size_t cap, i
         if (rows) *rows = nw;
         if (cols) *cols = 8;
         if (!out) return IWAE_OK;
-        if (!m->stamps.p) return fail(IWAE_ERR_STATE, "stamps not enabled (IWAE_STAMPS=1)");
+        if (!m->stamps.p) return fail(IWAE_ERR_STATE, "stamps not enabled (DIAG=1 build + option stamps)");
         std::vector<unsigned long long> h((size_t)nw * 8);
         HIPCHK(hipStreamSynchronize(m->stream));
         HIPCHK(hipMemcpy(h.data(), m->stamps.p, h.size() * 8, hipMemcpyDeviceToHost));

@@ -1235,7 +1235,7 @@ def test_float32_gemm_kernel_variants_agree(gpu, layers, B, k):
     """Round 5: the float32 GEMMs' k loop was rewritten (gemm_f32_v2_kernel: 16-byte conflict-free LDS stores and reads with lane quad q contracting
     k = 4q + j, transposed 16-byte epilogues, 8-wave 128 x 224 / 224 x 128 tiles, the v2 loop on 64 x 64 tiles, K-split few-row products with the
     epilogue in the reduction).  Every variant against the exact float64 oracle at the float32 tolerances, and against each other to 1e-5 -- they
-    differ in the ORDER of float32 sums only.  (The switches are process-wide: each is put back.)"""
+    differ in the ORDER of float32 sums only."""
     from iwae_amd.native import NativeModel
     nh, nl = (200, 100) if layers == 1 else ([200, 100], [100, 50])
     x, P, eps = MG.inputs(layers, nh, nl, 784, B, k, 880 + B + k)
@@ -1254,11 +1254,74 @@ def test_float32_gemm_kernel_variants_agree(gpu, layers, B, k):
             assert max(_grad_rel_errors(flat, g)) < F32_GRAD_REL, name
             grads[name] = flat.astype(np.float64)
         finally:
-            if name:
-                m.set_option(name, 0)
             m.close()
     for name, gv in grads.items():
         assert np.linalg.norm(gv - grads[None]) / np.linalg.norm(grads[None]) < 1e-5, name
+
+
+def test_float32_gemm_options_do_not_leak_between_handles(gpu):
+    """One handle = one GPU context of its own: a float32 GEMM switch set on handle B -- and never put back -- must not
+    change which kernels handle A launches.  The variants differ in the order of float32 sums at these shapes (which is why the test above
+    allows 1e-5 between them), so A's step after each switch on B is compared BITWISE with A's first step.  (With process-wide switches three of
+    the four changed A's gradient at this shape; f32_gemm_w4 selects no other kernel here and stays in the loop all the same.)"""
+    from iwae_amd.native import NativeModel
+    B, k = 100, 50
+    x, P, eps = MG.inputs(1, 200, 100, 784, B, k, 880 + B + k)
+
+    def step(m):
+        r = m.forward_backward(x, k, 1.0, "iwae_elbo", eps=eps)
+        return r, m.get_grads().copy()
+
+    ma = NativeModel(1, 200, 100, seed=123, precision="fp32")
+    mb = NativeModel(1, 200, 100, seed=123, precision="fp32")
+    try:
+        ma.set_params(O.flatten_params(P))
+        mb.set_params(O.flatten_params(P))
+        r0, g0 = step(ma)
+        for name in ("f32_gemm_v1", "f32_gemm_w4", "f32_gemm_small_v1", "f32_no_ksplit"):
+            mb.set_option(name, 1)
+            step(mb)
+            r1, g1 = step(ma)
+            np.testing.assert_array_equal(list(r1.values()), list(r0.values()), err_msg=name)
+            np.testing.assert_array_equal(g1, g0, err_msg=name)
+    finally:
+        ma.close()
+        mb.close()
+
+
+def test_evaluator_error_leaves_the_handle_usable(gpu):
+    """iwae_eval_llh tells its forward passes what it needs (log_w only, k-chunk keys, the condition rows of its chunk) per call.  When one of
+    them is refused -- here the condition covers 8 of the evaluator's 16 images: IWAE_ERR_STATE, nothing reaches the GPU -- none of that may
+    stay behind on the handle: the same forward before and after returns the same bits, with default outputs (where the evaluator's launches
+    skip the per-row outputs and the DReG density) and with per-row tensors."""
+    from iwae_amd.native import NativeModel
+    C, k = 10, 5
+    rng = np.random.default_rng(41)
+    x = O.synthetic_binarized(16, 31)
+    y = np.eye(C, dtype=np.float32)[rng.integers(0, C, 8)]
+    P = O.init_params(1, 200, 100, 17, x_mean=O.synthetic_pixel_means(), cond_dim=C)
+    m = NativeModel(1, 200, 100, seed=123, cond_dim=C)
+    try:
+        m.set_params(O.flatten_params(P))
+        m.set_condition(y)
+
+        def calls():
+            m.set_step(3, 0)
+            a = m.forward(x[:8], k)
+            m.set_step(3, 0)
+            return a, m.forward(x[:8], k, want=("log_w", "lpxz", "lpz", "lqzx", "z"))
+
+        before = calls()
+        for chunk in (0, 4):      # refused at the first launch / at the third, behind two that ran
+            with pytest.raises(RuntimeError, match="error -4: conditional model"):      # IWAE_ERR_STATE
+                m.eval_llh(x, k=64, chunk=chunk)
+            after = calls()
+            for a, b in zip(before, after):
+                assert a.keys() == b.keys()
+                for key in a:
+                    np.testing.assert_array_equal(np.asarray(a[key]), np.asarray(b[key]), err_msg="%s (chunk %d)" % (key, chunk))
+    finally:
+        m.close()
 
 
 @pytest.mark.parametrize("layers,B,k", [(1, 100, 50), (2, 96, 50), (1, 20, 5)])
