@@ -159,6 +159,7 @@ struct BlockBwdArgs {                 // block_bwd_kernel: the dX chain of a Bas
 bool block_bwd_ok(const BlockBwdArgs& a);
 void launch_block_bwd(const BlockBwdArgs& a, hipStream_t st);
 bool block_fwd_ok(const BlockFwdArgs& a);
+bool block_fwd_shape_ok(const BlockFwdArgs& a);      // block_fwd_ok's shape part: reads no buffer pointer
 void launch_block_fwd(const BlockFwdArgs& a, hipStream_t st);
 
 struct OutBwdArgs {

@@ -4752,9 +4752,16 @@ static bool launch_dense_g1(int epi, const DenseArgs& a, dim3 grid, size_t lds, 
     if (a.KT == 4 && epi == EPI_TANH) { LAUNCH_EV((dense_kernel<EPI_TANH, 4, 1>), grid, dim3(512), lds, st, a); return true; }
     return false;
 }
+// the launch's guard: the shapes block_fwd_kernel covers, with the buffers its sampling prologue / output layer need in place
 bool block_fwd_ok(const BlockFwdArgs& a) {
-    if (a.sample && (a.S.Dp != 32 * a.KT0 || a.KT0 > 15 || !a.S.ZP || a.S.ZF || a.S.M != a.R)) return false;
-    if (a.oimg && (a.NT2 != 0 || a.oH < 1 || !a.oXB || !a.olpxz || a.ok < 1)) return false;
+    if (a.sample && !a.S.ZP) return false;
+    if (a.oimg && (!a.oXB || !a.olpxz)) return false;
+    return block_fwd_shape_ok(a);
+}
+// ... the shapes alone (the host plans a step with it before any buffer exists)
+bool block_fwd_shape_ok(const BlockFwdArgs& a) {
+    if (a.sample && (a.S.Dp != 32 * a.KT0 || a.KT0 > 15 || a.S.ZF || a.S.M != a.R)) return false;
+    if (a.oimg && (a.NT2 != 0 || a.oH < 1 || a.ok < 1)) return false;
     return a.R <= 4096 && a.KT1 <= BLOCKFWD_MAX_KT && a.NT1 <= 16 && a.NT2 <= 16 && a.NT1 == 2 * a.KT1 &&
            (size_t)(a.KT0 + 2 * a.KT1) * 1024 <= 150 * 1024;
 }

@@ -127,6 +127,129 @@ struct FwdCall {
     bool no_ksplit = false;           // float32: no K split of few-row products (an image's result must not depend on how many images share the launch)
 };
 
+// Every switch and tuning value iwae_set_option writes (defaults: the measured best).  plan_step reads the switches that choose kernels and streams; the
+// launch code reads only the values that size a launch already chosen (wg_target*, wout_wg*, eps_blocks, dense_g1_mask, dec_bwd_nw).
+struct StepOptions {
+    bool allow_s_mode = true;   // option out_recompute switches back to recomputing the logits in out_bwd (A/B measurements)
+    bool allow_zin = true;      // option no_zin: always the separate sampling kernel (A/B measurements)
+    bool allow_zin_eval = false; // option zin_eval (round 4, measured and NOT the default): forward-only calls on many rows take their draws from eps_gen_kernel and let the decoder
+                                 // kernel make z in its prologue instead of sample_kernel (inline Philox) in front of it -- bf16 evaluator 146 k vs 158 k images/s: the prologue's 20 MB of
+                                 // float32 draws cost the vector-issue-bound kernel more than the separate pass
+    bool allow_eps_multi = true;   // option no_eps_multi: one draw launch per step there too
+    int eps_blocks = 512;      // blocks of the ahead-of-time noise draw (option eps_blocks; 0 = one block per 256 threads of work)
+    bool allow_block_fused = true;   // option no_block_fused: a BasicBlock on few rows stays three dense_kernel launches (A/B measurements)
+    bool allow_out_in_block = true;  // option no_out_in_block: the output layer of a few-row decoder stays a dense_kernel<EPI_BERN> launch (A/B measurements)
+    bool allow_dec_fused = true;     // option no_dec_fused: the two tanh layers of the decoder stay dense_kernel launches (A/B measurements)
+    bool allow_bern_pipe = true;   // option no_bern_pipe: the Bernoulli forward stays on dense_kernel<EPI_BERN> (A/B measurements)
+    bool bern_qw = true;             // option no_bern_qw: the decoder kernel's 8-wave / 128-row shape instead of 16 waves / 200 rows (A/B measurements)
+    bool bern_qw_force = false;      // option bern_qw_force: that shape at every row count it exists for (tests)
+    bool allow_lse_fused = true;  // the decoder kernel does lse_kernel's work for its rows (option no_lse_fused)
+    bool allow_lse_dup = true;      // option no_lse_dup: one lse_kernel, the side stream forks behind it (A/B measurements)
+    bool allow_lse_in_bwd = true;      // few rows: this step's lse_kernel work is left to dec_bwd_rows_kernel (option no_lse_in_bwd)
+    bool allow_early_wout = true;    // option no_early_wout: the output layer's weight gradient forks behind out_bwd with the others (A/B measurements)
+    // Option g2w (round 4, measured and NOT the default): the decoder kernel leaves g2w = bf16(g_r g2) and the output layer's weight gradient runs
+    // unweighted on it (no 870 cycles of row weighting per loader stage).  That kernel got faster (107 -> 97 us in the step) and the step SLOWER
+    // (0.2044 -> 0.2154 ms, interleaved A/B): the decoder kernel pays 4 us for 23 MB more writes and the backward phase is bound by its bytes, not
+    // by that kernel's instruction stream (DESIGN.md section 3, round 4).
+    bool allow_g2w = false;
+    bool allow_chain2 = true;   // option no_chain2: the 2-layer model's per-sample blocks as dense_kernel launches + sample_kernel + gauss_lp_kernel (A/B measurements, variant tests)
+    bool allow_chain2_bwd = true;      // option no_chain2_bwd: the per-sample blocks' backward as gauss_bwd_kernel + dense_kernel launches
+    unsigned dense_g1_mask = IWAE_DENSE_G1_DEFAULT;   // option dense_g1 = <mask> (tuning aid, kernels.h)
+    bool allow_dec_bwd = true;  // option no_dec_bwd: out_bwd_s + the two dX kernels stay three launches (A/B measurements)
+    bool small_dec_bwd = true; int small_rows = 8191;   // the one-launch dX chain also below 8 192 rows (option no_small_dec_bwd: the per-pixel-group out_bwd + finish + two dX launches
+                                                        // there).  Measured: B=20,k=1 0.1417 -> 0.1383 ms/step, B=100,k=5 150.7 -> 144.6 us, B=160,k=50 189.1 -> 165.7 us
+    int dec_rows_max = 1024;    // dec_bwd_rows_kernel up to this many rows (option dec_rows), dec_bwd_kernel beyond
+    int dec_bwd_nw = 8;         // option dec_bwd_nw: dec_bwd_kernel's shape (8 waves x 16 rows, round 4 | 4 waves x 32 rows)
+    bool allow_dz_half = true;  // option dz_f32: dec_bwd_kernel leaves dz as float32 (A/B measurements)
+    bool allow_wg3 = true;                           // few rows: the decoder's three weight gradients as one grouped launch (option no_wg3)
+    bool allow_dec_rows = true;                      // ... and, with <= 2 048 DATA rows, the decoder's in the same launch (dec_rows_step; option no_dec_rows)
+    bool allow_wgrad_rows = true;                    // few rows (<= 2 048): the image encoder's weight gradients + Adam in ONE launch, whole row reduction per workgroup (wgrad_rows_kernel; option no_wgrad_rows)
+    bool allow_lat_rows4 = false;                    // option lat_rows4 (round 5, measured and NOT the default): beyond 16 samples per image the sums inside block_bwd_kernel<4> (4 images per
+                                                     // workgroup, an image's samples over four waves, 256 workgroups).  In the step it takes 32.6 us where latent_bwd_kernel + block_bwd_kernel
+                                                     // take 18.7 + 10.1: its 1024-thread / 101-register workgroups need a whole CU each and only ~96 CUs are free beside the weight
+                                                     // gradients (three rounds), where latent_bwd_kernel's small workgroups fit anywhere: c1 0.1965 vs 0.1962 ms, c2 0.3856 vs 0.3802
+    bool allow_lat_in_block = true;                  // few images: latent_bwd_kernel's sums inside the encoder's block_bwd_kernel (option no_lat_in_block)
+    bool use_side2 = true;             // option no_side2: the hidden layers' weight gradients behind the output layer's on `side`, not beside it on `side2`
+    bool allow_wg_group = false;       // option wg_group: the hidden layers' gradients as ONE grouped launch (measured: 0.2450 vs 0.2384 ms/step as two launches --
+                                       // both at once take more of the machine from the output layer's gradient, which is what the step waits for)
+    int wout_split = 0, wout_wg1 = 56, wout_wg2 = 128;      // option wout_split (percent of the rows, 0 = off; round 5): the output layer's weight gradient as an EARLY launch on few
+                                // workgroups beside dec_bwd_kernel (rows [0, R1)) and a LATE one behind it (the rest, beside the hidden layers' gradients)
+    bool defer_split = false;   // option defer_split (round 5): 1-layer step, each side stream sums + updates the decoder layers whose gradients IT carried
+    bool allow_defer = true;    // option no_defer: always join at the end of the step (A/B measurements)
+    bool allow_defer2 = true;   // option no_defer2
+    bool allow_defer2_split = true;      // ... one deferred update per side stream (option no_defer2_split: one, on `tail`)
+    int wg_target16 = 0;       // workgroups aimed at per 16-wave weight-gradient launch (option wg16; 0 = the model's default: 96 for the 1-layer model, 64 (round 5; 128 before) for
+                               // the 2-layer one -- round 3, with the output layer's gradient starting right behind the decoder kernel: 80 / 88 / 96 / 104 / 112 / 128
+                               // -> 0.2192 / 0.2168 / 0.2132 / 0.2164 / 0.2206 / 0.2175 ms, 24 row splits write 17 MB of slabs instead of 22.5; the 2-layer
+                               // step: 0.3932 vs 0.3916): these are one-per-CU
+                               // workgroups (128 KB of LDS); 256 of them lock every CU against the kernels running beside them on the main
+                               // stream (256 -> 0.294, 192 -> 0.280, 160 -> 0.279 ms/step while the gradient forked behind out_bwd; forked
+                               // behind lse_kernel, beside out_bwd: 96 -> 0.268, 112 -> 0.262, 128 -> 0.258, 144 -> 0.261, 160 -> 0.265)
+    int wg_target16_1 = 64;    // same, for layers that are a single block wide (option wg16_1): the hidden layers' gradients -- with the specialised-wave kernel 64 row splits (12.8 MB of slabs each) beat 128 (0.259 -> 0.249-0.254 ms/step); 48 and 32 are slower again
+    int wg_target8 = 128;      // same for the 8-wave launches on many rows (narrow layers of the 2-layer model; option wg8): 128 row splits halve the 109 MB of fp32 slabs 256 wrote per step (c2: 0.4193 -> 0.4176 ms; 64: 0.462)
+    int wg_target8_few = 32;   // 8-wave launches on < 8 192 rows (the encoder's layers on the batch's images; option wg8_few): the 784-wide first layer in 4 row
+                               // splits instead of 16 (10.6 -> 2.7 MB of slabs each way): 0.2439 -> 0.2351 ms/step at B = 1 024; 8 / 16 / 48: 0.2374 / 0.2374 / 0.2360
+    int wg_shape9 = 0;          // option wg9 (bit mask, see wgradp_plan): layers that take the 8 + 8-wave / 128-feature shape of wgradws_kernel
+    bool allow_wg7 = true;      // option no_wg7: the 16-wave weight-gradient shapes also where the 8-wave 7 x 4 shape exists (A/B measurements)
+    bool dp_concurrent = false;        // option dp_concurrent: the two all-reduces of a step may run at the same time (see dp_finish)
+    GemmF32Opts gemm_f32;                     // kernel choice of the float32 GEMM launchers (options f32_gemm_*, f32_no_ksplit, f32_ksplit_min_tiles)
+    bool allow_f32_multi_reduce = true;      // option no_f32_multi_reduce: a slab reduction launch per gradient tensor instead of one per step
+    bool allow_f32_side = true, f32_wout_first = true;      // float32 step: the decoder's weight gradients + update on the side stream (options no_f32_side, f32_wout_first)
+    int f32_dw_last = 0;        // option f32_dw_last: all decoder weight gradients behind the dX chain (1: tiles as picked, 2: 4-wave tiles, 3: ... at 3 waves per SIMD)
+    int f32_dw_min_rows = 32;   // float32 weight gradients: a row split covers at least this many rows (option f32_dw_min_rows; 64 until round 5)
+    int f32_dw_tiles = 1024;    // float32 weight gradients: workgroups aimed at per launch (row splits = this / output tiles; option f32_dw_tiles)
+    bool f32_dec_fused_train = false;
+    bool allow_f32_dec_fused = true;                           // float32 mode: the decoder forward as one launch (dec_fwd_f32_kernel; option no_f32_dec_fused)
+    bool allow_f32_bern_fused = true;      // float32 mode: log p(x|z) (and, in a training step, s) in the output layer's GEMM epilogue (option no_f32_bern_fused)
+    int eval_rows = 0;                        // data rows per evaluator launch (option eval_rows): images x samples, k chunked beyond it; 0 = eval_rows_auto()
+    int grid_chunk = 0;                       // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT)
+};
+
+// The kernels and streams of one bf16 step.  plan_step decides all of it from shapes and options before forward_impl launches or allocates
+// anything; forward_impl, backward_impl and the entry points behind them read it and decide nothing themselves, so the forward pass never
+// predicts what the backward pass will do -- both follow the same plan.  Every bf16 forward, a forward-only one too, writes m->plan anew: the
+// backward half is valid only from a training forward to the entry points of that same step (backward_impl, dp_finish, the split step's halves).
+enum ZFrom { Z_SAMPLE = 0, Z_DENSE_ZIN, Z_DEC_PROLOGUE, Z_BLOCK, Z_CHAIN2 };      // who makes z (z1): sample_kernel | dense_kernel's sampled-input mode | the decoder kernel's prologue | block_fwd_kernel | chain2_fwd_kernel
+enum DecFwd { DEC_DENSE = 0, DEC_BLOCK2, DEC_BLOCK_OUT, DEC_PIPE };              // the decoder's tanh layers: dense_kernel launches | block_fwd_kernel | block_fwd_kernel with the output layer | inside the one-launch bern_pipe_kernel
+enum LseAt { LSE_FWD = 0, LSE_DECODER, LSE_BWD_ROWS };                           // the log-mean-exp: lse_kernel in the forward pass | the decoder kernel | dec_bwd_rows_kernel
+enum DxPath { DX_THREE = 0, DX_DEC_BWD, DX_ROWS };                               // the decoder's dX chain: out_bwd + two dense launches | dec_bwd_kernel | dec_bwd_rows_kernel
+enum OnStream { ON_MAIN = 0, ON_SIDE, ON_SIDE2 };
+struct StepPlan {
+    // ---- forward
+    bool zin_eval = false;      // forward-only call whose decoder kernel makes z from eps_gen_kernel's draws (option zin_eval)
+    bool keep_eps = false;      // the draws come from eps_gen_kernel's buffers (later kernels of the call read them again)
+    bool eps_multi = false;     // ... from the multi-step buffers (few data rows, single-stream backward)
+    bool enc_takes_f32 = false; // the encoder's block_fwd_kernel converts float32 input rows itself (else prep_rows runs first)
+    ZFrom z_from = Z_SAMPLE;
+    bool chain = false;         // 2-layer model: both per-sample blocks in chain2_fwd_kernel
+    bool chain2_bwd = false;    // ... and their backward as gblock_bwd_kernel
+    DecFwd dec_fwd = DEC_DENSE;
+    DenseArgs bern;             // shape half of the output layer's / decoder kernel's argument block (pipe: bern_pipe's shape 1 or 2); forward_impl adds the buffers
+    BlockFwdArgs dec_blk;       // ... of block_fwd_kernel on the decoder (DEC_BLOCK2, DEC_BLOCK_OUT)
+    int px_parts = 1;           // > 1: log p(x|z) of this forward arrives in px_part as that many partial sums per row
+    bool s_mode = false;        // the forward keeps s = x - sigmoid(l) in wdec1.dlP
+    bool early_wout = false;    // the output layer's weight gradient forks behind the decoder forward / lse_kernel, not behind out_bwd
+    bool lse_fused = false;     // the decoder kernel does lse_kernel's work for its rows
+    bool lse_dup = false;       // a second lse_kernel on the side stream makes the output layer's row weights
+    bool g2w = false;           // the decoder kernel leaves g2w = bf16(g_r g2) (option g2w)
+    LseAt lse_at = LSE_FWD;
+    bool want_dreg = false;     // the call wants the second (DReG) log q per sample
+    OnStream draw_on = ON_SIDE; // the stream of the speculative draw of the next step's noise
+    // ---- backward (filled when the forward is a training step's)
+    bool dec_rows = false;      // the decoder's weight gradients ride in the encoder's wgrad_rows_kernel launch: no side-stream work at all
+    DxPath dx = DX_THREE;
+    DecBwdRowsArgs rows;        // shape half of dec_bwd_rows_kernel's argument block (DX_ROWS)
+    bool out_parts = false;     // DX_THREE: out_bwd_s_kernel per pixel group, partial sums + finish kernel
+    bool dz_half = false;       // the dX kernel leaves dz as bf16
+    bool lat_fuse = false;      // latent_bwd_kernel's sums inside the encoder's block_bwd_kernel
+    bool rows_enc = false;      // the encoder's weight gradients + update as wgrad_rows_kernel
+    bool group3 = false;        // the decoder's three weight gradients as one grouped launch on `side2`
+    bool wout_two_part = false; // the output layer's weight gradient as an early and a late launch (option wout_split)
+    bool hid_group = false;     // the hidden layers' weight gradients as one grouped launch (option wg_group)
+    OnStream hid_on = ON_SIDE;  // the stream of the hidden layers' weight gradients (the output layer's: `side`, or `side2` in group3)
+    OnStream tail = ON_SIDE;    // the side stream that finishes last (carries the decoder's reduction / exchange / update)
+};
+
 struct iwae_model {
     iwae_config cfg;
     int X, Xp32;
@@ -150,18 +273,14 @@ struct iwae_model {
     // float32 weight gradients of a step keep their row-split slabs (each in its own region of f32.slab) and are summed by ONE launch at the end of
     // backward_f32 (reduce_slabs_multi_f32_kernel): jobs queued by f32_dw, slab offsets in floats (the buffer may still grow while they queue)
     struct F32Pending { size_t off; size_t stride; size_t n; float* out; int nsplit; int seg; };
-    std::vector<F32Pending> f32_pending; size_t f32_slab_used = 0; bool allow_f32_multi_reduce = true;
-    bool allow_f32_side = true, f32_side_active = false, f32_wout_first = true;      // float32 step: the decoder's weight gradients + update on the side stream (options no_f32_side, f32_wout_first)
+    std::vector<F32Pending> f32_pending; size_t f32_slab_used = 0;
+    bool f32_side_active = false;      // float32 step: the decoder's weight gradients + update run on the side stream
     bool f32_z_pending = false;
-    int f32_dw_last = 0;
     bool bf16_side_used = false;      // a bf16 call may have left a speculative draw on a side stream (forward_f32 waits for it on the host)
     size_t f32_slab_want = 0, f32_slab_want_step = 0;      // floats of slabs the last whole step asked for (the buffer's target size) / this step so far
-    GemmF32Opts gemm_f32;                     // kernel choice of the float32 GEMM launchers (options f32_gemm_*, f32_no_ksplit, f32_ksplit_min_tiles)
     DevBuf eval_x, eval_lme;                  // iwae_eval_llh: the images (uploaded once) and the per-image log-mean-exps of every launch
-    int eval_rows = 0;                        // data rows per evaluator launch (option eval_rows): images x samples, k chunked beyond it; 0 = eval_rows_auto()
     int eval_precision = IWAE_PREC_FP32;      // arithmetic of iwae_eval_llh and iwae_grid_posterior (iwae_set_eval_precision)
-    // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT) and the call's buffers
-    int grid_chunk = 0;
+    // iwae_grid_posterior's buffers
     struct GridWs { DevBuf x, xb, xP, flag, head, z, lw, zP, h1, h2, logits, lhi, llo, c, zc, w, part, run, lpx, mean, cov, qmass, kl, lj; } grid;
     // iwae_latent_activity's buffers: the images, the chunk's draws, z1 rows and q(z2|z1) activations of the composed paths, the block partials
     // of mu2 [N][blocks][D2] and the outputs
@@ -180,45 +299,23 @@ struct iwae_model {
     LayerDesc* d_descs = nullptr;
     int elem_blocks = 0, reduce_blocks = 0;
     bool descs_dirty = true;
+    StepOptions opt;
+    StepPlan plan;             // the kernels and streams of the step in flight: written by plan_step (forward_impl), read by the backward pass and the entry points behind it
     // per-call state: written by begin_forward only (the backward pass and eps_src read the forward's copy)
     FwdCall call;
     int B = 0, k = 0, M = 0, Mp = 0, Bp = 0;
     float beta = 1.0f;
     bool have_forward = false, user_eps = false;
-    unsigned dense_g1_mask = IWAE_DENSE_G1_DEFAULT;   // option dense_g1 = <mask> (tuning aid, kernels.h)
-    bool allow_s_mode = true;   // option out_recompute switches back to recomputing the logits in out_bwd (A/B measurements)
     DevBuf dg2_part;            // small row counts: out_bwd_s_kernel's per-pixel-group partial sums
-    int px_parts = 1;           // > 1: log p(x|z) of this forward arrives in px_part as that many partial sums per row
     DevBuf px_part;
-    bool s_mode = false;        // this step's forward kept s = x - sigmoid(l) in wdec1.dlP
     DevBuf xin, xP, epsbuf, zP[2];
     DevBuf rows[6];            // lpxz, t1, t2, t3, t4, lq_dreg   (per data row)
     DevBuf logw, wn, gx, cf, per_b, dzdir;
     // lse_kernel's outputs once more, written by the copy of it that runs on the side stream (see forward_impl): the output layer's
     // weight gradient takes its row weights from there
     DevBuf logw2, wn2, gx2, cf2, per_b2;
-    int f32_dw_min_rows = 32;   // float32 weight gradients: a row split covers at least this many rows (option f32_dw_min_rows; 64 until round 5)
-    int f32_dw_tiles = 1024;    // float32 weight gradients: workgroups aimed at per launch (row splits = this / output tiles; option f32_dw_tiles)
-    bool f32_dec_fused_train = false;
-    bool allow_f32_dec_fused = true;                           // float32 mode: the decoder forward as one launch (dec_fwd_f32_kernel; option no_f32_dec_fused)
-    bool allow_f32_bern_fused = true, f32_keeps_s = false;      // float32 mode: log p(x|z) (and, in a training step, s) in the output layer's GEMM epilogue (option no_f32_bern_fused)
-    bool allow_wg3 = true;                           // few rows: the decoder's three weight gradients as one grouped launch (option no_wg3)
-    bool allow_dec_rows = true;                      // ... and, with <= 2 048 DATA rows, the decoder's in the same launch (dec_rows_step; option no_dec_rows)
-    bool allow_wgrad_rows = true;                    // few rows (<= 2 048): the image encoder's weight gradients + Adam in ONE launch, whole row reduction per workgroup (wgrad_rows_kernel; option no_wgrad_rows)
-    bool lse_fused = false, allow_lse_fused = true;  // the decoder kernel does lse_kernel's work for its rows (option no_lse_fused)
-    // Option g2w (round 4, measured and NOT the default): the decoder kernel leaves g2w = bf16(g_r g2) and the output layer's weight gradient runs
-    // unweighted on it (no 870 cycles of row weighting per loader stage).  That kernel got faster (107 -> 97 us in the step) and the step SLOWER
-    // (0.2044 -> 0.2154 ms, interleaved A/B): the decoder kernel pays 4 us for 23 MB more writes and the backward phase is bound by its bytes, not
-    // by that kernel's instruction stream (DESIGN.md section 3, round 4).
-    bool allow_g2w = false, g2w = false, g2w_descs = false;
-    bool allow_lat_rows4 = false;                    // option lat_rows4 (round 5, measured and NOT the default): beyond 16 samples per image the sums inside block_bwd_kernel<4> (4 images per
-                                                     // workgroup, an image's samples over four waves, 256 workgroups).  In the step it takes 32.6 us where latent_bwd_kernel + block_bwd_kernel
-                                                     // take 18.7 + 10.1: its 1024-thread / 101-register workgroups need a whole CU each and only ~96 CUs are free beside the weight
-                                                     // gradients (three rounds), where latent_bwd_kernel's small workgroups fit anywhere: c1 0.1965 vs 0.1962 ms, c2 0.3856 vs 0.3802
-    bool allow_lat_in_block = true;                  // few images: latent_bwd_kernel's sums inside the encoder's block_bwd_kernel (option no_lat_in_block)
-    bool lse_pending = false, allow_lse_in_bwd = true;      // few rows: this step's lse_kernel work was left to dec_bwd_rows_kernel (lse_saved; option no_lse_in_bwd)
-    LseArgs lse_saved;
-    bool lse_dup = false, allow_lse_dup = true;      // option no_lse_dup: one lse_kernel, the side stream forks behind it (A/B measurements)
+    bool f32_keeps_s = false;      // float32 step: the output layer's GEMM epilogue left s where the logits would have gone
+    bool g2w_descs = false;     // the layer table was built for a step with plan.g2w
     BlockWs wenc1, wenc2, wdec2, wprior;
     MlpWs wdec1;
     DevBuf scratch;            // exports
@@ -226,18 +323,6 @@ struct iwae_model {
     DevBuf ds_data, ds_order;
     DevBuf ds_labels; bool ds_has_labels = false;   // class id per image of the resident set (iwae_dataset_set_labels; conditional models)
     int ds_N = 0;
-    int wg_target16_1 = 64;    // same, for layers that are a single block wide (option wg16_1): the hidden layers' gradients -- with the specialised-wave kernel 64 row splits (12.8 MB of slabs each) beat 128 (0.259 -> 0.249-0.254 ms/step); 48 and 32 are slower again
-    int eps_blocks = 512;      // blocks of the ahead-of-time noise draw (option eps_blocks; 0 = one block per 256 threads of work)
-    int wg_target8 = 128;      // same for the 8-wave launches on many rows (narrow layers of the 2-layer model; option wg8): 128 row splits halve the 109 MB of fp32 slabs 256 wrote per step (c2: 0.4193 -> 0.4176 ms; 64: 0.462)
-    int wg_target8_few = 32;   // 8-wave launches on < 8 192 rows (the encoder's layers on the batch's images; option wg8_few): the 784-wide first layer in 4 row
-                               // splits instead of 16 (10.6 -> 2.7 MB of slabs each way): 0.2439 -> 0.2351 ms/step at B = 1 024; 8 / 16 / 48: 0.2374 / 0.2374 / 0.2360
-    int wg_target16 = 0;       // workgroups aimed at per 16-wave weight-gradient launch (option wg16; 0 = the model's default: 96 for the 1-layer model, 64 (round 5; 128 before) for
-                               // the 2-layer one -- round 3, with the output layer's gradient starting right behind the decoder kernel: 80 / 88 / 96 / 104 / 112 / 128
-                               // -> 0.2192 / 0.2168 / 0.2132 / 0.2164 / 0.2206 / 0.2175 ms, 24 row splits write 17 MB of slabs instead of 22.5; the 2-layer
-                               // step: 0.3932 vs 0.3916): these are one-per-CU
-                               // workgroups (128 KB of LDS); 256 of them lock every CU against the kernels running beside them on the main
-                               // stream (256 -> 0.294, 192 -> 0.280, 160 -> 0.279 ms/step while the gradient forked behind out_bwd; forked
-                               // behind lse_kernel, beside out_bwd: 96 -> 0.268, 112 -> 0.262, 128 -> 0.258, 144 -> 0.261, 160 -> 0.265)
     // N(0,1) draws of a step, fp32 [Mp][Dp] per latent layer, made by eps_gen_kernel and read by the sampling / decoder and
     // backward kernels.  A training step draws the NEXT step's noise during its forward pass on the side stream, idle then
     // (speculating step+1, same batch shape); it is ordered by the join the main stream performs anyway, and a forward
@@ -251,7 +336,6 @@ struct iwae_model {
     // (the next group is drawn during the forward pass of the current group's last step: the buffer it overwrites was last read a whole group ago, in stream order)
     DevBuf epsm[2][2];          // [buffer][layer]: [EPSM_STEPS][Mp][eps_ld]
     struct EpsMTag { bool valid = false; uint32_t step0 = 0; uint64_t row_offset = 0; int M = 0; } epsm_tag[2];
-    bool allow_eps_multi = true;   // option no_eps_multi: one draw launch per step there too
     const float* epsc_ptr[2] = {nullptr, nullptr};
     char* d_zero = nullptr;    // 1 KiB of zeros (wgradp_kernel's source for rows >= M)
     uint32_t ds_epoch = 0;
@@ -261,18 +345,11 @@ struct iwae_model {
     // optional HIP-event timing of the dominant kernels (iwae_enable_timing): pairs recorded on m->stream
     // fork/join of the decoder weight-gradient GEMMs (independent of the dz -> encoder chain) onto a side stream
     hipStream_t side = nullptr;
-    hipStream_t tail = nullptr;        // this step's side stream that finishes last (carries the decoder's reduction / exchange / update)
-    bool allow_wg_group = false;       // option wg_group: the hidden layers' gradients as ONE grouped launch (measured: 0.2450 vs 0.2384 ms/step as two launches --
-                                       // both at once take more of the machine from the output layer's gradient, which is what the step waits for)
     hipStream_t side2 = nullptr;       // the hidden layers' weight gradients beside the output layer's (option no_side2: behind it on `side`)
     hipEvent_t ev_s2 = nullptr;
     hipEvent_t ev_ar = nullptr;        // data-parallel step: recorded behind the encoder segment's all-reduce (dp_finish)
     bool early_held = false;           // in-library data-parallel step: backward_impl left the decoder's slab reduction to dp_finish
-    bool dp_concurrent = false;        // option dp_concurrent: the two all-reduces of a step may run at the same time (see dp_finish)
-    bool use_side2 = true;
-    int dec_bwd_nw = 8;         // option dec_bwd_nw: dec_bwd_kernel's shape (8 waves x 16 rows, round 4 | 4 waves x 32 rows)
     hipEvent_t ev_lse = nullptr;
-    bool early_wout = false, allow_early_wout = true;    // option no_early_wout: the output layer's weight gradient forks behind out_bwd with the others (A/B measurements)
     hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_blk = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_dec = nullptr;
     // Single-GPU train step: the decoder's slab reduction + Adam (90 % of the slab bytes) stays on the side stream and is
     // NOT joined at the end of the step -- nothing needs the decoder's new weights before the next step's d1 layer, so it
@@ -280,37 +357,13 @@ struct iwae_model {
     // join_side() does that, and every entry point that touches parameters, gradients or the decoder calls it.
     bool dec_pending = false;
     size_t split_offset = 0;    // iwae_forward_backward_split: first float of the flat gradient that was left on the side stream
-    int wg_shape9 = 0;          // option wg9 (bit mask, see wgradp_plan): layers that take the 8 + 8-wave / 128-feature shape of wgradws_kernel
     int fake_s = 0;             // DIAG builds: byte ablations of s (option fake_s)
     int abl_skip = 0;           // DIAG builds: launch ablations of the full-size step (option abl_skip; timing only, results wrong): 1 no output-layer weight gradient,
                                 // 2 no hidden-layer weight gradients, 4 no deferred decoder reduction + update, 8 no latent_bwd_kernel, 16 no noise draw ahead
     int wg_debug = 0;           // option wg_debug (DIAG builds): diagnostic ablations of wgradp_kernel (kernels.h)
-    bool allow_wg7 = true;      // option no_wg7: the 16-wave weight-gradient shapes also where the 8-wave 7 x 4 shape exists (A/B measurements)
-    int dec_rows_max = 1024;    // dec_bwd_rows_kernel up to this many rows (option dec_rows), dec_bwd_kernel beyond
-    bool small_dec_bwd = true; int small_rows = 8191;   // the one-launch dX chain also below 8 192 rows (option no_small_dec_bwd: the per-pixel-group out_bwd + finish + two dX launches
-                                                        // there).  Measured: B=20,k=1 0.1417 -> 0.1383 ms/step, B=100,k=5 150.7 -> 144.6 us, B=160,k=50 189.1 -> 165.7 us
-    bool allow_dz_half = true;  // option dz_f32: dec_bwd_kernel leaves dz as float32 (A/B measurements)
-    bool allow_chain2_bwd = true, chain2_bwd = false;      // option no_chain2_bwd: the per-sample blocks' backward as gauss_bwd_kernel + dense_kernel launches; chain2_bwd: this step takes gblock_bwd_kernel
-    bool allow_chain2 = true;   // option no_chain2: the 2-layer model's per-sample blocks as dense_kernel launches + sample_kernel + gauss_lp_kernel (A/B measurements, variant tests)
-    bool allow_dec_bwd = true;  // option no_dec_bwd: out_bwd_s + the two dX kernels stay three launches (A/B measurements)
-    bool allow_zin = true;      // option no_zin: always the separate sampling kernel (A/B measurements)
-    bool allow_zin_eval = false; // option zin_eval (round 4, measured and NOT the default): forward-only calls on many rows take their draws from eps_gen_kernel and let the decoder
-                                 // kernel make z in its prologue instead of sample_kernel (inline Philox) in front of it -- bf16 evaluator 146 k vs 158 k images/s: the prologue's 20 MB of
-                                 // float32 draws cost the vector-issue-bound kernel more than the separate pass
-    bool allow_out_in_block = true;  // option no_out_in_block: the output layer of a few-row decoder stays a dense_kernel<EPI_BERN> launch (A/B measurements)
-    bool allow_block_fused = true;   // option no_block_fused: a BasicBlock on few rows stays three dense_kernel launches (A/B measurements)
     int num_cus = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    bool bern_qw_force = false;      // option bern_qw_force: that shape at every row count it exists for (tests)
-    bool bern_qw = true;             // option no_bern_qw: the decoder kernel's 8-wave / 128-row shape instead of 16 waves / 200 rows (A/B measurements)
-    bool allow_dec_fused = true;     // option no_dec_fused: the two tanh layers of the decoder stay dense_kernel launches (A/B measurements)
-    bool allow_bern_pipe = true;   // option no_bern_pipe: the Bernoulli forward stays on dense_kernel<EPI_BERN> (A/B measurements)
-    bool allow_defer = true;    // option no_defer: always join at the end of the step (A/B measurements)
-    int wout_split = 0, wout_wg1 = 56, wout_wg2 = 128;      // option wout_split (percent of the rows, 0 = off; round 5): the output layer's weight gradient as an EARLY launch on few
-                                // workgroups beside dec_bwd_kernel (rows [0, R1)) and a LATE one behind it (the rest, beside the hidden layers' gradients)
-    bool defer_split = false;   // option defer_split (round 5): 1-layer step, each side stream sums + updates the decoder layers whose gradients IT carried
     int early_first2 = -1;      // 2-layer model: first reduce block behind the image encoder's layers (everything whose weight gradients run on the side streams)
-    bool allow_defer2 = true;   // option no_defer2
-    bool allow_defer2_split = true, dec2_pending = false;      // ... one deferred update per side stream (option no_defer2_split: one, on `tail`)
+    bool dec2_pending = false;
     hipEvent_t ev_dec2 = nullptr;
     int early_first = -1;       // first reduce block of the decoder's layers when they are the tail of the table, else -1
     int timing = 0;            // 0 off, n > 0: time every n-th forward (event records cost a few us of stream bubble each)
@@ -447,6 +500,14 @@ std::vector<Linear*> all_linears(iwae_model* m) {
     return v;
 }
 
+// table order enc1 | enc2 | dec2 | dec1 [| prior]: are the decoder's three layers (one table entry each) the tail of the table / does the
+// 2-layer model's share of it start with the per-sample encoder?  (build_descs turns these into early_first / early_first2)
+bool dec_layers_last(const iwae_model* m) {
+    const int d0 = m->dec1[0].sub[0];
+    return m->dec1[0].nsub == 1 && m->dec1[1].nsub == 1 && m->dec1[2].nsub == 1 && m->dec1[1].sub[0] == d0 + 1 && m->dec1[2].sub[0] == d0 + 2 && d0 + 3 == (int)m->klayers.size();
+}
+bool side_layers_from_enc2(const iwae_model* m) { return m->cfg.n_layers == 2 && m->enc2[0].nsub >= 1; }
+
 int build_descs(iwae_model* m) {
     m->descs.assign(m->klayers.size(), LayerDesc());
     for (Linear* L : all_linears(m)) {
@@ -460,7 +521,7 @@ int build_descs(iwae_model* m) {
             d.slabW = ptr<float>(L->slabW); d.slabB = ptr<float>(L->slabB);
             d.nsplit = L->nsplit; d.slab_ld = L->JT * 16; d.slab_stride = (size_t)L->IT * 16 * L->JT * 16;
             d.slabB_stride = 0;
-            if (m->g2w && L == &m->dec1[2]) {      // pre-weighted output layer: the bias gradient is product row H (the pad feature that carries g_r) of every slab
+            if (m->plan.g2w && L == &m->dec1[2]) {      // pre-weighted output layer: the bias gradient is product row H (the pad feature that carries g_r) of every slab
                 d.slabB = ptr<float>(L->slabW) + (size_t)kl.Kin * d.slab_ld;
                 d.slabB_stride = d.slab_stride;
             }
@@ -476,18 +537,15 @@ int build_descs(iwae_model* m) {
     m->elem_blocks = blocks;
     m->reduce_blocks = rblocks;
     m->early_first = -1;
-    m->early_first2 = (m->cfg.n_layers == 2 && m->enc2[0].nsub >= 1) ? m->descs[m->enc2[0].sub[0]].rblock_begin : -1;      // (table order: enc1, enc2, dec2, dec1)
-    const int d0 = m->dec1[0].sub[0];
-    if (m->dec1[0].nsub == 1 && m->dec1[1].nsub == 1 && m->dec1[2].nsub == 1 && m->dec1[1].sub[0] == d0 + 1 &&
-        m->dec1[2].sub[0] == d0 + 2 && d0 + 3 == (int)m->descs.size())
-        m->early_first = m->descs[d0].rblock_begin;
+    m->early_first2 = side_layers_from_enc2(m) ? m->descs[m->enc2[0].sub[0]].rblock_begin : -1;      // (table order: enc1, enc2, dec2, dec1)
+    if (dec_layers_last(m)) m->early_first = m->descs[m->dec1[0].sub[0]].rblock_begin;
     if (!m->d_descs) HIPCHK(hipMalloc((void**)&m->d_descs, sizeof(LayerDesc) * m->descs.size()));
     HIPCHK(hipMemcpyAsync(m->d_descs, m->descs.data(), sizeof(LayerDesc) * m->descs.size(), hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->side) HIPCHK(hipStreamSynchronize(m->side));      // a deferred decoder update may still be reading the old table
     if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
     m->descs_dirty = false;
-    m->g2w_descs = m->g2w;
+    m->g2w_descs = m->plan.g2w;
     return IWAE_OK;
 }
 
@@ -565,7 +623,7 @@ int dense_fwd(iwae_model* m, Linear& L, int epi, const uint16_t* XP, int rows, u
     memset(&a, 0, sizeof(a));
     a.X = XP; a.ldX = L.Kp32; a.img = L.imgF;
     a.split = (L.nsub == 2) ? L.joff[1] : (1 << 30);
-    a.M = rows; a.KT = L.KT; a.MG = L.MG; a.mg_per_block = (rows <= 8192) ? 1 : L.MG; a.Np32 = L.Np32; a.g1_mask = m->dense_g1_mask;
+    a.M = rows; a.KT = L.KT; a.MG = L.MG; a.mg_per_block = (rows <= 8192) ? 1 : L.MG; a.Np32 = L.Np32; a.g1_mask = m->opt.dense_g1_mask;
     a.stage_all = (a.mg_per_block == 1 && L.KT > 8 && (L.KT + 7) / 8 <= 4) ? 1 : 0;
     if (zin) {      // sampled-input mode: the layer makes its own input rows z = mu + sigma*eps (and keeps them in zin->ZP)
         a.zhead = zin->head; a.ldZH = zin->ldH; a.zeps = zin->eps.cache; a.zldE = zin->eps.ldC; a.zD = zin->D; a.zDp = zin->Dp;
@@ -594,25 +652,27 @@ int block_alloc(iwae_model* m, Linear* blk, BlockWs& w, int R, int Rp, bool bwd,
     return IWAE_OK;
 }
 
-// xf != null: the input rows are still fp32 [R][xdim]; the fused kernel converts them into XP itself (returns *took = true),
-// otherwise the caller runs prep_rows first
-int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R, const float* xf = nullptr, int xdim = 0, bool* took = nullptr) {
-    if (took) *took = false;
-    if (m->allow_block_fused) {       // few rows (the encoder on the batch's images): the whole block in one launch
-        BlockFwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.X = XP; a.ldX = blk[0].Kp32; a.img0 = blk[0].imgF; a.img1 = blk[1].imgF; a.img2 = blk[2].imgF;
-        a.KT0 = blk[0].KT; a.KT1 = blk[1].KT; a.NT1 = blk[0].Np32 / 16; a.NT2 = blk[2].Np32 / 16; a.R = R;
-        a.H1 = ptr<uint16_t>(w.h1P); a.H2 = ptr<uint16_t>(w.h2P); a.ldH = blk[0].Np32;
-        a.YF = ptr<float>(w.head); a.ldYF = blk[2].Np32; a.split = (blk[2].nsub == 2) ? blk[2].joff[1] : (1 << 30);
-        if (blk[1].Np32 == blk[0].Np32 && blk[2].KT == blk[1].KT && blk[1].Kp32 == blk[0].Np32 && block_fwd_ok(a)) {
-            if (xf && took) { a.Xf = xf; a.Xdim = xdim; a.XPout = const_cast<uint16_t*>(XP); *took = true; }
-            launch_block_fwd(a, m->stream);
-            HIPCHK(hipGetLastError());
-            return IWAE_OK;
-        }
+// Does block_fwd_kernel take the whole block on R rows (few rows: the encoder on the batch's images)?  Fills the shape half of its argument block.
+bool block_fwd_shape(const iwae_model* m, const Linear* blk, int R, BlockFwdArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.ldX = blk[0].Kp32; a.img0 = blk[0].imgF; a.img1 = blk[1].imgF; a.img2 = blk[2].imgF;
+    a.KT0 = blk[0].KT; a.KT1 = blk[1].KT; a.NT1 = blk[0].Np32 / 16; a.NT2 = blk[2].Np32 / 16; a.R = R;
+    a.ldH = blk[0].Np32; a.ldYF = blk[2].Np32; a.split = (blk[2].nsub == 2) ? blk[2].joff[1] : (1 << 30);
+    return m->opt.allow_block_fused && blk[1].Np32 == blk[0].Np32 && blk[2].KT == blk[1].KT && blk[1].Kp32 == blk[0].Np32 && block_fwd_ok(a);
+}
+
+// xf != null: the input rows are still fp32 [R][xdim] and the fused kernel converts them into XP itself -- only where block_fwd_shape says
+// that kernel runs (StepPlan::enc_takes_f32); elsewhere the caller runs prep_rows first
+int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R, const float* xf = nullptr, int xdim = 0) {
+    BlockFwdArgs a;
+    if (block_fwd_shape(m, blk, R, a)) {       // few rows: the whole block in one launch
+        a.X = XP; a.H1 = ptr<uint16_t>(w.h1P); a.H2 = ptr<uint16_t>(w.h2P); a.YF = ptr<float>(w.head);
+        if (xf) { a.Xf = xf; a.Xdim = xdim; a.XPout = const_cast<uint16_t*>(XP); }
+        launch_block_fwd(a, m->stream);
+        HIPCHK(hipGetLastError());
+        return IWAE_OK;
     }
-    if (xf) return IWAE_OK;      // not taken (*took = false): the caller converts the rows and calls again
+    if (xf) return fail(IWAE_ERR_STATE, "block_fwd: float32 input rows on a shape block_fwd_kernel does not cover");
     CHK(dense_fwd(m, blk[0], EPI_TANH, XP, R, ptr<uint16_t>(w.h1P), nullptr, 0));
     CHK(dense_fwd(m, blk[1], EPI_TANH, ptr<uint16_t>(w.h1P), R, ptr<uint16_t>(w.h2P), nullptr, 0));
     CHK(dense_fwd(m, blk[2], EPI_HEAD, ptr<uint16_t>(w.h2P), R, nullptr, ptr<float>(w.head), blk[2].Np32));
@@ -623,10 +683,11 @@ int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R,
 // weight gradient from the P-layout operands (wgradp_kernel); XP/GP row-major bf16, `rows` valid rows.
 // wgradp_plan sizes the row splits and the slabs and fills the argument block; nw = the kernel shape (launch_wgradp:
 // 8 = small, 16 = 16 waves, 7 = 8 waves with 7 x 4 accumulator tiles each, for inputs <= 224 features wide).
-int wgradp_plan(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP, int rows, WgradPArgs& a, int& nsplit, int& nw) {
+// the shape part: the kernel shape, the row splits and the 64-row chunks per split (no allocation: plan_step asks for the shape alone)
+void wgradp_shape(const iwae_model* m, const Linear& L, int rows, int& nsplit, int& nw, int& cps) {
     const int chunks = (rows + 63) / 64;
     nw = (L.JT > 8 && chunks >= 128) ? 16 : 8;
-    if (nw == 16 && L.IT <= 14 && m->allow_wg7) nw = (m->wg_shape9 & (L.JT > 16 ? 1 : 2)) ? 9 : 7;      // option wg9: bit 0 the output layer, bit 1 the hidden layers
+    if (nw == 16 && L.IT <= 14 && m->opt.allow_wg7) nw = (m->opt.wg_shape9 & (L.JT > 16 ? 1 : 2)) ? 9 : 7;      // option wg9: bit 0 the output layer, bit 1 the hidden layers
     const int blocks = ((L.JT + wgradp_strip(nw) - 1) / wgradp_strip(nw)) * ((L.IT + 15) / 16);
     // Workgroup targets (measured at k=50, B=1024).  Early builds, the weight gradients alone on the machine: 64 -> 0.501,
     // 128 -> 0.425, 256 -> 0.406, 384 -> 0.443 ms/step (fewer leaves CUs idle, more pays a full fp32 slab per extra split).
@@ -634,11 +695,15 @@ int wgradp_plan(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP
     // single-block-wide hidden layers prefer 128.
     // (round 5: the 2-layer step's MAIN stream is its long chain and its side streams have slack: 64 workgroups for the output layer's gradient leave the
     // main chain's kernels more CUs -- 128 / 96 / 72 / 64 / 56 / 48 -> 0.3915 / 0.3834 / 0.3896 / 0.3769 / 0.3805 / 0.3852 ms, interleaved)
-    const int target16 = m->wg_target16 > 0 ? m->wg_target16 : (m->cfg.n_layers == 2 ? 64 : 96);
-    const int target = (nw != 8) ? (blocks == 1 ? m->wg_target16_1 : target16) : (chunks < 128 ? m->wg_target8_few : m->wg_target8);
+    const int target16 = m->opt.wg_target16 > 0 ? m->opt.wg_target16 : (m->cfg.n_layers == 2 ? 64 : 96);
+    const int target = (nw != 8) ? (blocks == 1 ? m->opt.wg_target16_1 : target16) : (chunks < 128 ? m->opt.wg_target8_few : m->opt.wg_target8);
     nsplit = std::max(1, std::min(chunks, target / std::max(1, blocks)));
-    const int cps = (chunks + nsplit - 1) / nsplit;
+    cps = (chunks + nsplit - 1) / nsplit;
     nsplit = (chunks + cps - 1) / cps;
+}
+int wgradp_plan(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP, int rows, WgradPArgs& a, int& nsplit, int& nw) {
+    int cps;
+    wgradp_shape(m, L, rows, nsplit, nw, cps);
     const size_t needW = (size_t)nsplit * L.IT * 16 * L.JT * 16 * 4, needB = (size_t)nsplit * L.JT * 16 * 4;
     void* oldW = L.slabW.p; void* oldB = L.slabB.p;
     CHK(ensure(L.slabW, needW, m->stream));
@@ -676,12 +741,12 @@ int wgradp(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP, int
 int wgradp_two_plan(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP, int rows, const float* rowscale, WgradPArgs& a1, int& n1, WgradPArgs& a2, int& n2) {
     const int blocks = (L.JT + 15) / 16;
     const int chunks = (rows + 63) / 64;
-    const int c1 = std::min(chunks - 1, std::max(1, (int)((long)chunks * m->wout_split / 100)));
+    const int c1 = std::min(chunks - 1, std::max(1, (int)((long)chunks * m->opt.wout_split / 100)));
     const int c2 = chunks - c1;
     auto split = [&](int ch, int target, int& n, int& cps) { n = std::max(1, std::min(ch, target / std::max(1, blocks))); cps = (ch + n - 1) / n; n = (ch + cps - 1) / cps; };
     int cps1, cps2;
-    split(c1, m->wout_wg1, n1, cps1);
-    split(c2, m->wout_wg2, n2, cps2);
+    split(c1, m->opt.wout_wg1, n1, cps1);
+    split(c2, m->opt.wout_wg2, n2, cps2);
     const int ns = n1 + n2;
     const size_t stride = (size_t)L.IT * 16 * L.JT * 16;
     void* oldW = L.slabW.p; void* oldB = L.slabB.p;
@@ -703,7 +768,7 @@ int dense_dx(iwae_model* m, Linear& L, const uint16_t* GP, int rows, const uint1
     memset(&a, 0, sizeof(a));
     a.X = GP; a.ldX = L.Np32; a.img = L.imgB;
     a.split = 1 << 30;
-    a.M = rows; a.KT = L.KT_B; a.MG = L.MG_B; a.mg_per_block = (rows <= 8192) ? 1 : L.MG_B; a.Np32 = L.Kp32; a.g1_mask = m->dense_g1_mask;
+    a.M = rows; a.KT = L.KT_B; a.MG = L.MG_B; a.mg_per_block = (rows <= 8192) ? 1 : L.MG_B; a.Np32 = L.Kp32; a.g1_mask = m->opt.dense_g1_mask;
     a.YP = YP; a.ldYP = L.Kp32; a.YF = YF; a.ldYF = L.Kp32;
     a.ACT = ACT; a.ldACT = L.Kp32;
     CHK(attach_dense_stamps(m, ACT ? EPI_DX : EPI_F32, a));
@@ -715,29 +780,32 @@ int dense_dx(iwae_model* m, Linear& L, const uint16_t* GP, int rows, const uint1
 // backward of one BasicBlock over R rows: the dX chain first, then the three weight gradients -- they only feed the
 // slab reduction, so for small R (latency-bound 8-wave kernels) they go out as ONE grouped launch
 // dx_done: the dX chain (dhead -> d2 -> d1 -> dx) has been computed already (gblock_bwd_kernel): only the weight gradients are left
-// lat != null: the block's dhead rows are made inside block_bwd_kernel (latent_bwd_kernel's sums, a wave per image) -- *lat_taken says whether
-// that happened (else the caller launches latent_bwd_kernel first and calls again without it)
+// Does block_bwd_kernel take both dX products of the block on R rows?  Fills the shape half of its argument block.
+bool block_bwd_shape(const iwae_model* m, const Linear* blk, int R, BlockBwdArgs& b) {
+    memset(&b, 0, sizeof(b));
+    b.ldDH = blk[2].Np32; b.imgH = blk[2].imgB; b.imgL2 = blk[1].imgB;
+    b.KTH = blk[2].KT_B; b.KT1 = blk[1].KT_B; b.NT1 = blk[0].Np32 / 16; b.R = R; b.ldH = blk[0].Np32;
+    return m->opt.allow_block_fused && !blk[2].kmajor && !blk[1].kmajor && blk[1].Np32 == blk[0].Np32 && blk[1].Kp32 == blk[0].Np32 && blk[2].Kp32 == blk[0].Np32 && block_bwd_ok(b);
+}
+// ... and can that launch make the head's gradient rows of a latent Dp wide itself (no conditional prior, bf16 rows)?
+bool lat_in_block_ok(const Linear* blk, int Dp, bool prior, bool f32_rows) { return Dp <= 128 && Dp == blk[2].Np32 / 2 && !prior && !f32_rows; }
+// lat != null: the block's dhead rows are made inside block_bwd_kernel (latent_bwd_kernel's sums, a wave per image) -- only where
+// block_bwd_shape and lat_in_block_ok say so (StepPlan::lat_fuse); elsewhere the caller launches latent_bwd_kernel first
 int block_bwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* inP, int R, bool need_dx, bool wgrad_on_side, bool dx_done = false, hipStream_t side_st = nullptr,
-              bool skip_wgrad = false, const LatentBwdArgs* lat = nullptr, bool* lat_taken = nullptr) {
-    if (lat_taken) *lat_taken = false;
+              bool skip_wgrad = false, const LatentBwdArgs* lat = nullptr) {
     bool chain_fused = dx_done;
     if (dx_done) need_dx = false;
-    if (!dx_done && m->allow_block_fused && !blk[2].kmajor && !blk[1].kmajor && blk[1].Np32 == blk[0].Np32 && blk[1].Kp32 == blk[0].Np32 && blk[2].Kp32 == blk[0].Np32) {
-        BlockBwdArgs b;      // few rows (the encoder on the batch's images): both dX products in one launch
-        memset(&b, 0, sizeof(b));
-        b.DH = ptr<uint16_t>(w.dheadP); b.ldDH = blk[2].Np32; b.imgH = blk[2].imgB; b.imgL2 = blk[1].imgB;
-        b.KTH = blk[2].KT_B; b.KT1 = blk[1].KT_B; b.NT1 = blk[0].Np32 / 16; b.R = R;
-        b.H2 = ptr<uint16_t>(w.h2P); b.H1 = ptr<uint16_t>(w.h1P); b.ldH = blk[0].Np32;
+    BlockBwdArgs b;
+    if (!dx_done && block_bwd_shape(m, blk, R, b)) {      // few rows (the encoder on the batch's images): both dX products in one launch
+        b.DH = ptr<uint16_t>(w.dheadP); b.H2 = ptr<uint16_t>(w.h2P); b.H1 = ptr<uint16_t>(w.h1P);
         b.D2 = ptr<uint16_t>(w.d2P); b.D1 = ptr<uint16_t>(w.d1P);
-        if (block_bwd_ok(b)) {
-            if (lat && lat->Dp <= 128 && lat->Dp == blk[2].Np32 / 2 && !lat->prior_head && !lat->DHF) {
-                b.lat_on = 1; b.lat = *lat; if (lat_taken) *lat_taken = true;
-                b.rows_per_wg = lat->k > 16 ? 4 : 16;      // (many samples per image: four waves per image, 4 images per workgroup -- block_bwd_kernel<4>)
-            }
-            else if (lat) return IWAE_OK;      // (not taken: nothing launched)
-            launch_block_bwd(b, m->stream); chain_fused = true;
-        } else if (lat) return IWAE_OK;
-    } else if (lat) return IWAE_OK;
+        if (lat) {
+            if (!lat_in_block_ok(blk, lat->Dp, lat->prior_head != nullptr, lat->DHF != nullptr)) return fail(IWAE_ERR_STATE, "block_bwd: latent sums on a shape block_bwd_kernel does not cover");
+            b.lat_on = 1; b.lat = *lat;
+            b.rows_per_wg = lat->k > 16 ? 4 : 16;      // (many samples per image: four waves per image, 4 images per workgroup -- block_bwd_kernel<4>)
+        }
+        launch_block_bwd(b, m->stream); chain_fused = true;
+    } else if (lat) return fail(IWAE_ERR_STATE, "block_bwd: latent sums on a shape block_bwd_kernel does not cover");
     if (!chain_fused) {
         CHK(dense_dx(m, blk[2], ptr<uint16_t>(w.dheadP), R, ptr<uint16_t>(w.h2P), ptr<uint16_t>(w.d2P), nullptr));
         CHK(dense_dx(m, blk[1], ptr<uint16_t>(w.d2P), R, ptr<uint16_t>(w.h1P), ptr<uint16_t>(w.d1P), nullptr));
@@ -782,13 +850,13 @@ int block_bwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* inP, int R
 // (fuse) the Adam update in the epilogue -- one launch instead of the grouped weight gradient + slabs + reduce_grads_kernel (round 4).
 // with_means: one extra block turns the step's per-image values into its batch means (what reduce_grads_kernel's extra block did).
 bool wgrad_rows_ok(const iwae_model* m, const Linear* blk, int R) {
-    return m->allow_wgrad_rows && R <= 2048 && blk[0].nsub == 1 && blk[1].nsub == 1 && blk[2].nsub <= 2 && !blk[0].kmajor && !blk[1].kmajor && !blk[2].kmajor;      // (its epilogue writes MG-major images)
+    return m->opt.allow_wgrad_rows && R <= 2048 && blk[0].nsub == 1 && blk[1].nsub == 1 && blk[2].nsub <= 2 && !blk[0].kmajor && !blk[1].kmajor && !blk[2].kmajor;      // (its epilogue writes MG-major images)
 }
 // Few DATA rows too (M = B * k <= 2 048: the reference's default regime, B = 20): the decoder's three weight gradients join the encoder's in the
 // SAME launch (six jobs; the output layer's G = the stored s takes its row weights on the way in) -- no side-stream launches, no slabs, no
 // deferred reduction, no cross-stream events in the whole backward pass.  1-layer model only (the 2-layer model's per-sample blocks keep their path).
 bool dec_rows_step(const iwae_model* m, int M, int B) {
-    return m->allow_dec_rows && m->cfg.n_layers == 1 && M <= 2048 && wgrad_rows_ok(m, m->enc1, B) && m->dec1[0].nsub == 1 && m->dec1[1].nsub == 1 &&
+    return m->opt.allow_dec_rows && m->cfg.n_layers == 1 && M <= 2048 && wgrad_rows_ok(m, m->enc1, B) && m->dec1[0].nsub == 1 && m->dec1[1].nsub == 1 &&
            m->dec1[2].nsub == 1 && !m->dec1[0].kmajor && !m->dec1[1].kmajor;
 }
 int block_wgrad_rows(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* inP, int R, float alpha, bool fuse, bool with_means, bool with_decoder = false) {
@@ -805,7 +873,7 @@ int block_wgrad_rows(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* inP
         jobs[i].sub1 = ls[i]->nsub == 2 ? ls[i]->sub[1] : -1;
         jobs[i].split = ls[i]->nsub == 2 ? ls[i]->joff[1] : (1 << 30);
     }
-    if (with_decoder && m->s_mode) jobs[3].rowscale = ptr<float>(m->gx);      // the forward pass kept s: dl = g_r s is made on the way in (else dlP already holds dl)
+    if (with_decoder && m->plan.s_mode) jobs[3].rowscale = ptr<float>(m->gx);      // the forward pass kept s: dl = g_r s is made on the way in (else dlP already holds dl)
     const bool two = m->cfg.n_layers == 2;
     launch_wgrad_rows(jobs, njobs, m->d_descs, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, fuse ? 1 : 0,
                       with_means ? ptr<float>(m->per_b) : nullptr, m->B, two ? 1.f : m->beta, m->d_scalars, m->d_zero, m->stream);
@@ -874,21 +942,218 @@ int epsm_find(const iwae_model* m, uint32_t step, int M) {
     return -1;
 }
 
-// the stream that carries the speculative draw of the NEXT step's noise: one that this step's backward pass orders behind the main stream
-// and whose last event the next forward joins (see the call in forward_impl; m->early_wout must be decided)
-hipStream_t eps_draw_stream(const iwae_model* m, int M) {
-    if (dec_rows_step(m, M, m->B)) return m->stream;      // (that backward pass touches no side stream at all: the draw stays in stream order)
-    return (m->allow_wg3 && m->use_side2 && m->side2 && M <= 4096 && m->early_wout) ? m->side2 : m->side;
+inline hipStream_t on_stream(const iwae_model* m, OnStream s) { return s == ON_SIDE2 ? m->side2 : s == ON_SIDE ? m->side : m->stream; }
+
+// ---------------------------------------------------------------- the step's plan
+// Which kernels a bf16 call launches and on which streams, decided once from the options, the layer tables and the call's shape.  A pure host
+// function: it touches no buffer, stream or event, and forward_impl calls it before it launches or allocates anything.  Every shape predicate
+// is asked here, on the shape half of the launch's own argument block; the launch code adds the buffers and asks nothing again.
+StepPlan plan_step(const iwae_model* m, int B, int k, int objective, bool bwd, const FwdCall& call, const iwae_tensors* want, bool host_eps) {
+    const StepOptions& o = m->opt;
+    StepPlan p = StepPlan();
+    const bool two = m->cfg.n_layers == 2;
+    const int M = B * k, Mp = round_up(M, 128), X = m->X, Xp = m->Xp32;
+    const Linear* d1 = m->dec1;
+    const Linear& L = m->dec1[2];
+    BlockFwdArgs bf;
+    p.enc_takes_f32 = m->C == 0 && block_fwd_shape(m, m->enc1, B, bf);
+    p.dec_rows = bwd && dec_rows_step(m, M, B);
+    p.want_dreg = !two && (objective == OBJ_DREG || (!bwd && !call.log_w_only));    // tasks/task02.py:63-65
+    // ---- the step's N(0,1) draws
+    // (round 4: a forward-only call on many rows -- the k = 5000 evaluator on bf16 operands -- also takes its draws from eps_gen_kernel, so that the
+    // decoder kernel makes z itself in its prologue instead of sample_kernel drawing inline and writing z out: option zin_eval, off by default -- measured slower)
+    p.zin_eval = !bwd && !two && m->C == 0 && o.allow_zin && o.allow_zin_eval && (int64_t)B * k >= 8192 && o.allow_dec_fused && o.allow_bern_pipe;
+    p.keep_eps = !host_eps && (bwd || two || p.zin_eval);
+    // few data rows, training step, single-stream backward (dec_rows_step): the draws come from the multi-step buffers (one launch per EPSM_STEPS steps)
+    p.eps_multi = p.keep_eps && bwd && !two && o.allow_eps_multi && call.k_total == 0 && p.dec_rows;
+    // ---- who would make z
+    // 1-layer training step on the device's own noise: the first decoder layer makes z itself (dense_kernel ZIN mode, or the decoder kernel's prologue,
+    // which also sums the DReG step's second log q)
+    const bool fuse_z = o.allow_zin && !two && m->C == 0 && (bwd || p.zin_eval) && p.keep_eps && M >= 8192 && (d1[0].KT == 4 || d1[0].KT == 2) && d1[0].Kp32 == m->Dp[0];
+    // few rows: block_fwd_kernel (the decoder's two tanh layers in one launch) makes z itself -- one latency-bound launch less
+    const bool sample_in_block = o.allow_block_fused && o.allow_zin && !two && !fuse_z && M <= 4096 && d1[0].Kp32 == m->Dp[0];
+    // 2-layer model at large row counts, the reference's dims: chain2_fwd_kernel makes z1 itself, as its first layer's operand
+    if (two) {
+        const Linear *e2 = m->enc2, *d2 = m->dec2;
+        p.chain = o.allow_chain2 && chain2_fwd_ok(e2[0].KT, e2[1].KT, d2[0].KT, M) && e2[0].Kp32 == m->Dp[0] && e2[0].Np32 == 32 * e2[1].KT &&
+                  e2[1].Np32 == e2[0].Np32 && e2[2].KT == e2[1].KT && e2[2].Np32 == 2 * m->Dp[1] && d2[0].Kp32 == m->Dp[1] && d2[0].Np32 == e2[0].Np32 &&
+                  d2[1].KT == e2[1].KT && d2[1].Np32 == d2[0].Np32 && d2[2].KT == e2[1].KT && d2[2].Np32 == 2 * m->Dp[0];
+        p.chain2_bwd = p.chain && bwd && o.allow_chain2_bwd && gblock_bwd_ok(e2[0].KT, e2[1].KT, d2[0].KT, M) && e2[0].imgB && d2[0].imgB;
+    }
+    // ---- the output layer's block
+    DenseArgs& a = p.bern;
+    a.ldX = L.Kp32; a.img = L.imgF;
+    a.split = 1 << 30;
+    a.M = M; a.KT = L.KT; a.MG = L.MG; a.mg_per_block = L.MG; a.Np32 = L.Np32; a.g1_mask = o.dense_g1_mask;
+    // few rows: the output layer runs inside block_fwd_kernel, behind the two tanh layers of the same 16-row tile (one launch for the
+    // whole decoder; log p(x|z) per row comes out whole, not as per-group partial sums)
+    const bool out_in_block = o.allow_block_fused && o.allow_out_in_block && !fuse_z && M <= 4096 && !(want && want->logits) && !m->want_stamps &&
+                              d1[1].Np32 == d1[0].Np32 && d1[1].Kp32 == d1[0].Np32 && L.Kp32 == d1[1].Np32 && L.KT == d1[1].KT && L.KT <= 8;
+    // small row counts (the reference's default B = 20, k = 5): a handful of workgroups walking all 13 pixel groups
+    // in turn is 40 us of latency -- one pixel group per block instead, log p(x|z) as per-group partial sums that
+    // lse_kernel adds up in fixed order
+    if (M < 8192 && L.MG > 1 && !out_in_block) { a.mg_per_block = 1; p.px_parts = L.MG; }
+    a.ldXB = m->Xinp; a.k = k; a.B = B; a.Xdim = X;
+    a.lpxz_stride = p.px_parts > 1 ? (size_t)Mp : 0;
+    // training step: keep s = x - sigmoid(l) for the backward pass (out_bwd_s_kernel, output-layer weight gradient)
+    p.s_mode = bwd && o.allow_s_mode && out_bwd_has_s_mode(L.KT);
+    if (p.s_mode) {
+        a.ldYP = Xp;
+        if (m->fake_s & 4) a.dbg = 32;
+        if (m->fake_s & 16) a.dbg |= 64;      // (the decoder kernel's tanh layers without their weight DMA)
+        if (m->fake_s & 32) a.dbg |= 128;     // (phase exits of the decoder kernel, for instruction counters: behind the prologue,
+        if (m->fake_s & 64) a.dbg |= 256;     //  behind both tanh layers,
+        if (m->fake_s & 128) a.dbg |= 512;    //  behind the first)
+    }
+    a.pipe = o.allow_bern_pipe ? 1 : 0;
+    if (a.pipe && o.bern_qw) {      // the 16-wave / 200-row shape is one workgroup per CU: only where its last round is nearly full
+        const int nwg = (M + 199) / 200, ncu = std::max(1, m->num_cus);
+        const int rounds = (nwg + ncu - 1) / ncu;
+        if ((double)nwg >= 0.9 * (double)rounds * ncu || o.bern_qw_force) a.pipe = 2;
+    }
+    // ---- the decoder's tanh layers
+    // The whole decoder in one launch (bern_pipe_kernel<.., PRE>) where that kernel exists: the two tanh layers' activations
+    // stay in registers from layer to layer (z made in the kernel when the step runs on the device's noise).
+    if (o.allow_dec_fused && a.pipe && m->C == 0 && d1[0].KT <= 4 && d1[0].Kp32 == m->Dp[0] && d1[0].Np32 == L.Kp32 && d1[1].Kp32 == L.Kp32 && d1[1].Np32 == L.Kp32) {
+        DenseArgs pre = a;
+        pre.pre_img1 = d1[0].imgF; pre.pre_KT1 = d1[0].KT; pre.pre_img2 = d1[1].imgF;
+        pre.logits_out = want ? want->logits : nullptr;      // (only "logits are written", in this local copy: the predicate refuses it, so the plan's block never holds the caller's pointer)
+        if (bern_pipe_ok(pre)) { a = pre; p.dec_fwd = DEC_PIPE; }
+    }
+    // few rows: the two tanh layers as ONE launch of block_fwd_kernel (a BasicBlock without its head: 16-row workgroups,
+    // weights straight from the L2-resident images) instead of two latency-bound dense_kernel launches
+    if (p.dec_fwd != DEC_PIPE && o.allow_block_fused && !fuse_z && M <= 4096 && d1[1].Np32 == d1[0].Np32 && d1[1].Kp32 == d1[0].Np32) {
+        BlockFwdArgs& b = p.dec_blk;
+        b.ldX = d1[0].Kp32; b.img0 = d1[0].imgF; b.img1 = d1[1].imgF; b.img2 = d1[1].imgF;
+        b.KT0 = d1[0].KT; b.KT1 = d1[1].KT; b.NT1 = d1[0].Np32 / 16; b.NT2 = 0; b.R = M;
+        b.ldH = d1[0].Np32; b.split = 1 << 30;
+        if (sample_in_block) { b.sample = 1; b.S.Dp = m->Dp[0]; b.S.M = M; }      // (forward_impl puts the whole sampling block there)
+        if (out_in_block) { b.oimg = L.imgF; b.oXdim = X; b.oH = L.Np32 >> 5; b.oldXB = m->Xinp; b.ok = k; b.oldS = Xp; }
+        if (block_fwd_shape_ok(b)) p.dec_fwd = out_in_block ? DEC_BLOCK_OUT : DEC_BLOCK2;
+    }
+    const bool in_block = p.dec_fwd == DEC_BLOCK2 || p.dec_fwd == DEC_BLOCK_OUT;
+    // (dense_kernel's sampled-input mode has no DReG sum; a block kernel that does not run cannot sample either: sample_kernel then)
+    p.z_from = p.chain ? Z_CHAIN2 : (fuse_z && p.dec_fwd == DEC_PIPE) ? Z_DEC_PROLOGUE : (fuse_z && !p.want_dreg) ? Z_DENSE_ZIN : (sample_in_block && in_block) ? Z_BLOCK : Z_SAMPLE;
+    // ---- log-mean-exp and the output layer's weight gradient
+    p.early_wout = bwd && p.s_mode && o.allow_early_wout && !p.dec_rows;      // (few data rows: no side-stream work in the backward pass at all)      // (round 3: the 2-layer model too -- its weight gradients are 220 us of kernels, on ONE side stream behind dec_bwd they ended 100 us after the main stream)
+    // Round 3: where the decoder kernel's workgroups own whole images (16-wave / 200-row shape, k a divisor of 200) it also does
+    // lse_kernel's work for them -- the backward pass starts right behind it: one launch (7 us) and one dispatch gap (6 us) less
+    // on the loop that sets the step, and no second lse_kernel on the side stream.
+    if (p.dec_fwd == DEC_PIPE && o.allow_lse_fused && !m->want_stamps) {
+        DenseArgs lse = a;      // (shapes only; forward_impl asks again on the filled block, where z made in the prologue brings its term pointers)
+        lse.lse_on = 1; lse.lse.n_px_part = 1;
+        if (bern_lse_ok(lse)) { a.lse_on = 1; p.lse_fused = true; }
+    }
+    // round 4: with the row weights made inside the decoder kernel, it also leaves g2w = bf16(g_r g2) -- the output layer's weight gradient
+    // (forked right behind this kernel) then needs no row weighting.  Needs a pad column in the hidden width for g_r itself (the bias gradient).
+    p.g2w = p.lse_fused && p.early_wout && o.allow_g2w && p.s_mode && L.Kin < L.Kp32 && !two;
+    if (p.g2w) a.g2w_feat = L.Kin;
+    // s-mode training step: the output layer's weight gradient needs s, g2 and the row weights -- not out_bwd -- so the
+    // side stream forks early.  Round 2: it forks behind the decoder kernel (event on its dispatch packet) and runs its own copy of
+    // lse_kernel (7 us, a few waves) for the row weights, instead of forking behind the main stream's lse_kernel: the ~12 us
+    // a cross-stream hand-off takes now pass beside the main stream's lse_kernel, not behind it.
+    p.lse_dup = p.early_wout && o.allow_lse_dup && p.px_parts == 1 && p.dec_fwd != DEC_BLOCK_OUT && !p.lse_fused;
+    if (p.lse_fused) p.lse_at = LSE_DECODER;
+    if (!bwd) return p;
+
+    // ---- the backward pass
+    // One launch for out_bwd + dX of d2 + dX of d1 (dec_bwd_kernel) where it exists: s kept by the forward pass, hidden width with an
+    // instantiation, large row counts or (small_dec_bwd) few; dpre2 / dpre1 stay in registers from product to product.
+    const bool small_fused = o.small_dec_bwd && o.allow_dec_bwd && p.s_mode && M <= o.small_rows && out_bwd_has_s_mode(L.KT) && !m->want_stamps;
+    p.out_parts = p.s_mode && M < 8192 && L.MG > 1 && !small_fused;      // small row counts: one pixel group per block, partial sums + finish kernel
+    const bool fused_dx = o.allow_dec_bwd && p.s_mode && !p.out_parts && (M >= 8192 || small_fused) && !(m->want_stamps && L.KT == 7) && L.kmajor && L.imgB &&
+                          d1[1].KT_B == L.KT && d1[1].MG_B == (L.KT + 1) / 2 && d1[0].KT_B == L.KT && d1[1].Kp32 == L.Kp32 && d1[0].Np32 == L.Kp32;
+    // 1-layer model: dz has one reader (latent_bwd_kernel): bf16 halves its 26 MB each way (the 2-layer model adds two more
+    // float32 terms to it there and keeps float32)
+    p.dz_half = fused_dx && !two && o.allow_dz_half;
+    DecBwdRowsArgs& r = p.rows;      // few rows: 16-row workgroups, weights straight from L2
+    r.ldS = Xp; r.KTX = Xp / 32; r.imgK3 = L.imgB; r.MT3 = L.MT_B;
+    r.imgB2 = d1[1].imgB; r.imgB1 = d1[0].imgB; r.KT = L.KT; r.NT1 = L.Kp32 / 16; r.NT3 = d1[0].Kp32 / 16; r.M = M;
+    r.ldH = L.Kp32; r.ldDZ = d1[0].Kp32;
+    p.dx = !fused_dx ? DX_THREE : (M <= o.dec_rows_max && o.allow_block_fused && dec_bwd_rows_ok(r)) ? DX_ROWS : DX_DEC_BWD;
+    // Few rows (round 4): the training step's log-mean-exp is done by the backward pass's first kernel (dec_bwd_rows_kernel, a wave per
+    // image in front of its own work): one dependent launch less on a chain of ~10 us launches.  1-layer model below small_rows only: the
+    // kernel has never taken the 2-layer model's five terms, nor the log-mean-exp of a step of 8 192 rows or more
+    if (!p.lse_fused && o.allow_lse_in_bwd && !p.lse_dup && !p.early_wout && p.dx == DX_ROWS && small_fused && !two) { p.lse_at = LSE_BWD_ROWS; r.lse_on = 1; }
+    // ---- the side streams: the decoder's weight gradients only need what the dX chain produced plus forward activations
+    // Few rows (round 3): the three as ONE grouped launch on `side2` behind the dX chain (the B = 20 step is bound by the host's
+    // launches and the streams' hand-offs, not by these kernels: 13 -> 11 launches, two events less)
+    // (early_wout says: stored s, and not the single-stream dec_rows step)
+    const bool few_side2 = p.early_wout && o.allow_wg3 && o.use_side2 && M <= 4096;
+    int ns[3], nw[3], cps;
+    for (int i = 0; i < 3; ++i) wgradp_shape(m, d1[i], M, ns[i], nw[i], cps);
+    p.group3 = few_side2 && fused_dx && nw[0] == 8 && nw[1] == 8 && nw[2] == 8;
+    p.wout_two_part = !p.dec_rows && !p.group3 && o.wout_split > 0 && p.s_mode && !p.g2w && p.early_wout && o.use_side2 && fused_dx && M >= 8192 && L.IT <= 14 && o.allow_wg7 && !(m->abl_skip & 1);
+    // The hidden layers' weight gradients need dpre2 / dpre1, not the output layer's gradient: forked early, that one keeps `side` busy well
+    // past the end of the dX chain, so they go to a second side stream and run beside it.  They finish last, so that stream is the `tail`.
+    p.hid_on = p.dec_rows ? ON_MAIN : (p.group3 || (p.early_wout && o.use_side2)) ? ON_SIDE2 : ON_SIDE;
+    p.hid_group = nw[1] == 7 && nw[0] == 7 && o.allow_wg_group && (p.early_wout || fused_dx);      // (both inputs ready: one launch)
+    p.tail = p.dec_rows ? ON_SIDE : p.hid_on;
+    // The NEXT step's noise is drawn on a stream that this backward pass orders behind the main stream and whose last event the next forward
+    // joins: `side`; few rows, where `side2` carries the group (or the hidden layers' gradients) and the decoder update in front of that
+    // event: `side2`; the dec_rows step touches no side stream at all: the draw stays in stream order
+    p.draw_on = p.dec_rows ? ON_MAIN : few_side2 ? ON_SIDE2 : ON_SIDE;
+    // ---- the encoder
+    // Few images and samples (round 4): latent_bwd_kernel's per-image sums are made inside the encoder's block_bwd_kernel (a wave per image in
+    // front of its dX chain) -- one dependent launch less; the separate kernel (256 threads per image) stays for many samples per image
+    // (measured, end-to-end us per step with / without: B = 20, k = 1: 67.7 / 70.0; B = 20, k = 5: 67.5 / 69.3; B = 100, k = 5: 72.1 / 73.4; B = 20, k = 50: 88.2 / 78.5 --
+    // one wave walking 50 samples is slower than latent_bwd_kernel's 256 threads: up to 16 samples per image)
+    // (round 5, option lat_rows4: beyond 16 samples per image block_bwd_kernel<4> -- 4 images per workgroup, an image's samples over four waves --
+    // can take the sums on 4 x the workgroups; measured no faster than the two launches in the step, see allow_lat_rows4)
+    BlockBwdArgs bb;
+    p.lat_fuse = o.allow_lat_in_block && B <= 1024 && (k <= 16 || (o.allow_lat_rows4 && B >= 64)) && block_bwd_shape(m, m->enc1, B, bb) &&
+                 lat_in_block_ok(m->enc1, m->Dp[0], m->has_prior, false);
+    // Round 4: on few rows the image encoder's weight gradients, their sum over ALL rows and (fused step) the Adam update are one launch
+    // (wgrad_rows_kernel) -- the encoder's layers (the head of the table) then need no slabs and no share of reduce_grads_kernel
+    p.rows_enc = wgrad_rows_ok(m, m->enc1, B);
+    return p;
 }
 
-// will this step's backward pass run the decoder's dX chain as dec_bwd_rows_kernel (few rows)?  Mirrors backward_impl's choice (which
-// copes with a wrong answer: a pending log-mean-exp is then launched as lse_kernel after all); m->s_mode must be decided.
-bool dec_bwd_rows_planned(const iwae_model* m, int M) {
-    const Linear& L = m->dec1[2];
-    if (!(m->s_mode && m->allow_dec_bwd && m->small_dec_bwd && M <= m->small_rows && out_bwd_has_s_mode(L.KT) && !m->want_stamps)) return false;
-    if (!(L.kmajor && L.imgB && m->dec1[1].KT_B == L.KT && m->dec1[1].MG_B == (L.KT + 1) / 2 && m->dec1[0].KT_B == L.KT && m->dec1[1].Kp32 == L.Kp32 &&
-          m->dec1[0].Np32 == L.Kp32)) return false;
-    return M <= m->dec_rows_max && m->allow_block_fused && m->cfg.n_layers == 1;
+// log_w / log-mean-exp arguments of the call in flight (lse_kernel, or the kernel that does its work: StepPlan::lse_at); the buffers exist (lse_alloc)
+void lse_args(iwae_model* m, int objective, bool bwd, const iwae_tensors* want, LseArgs& a) {
+    const bool two = m->cfg.n_layers == 2;
+    float* lpxz = ptr<float>(m->rows[0]);
+    memset(&a, 0, sizeof(a));
+    if (!two) {
+        a.term[0] = lpxz; a.coef[0] = 1.f;
+        a.term[1] = ptr<float>(m->rows[1]); a.coef[1] = m->beta;
+        a.term[2] = ptr<float>(m->rows[2]); a.coef[2] = -m->beta;
+        a.head = ptr<float>(m->wenc1.head); a.ldH = 2 * m->Dp[0]; a.D = m->D[0]; a.Dp = m->Dp[0];
+        a.cz_on = 1.f;
+    } else {
+        a.term[0] = lpxz; a.coef[0] = 1.f;    // iwae2.py:128 (beta unused there)
+        a.term[1] = ptr<float>(m->rows[1]); a.coef[1] = 1.f;
+        a.term[2] = ptr<float>(m->rows[2]); a.coef[2] = 1.f;
+        a.term[3] = ptr<float>(m->rows[3]); a.coef[3] = -1.f;
+        a.term[4] = ptr<float>(m->rows[4]); a.coef[4] = -1.f;
+        a.head = nullptr;
+        a.cz_on = 0.f;
+    }
+    a.lq_dreg = m->plan.want_dreg ? ptr<float>(m->rows[5]) : nullptr;
+    a.B = m->B; a.k = m->k; a.beta = two ? 1.f : m->beta; a.objective = objective;
+    a.lme_only = (!bwd && m->call.log_w_only && !want) ? 1 : 0;
+    a.logw = ptr<float>(m->logw); a.wn = ptr<float>(m->wn); a.gx = ptr<float>(m->gx);
+    a.cf = ptr<float4>(m->cf); a.per_b = ptr<float>(m->per_b);
+    a.n_px_part = 1; a.px_stride = (size_t)m->Mp; a.term0_out = lpxz;
+}
+// ... with log p(x|z) taken from the per-pixel-group partial sums where the forward left those (lse_kernel, dec_bwd_rows_kernel)
+void lse_args_parts(iwae_model* m, int objective, bool bwd, const iwae_tensors* want, LseArgs& a) {
+    lse_args(m, objective, bwd, want, a);
+    if (m->plan.px_parts > 1) a.term[0] = ptr<float>(m->px_part);
+    a.n_px_part = m->plan.px_parts;
+}
+int lse_alloc(iwae_model* m) {
+    hipStream_t st = m->stream;
+    CHK(ensure(m->logw, (size_t)m->Mp * 4, st));
+    CHK(ensure(m->wn, (size_t)m->Mp * 4, st));
+    {   // the row weights are also read 64 at a time by the output layer's weight gradient: pad rows must stay finite
+        const void* before = m->gx.p;
+        CHK(ensure(m->gx, (size_t)m->Mp * 4, st));
+        if (m->gx.p != before) HIPCHK(hipMemsetAsync(m->gx.p, 0, m->gx.cap, st));
+    }
+    CHK(ensure(m->cf, (size_t)m->Mp * 16, st));
+    CHK(ensure(m->per_b, (size_t)PB_COUNT * m->B * 4, st));
+    return IWAE_OK;
 }
 
 // What both forward passes start with: the argument checks, the conditional model's y rows of these images (*cond, null without) and the
@@ -938,23 +1203,18 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
                  const iwae_tensors* want, const FwdCall& call) {
     const float* cond;
     CHK(begin_forward(m, x, B, k, beta, call, &cond));
+    m->plan = plan_step(m, B, k, objective, bwd, call, want, eps != nullptr);
+    const StepPlan& p = m->plan;
     const bool two = m->cfg.n_layers == 2;
     m->bf16_side_used = true;
     if (m->f32_z_pending) { HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->f32_z_pending = false; }      // (ev_join is this path's too)
-    m->lse_pending = false;      // (set again below if this step leaves its log-mean-exp to the backward pass)
     m->time_this = m->timing > 0 && (m->timing_calls++ % m->timing) == 0;
     const int M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X, Xp = m->Xp32, Xinp = m->Xinp;
     hipStream_t st = m->stream;
     m->user_eps = eps != nullptr;
     // ---- the step's N(0,1) draws: normally already there (prefetched by the previous training step), else drawn now
-    // (round 4: a forward-only call on many rows -- the k = 5000 evaluator on bf16 operands -- also takes its draws from eps_gen_kernel, so that the
-    // decoder kernel makes z itself in its prologue instead of sample_kernel drawing inline and writing z out: option zin_eval, off by default -- measured slower)
-    const bool zin_eval = !bwd && !two && m->C == 0 && m->allow_zin && m->allow_zin_eval && (int64_t)B * k >= 8192 && m->allow_dec_fused && m->allow_bern_pipe;
-    const bool keep_eps = !eps && (bwd || two || zin_eval);
     m->epsc_ptr[0] = m->epsc_ptr[1] = nullptr;
-    // few data rows, training step, single-stream backward (dec_rows_step): the draws come from the multi-step buffers (one launch per EPSM_STEPS steps)
-    const bool eps_multi = keep_eps && bwd && !two && m->allow_eps_multi && call.k_total == 0 && dec_rows_step(m, M, B);
-    if (eps_multi) {
+    if (p.eps_multi) {      // few data rows: from the multi-step buffers (one launch per EPSM_STEPS steps)
         int bi = epsm_find(m, m->noise_step, M);
         if (bi < 0) {      // (first step, another batch shape, a jump of iwae_set_step: drawn now, in stream order)
             bi = (m->epsm_tag[0].valid && !m->epsm_tag[1].valid) ? 1 : 0;
@@ -963,7 +1223,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         const size_t soff = (size_t)(m->noise_step - m->epsm_tag[bi].step0) * (size_t)round_up(M, 128);
         for (int l = 0; l < m->cfg.n_layers; ++l) m->epsc_ptr[l] = ptr<float>(m->epsm[bi][l]) + soff * eps_ld(m, l);
     } else
-    if (keep_eps) {
+    if (p.keep_eps) {
         const int np = (m->epsc_par + 1) % 3;
         const uint64_t ro = (uint64_t)call.batch_offset * (uint64_t)k;
         iwae_model::EpsTag& tg = m->eps_tag[np];
@@ -982,7 +1242,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     const float *xd, *xf_pending = nullptr;
     CHK(stage_input(m, x, B, false, &xd));
     if (xd) {      // (the resident set's rows are in m->xP already)
-        if (m->C == 0 && m->allow_block_fused) xf_pending = xd;      // the fused encoder kernel converts the rows itself
+        if (p.enc_takes_f32) xf_pending = xd;      // the fused encoder kernel converts the rows itself
         else launch_prep_rows(xd, cond, B, X, m->C, Xinp, Bp, ptr<uint16_t>(m->xP), st);
     }
 
@@ -990,16 +1250,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     CHK(block_alloc(m, m->enc1, m->wenc1, B, Bp, bwd, false));
     {
     ScopedTimer tm_enc(m, T_ENC_FWD);
-    if (xf_pending) {
-        bool took = false;
-        CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, xf_pending, X, &took));
-        if (!took) {        // shapes the fused kernel does not cover: convert, then the three-launch path
-            launch_prep_rows(xf_pending, nullptr, B, X, 0, Xinp, Bp, ptr<uint16_t>(m->xP), st);
-            CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B));
-        }
-    } else {
-        CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B));
-    }
+    CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, xf_pending, X));
     }
 
     for (int i = 0; i < 6; ++i) CHK(ensure(m->rows[i], (size_t)Mp * 4, st));
@@ -1014,8 +1265,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     // the draws are kept when later kernels of this call need them again (backward, 2-layer densities)
     CHK(ensure(m->zP[0], (size_t)Mp * m->Dp[0] * 2, st));
     CHK(join_side(m));      // from here on: the prefetched noise, then the decoder's weights
-    bool fuse_z = false, sample_in_block = false, chain = false;
-    SampleArgs zin;
+    SampleArgs zin;      // the sampling of z (z1): sample_kernel's arguments, or the prologue's of the kernel that makes z itself (p.z_from)
     memset(&zin, 0, sizeof(zin));
     if (m->has_prior) {     // p(z|y) = N(mu_p(y), sigma_p(y)) (tasks/task04.py:124): the prior block on the B condition rows
         const int Cp = round_up(m->C, 32);
@@ -1034,23 +1284,9 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         s.prior_head = m->has_prior ? ptr<float>(m->wprior.head) : nullptr;
         s.lp_prior = two ? nullptr : t1;
         s.lq = two ? t3 : t2;
-        const bool want_dreg = !two && (objective == OBJ_DREG || (!bwd && !call.log_w_only));    // tasks/task02.py:63-65
-        s.lq_dreg = want_dreg ? lqd : nullptr;
-        // 1-layer training step on the device's own noise: the first decoder layer makes z itself (dense_kernel ZIN mode)
-        // (the DReG step too: the decoder kernel's prologue also sums the second log q; if that kernel turns out not to apply, sample_kernel runs after all)
-        fuse_z = m->allow_zin && !two && m->C == 0 && (bwd || zin_eval) && s.eps.cache != nullptr && M >= 8192 &&
-                 (m->dec1[0].KT == 4 || m->dec1[0].KT == 2) && m->dec1[0].Kp32 == m->Dp[0];
-        // few rows: block_fwd_kernel (the decoder's two tanh layers in one launch, below) makes z itself -- one latency-bound launch less
-        sample_in_block = m->allow_block_fused && m->allow_zin && !two && !fuse_z && M <= 4096 && !s.ZF && m->dec1[0].Kp32 == m->Dp[0];
-        // 2-layer model at large row counts, the reference's dims: chain2_fwd_kernel (below) makes z1 itself, as its first layer's operand
-        if (two) {
-            const Linear *e2 = m->enc2, *d2 = m->dec2;
-            chain = m->allow_chain2 && chain2_fwd_ok(e2[0].KT, e2[1].KT, d2[0].KT, M) && e2[0].Kp32 == m->Dp[0] && e2[0].Np32 == 32 * e2[1].KT &&
-                    e2[1].Np32 == e2[0].Np32 && e2[2].KT == e2[1].KT && e2[2].Np32 == 2 * m->Dp[1] && d2[0].Kp32 == m->Dp[1] && d2[0].Np32 == e2[0].Np32 &&
-                    d2[1].KT == e2[1].KT && d2[1].Np32 == d2[0].Np32 && d2[2].KT == e2[1].KT && d2[2].Np32 == 2 * m->Dp[0];
-        }
-        if (fuse_z || sample_in_block) zin = s;
-        else if (!chain) launch_sample(s, st);
+        s.lq_dreg = p.want_dreg ? lqd : nullptr;
+        zin = s;
+        if (p.z_from == Z_SAMPLE) launch_sample(s, st);
     }
     if (two) {
         // ---- q(z2|z1), z2, p(z1|z2)  (iwae2.py:63-65, :90, :118-124)
@@ -1059,8 +1295,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         CHK(block_alloc(m, m->dec2, m->wdec2, M, Mp, bwd, true));
         // large row counts, the reference's dims: the z1 sampling, both per-sample blocks, the z2 sampling and the four log-densities in ONE launch
         const Linear *e2 = m->enc2, *d2 = m->dec2;
-        m->chain2_bwd = false;
-        if (chain) {
+        if (p.chain) {
             Chain2FwdArgs c;
             memset(&c, 0, sizeof(c));
             c.Z1P = ptr<uint16_t>(m->zP[0]); c.lqz1x = t3;
@@ -1069,8 +1304,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
             c.M = M; c.k = k; c.B = B; c.D0 = m->D[0]; c.D1 = m->D[1];
             // the backward pass reads the blocks' tanh activations; the float32 heads only where something still reads THEM: the unfused
             // backward kernels (gauss_bwd_kernel) and the z2 / snis exports -- gblock_bwd_kernel recomputes them from h2
-            m->chain2_bwd = bwd && m->allow_chain2_bwd && gblock_bwd_ok(e2[0].KT, e2[1].KT, d2[0].KT, M) && e2[0].imgB && d2[0].imgB;
-            const bool heads = want != nullptr || (bwd && !m->chain2_bwd);
+            const bool heads = want != nullptr || (bwd && !p.chain2_bwd);
             c.EH1 = bwd ? ptr<uint16_t>(m->wenc2.h1P) : nullptr; c.EH2 = bwd ? ptr<uint16_t>(m->wenc2.h2P) : nullptr;
             c.EHEAD = heads ? ptr<float>(m->wenc2.head) : nullptr;
             c.Z2P = ptr<uint16_t>(m->zP[1]);
@@ -1099,204 +1333,86 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         }
     }
 
-    // log_w / log-mean-exp arguments (lse_kernel, or the decoder kernel where it does that itself); allocates the outputs
-    LseArgs la;
-    auto lse_args = [&](LseArgs& a) -> int {
-        memset(&a, 0, sizeof(a));
-        CHK(ensure(m->logw, (size_t)Mp * 4, st));
-        CHK(ensure(m->wn, (size_t)Mp * 4, st));
-        {   // the row weights are also read 64 at a time by the output layer's weight gradient: pad rows must stay finite
-            const void* before = m->gx.p;
-            CHK(ensure(m->gx, (size_t)Mp * 4, st));
-            if (m->gx.p != before) HIPCHK(hipMemsetAsync(m->gx.p, 0, m->gx.cap, st));
-        }
-        CHK(ensure(m->cf, (size_t)Mp * 16, st));
-        CHK(ensure(m->per_b, (size_t)PB_COUNT * B * 4, st));
-        if (!two) {
-            a.term[0] = lpxz; a.coef[0] = 1.f;
-            a.term[1] = t1; a.coef[1] = beta;
-            a.term[2] = t2; a.coef[2] = -beta;
-            a.head = ptr<float>(m->wenc1.head); a.ldH = 2 * m->Dp[0]; a.D = m->D[0]; a.Dp = m->Dp[0];
-            a.cz_on = 1.f;
-        } else {
-            a.term[0] = lpxz; a.coef[0] = 1.f;    // iwae2.py:128 (beta unused there)
-            a.term[1] = t1; a.coef[1] = 1.f;
-            a.term[2] = t2; a.coef[2] = 1.f;
-            a.term[3] = t3; a.coef[3] = -1.f;
-            a.term[4] = t4; a.coef[4] = -1.f;
-            a.head = nullptr;
-            a.cz_on = 0.f;
-        }
-        a.lq_dreg = (!two && (objective == OBJ_DREG || (!bwd && !call.log_w_only))) ? lqd : nullptr;
-        a.B = B; a.k = k; a.beta = two ? 1.f : beta; a.objective = objective;
-        a.lme_only = (!bwd && call.log_w_only && !want) ? 1 : 0;
-        a.logw = ptr<float>(m->logw); a.wn = ptr<float>(m->wn); a.gx = ptr<float>(m->gx);
-        a.cf = ptr<float4>(m->cf); a.per_b = ptr<float>(m->per_b);
-        a.n_px_part = 1; a.px_stride = (size_t)Mp; a.term0_out = lpxz;
-        return IWAE_OK;
-    };
-
     // ---- decoder + Bernoulli log-likelihood (iwae1.py:81-83,111)
     MlpWs& w = m->wdec1;
     const int Hp = m->dec1[0].Np32;
     CHK(ensure(w.g1P, (size_t)Mp * Hp * 2, st));
     CHK(ensure(w.g2P, (size_t)Mp * Hp * 2, st));
     {
-        Linear& L = m->dec1[2];
-        DenseArgs a;
-        memset(&a, 0, sizeof(a));
-        a.X = ptr<uint16_t>(w.g2P); a.ldX = L.Kp32; a.img = L.imgF;
-        a.split = 1 << 30;
-        a.M = M; a.KT = L.KT; a.MG = L.MG; a.mg_per_block = L.MG; a.Np32 = L.Np32; a.g1_mask = m->dense_g1_mask;
-        // small row counts (the reference's default B = 20, k = 5): a handful of workgroups walking all 13 pixel groups
-        // in turn is 40 us of latency -- one pixel group per block instead, log p(x|z) as per-group partial sums that
-        // lse_kernel adds up in fixed order
-        m->px_parts = 1;
-        // few rows: the output layer runs inside block_fwd_kernel, behind the two tanh layers of the same 16-row tile (one launch for the
-        // whole decoder; log p(x|z) per row comes out whole, not as per-group partial sums)
-        const bool out_in_block = m->allow_block_fused && m->allow_out_in_block && !fuse_z && M <= 4096 && !(want && want->logits) && !m->want_stamps &&
-                                  m->dec1[1].Np32 == m->dec1[0].Np32 && m->dec1[1].Kp32 == m->dec1[0].Np32 && L.Kp32 == m->dec1[1].Np32 && L.KT == m->dec1[1].KT && L.KT <= 8;
-        if (M < 8192 && L.MG > 1 && !out_in_block) {
-            a.mg_per_block = 1;
-            m->px_parts = L.MG;
-            CHK(ensure(m->px_part, (size_t)L.MG * Mp * 4, st));
-        }
-        a.XB = ptr<uint16_t>(m->xP); a.ldXB = Xinp; a.k = k; a.B = B; a.Xdim = X;
-        a.lpxz = m->px_parts > 1 ? ptr<float>(m->px_part) : lpxz; a.lpxz_stride = m->px_parts > 1 ? (size_t)Mp : 0;
-        // training step: keep s = x - sigmoid(l) for the backward pass (out_bwd_s_kernel, output-layer weight gradient)
-        m->s_mode = bwd && m->allow_s_mode && out_bwd_has_s_mode(L.KT);
-        if (m->s_mode) {
+        DenseArgs a = p.bern;      // the plan's shapes; the buffers follow
+        a.X = ptr<uint16_t>(w.g2P);
+        if (p.px_parts > 1) CHK(ensure(m->px_part, (size_t)p.px_parts * Mp * 4, st));
+        a.XB = ptr<uint16_t>(m->xP);
+        a.lpxz = p.px_parts > 1 ? ptr<float>(m->px_part) : lpxz;
+        if (p.s_mode) {      // s = x - sigmoid(l) stays for the backward pass (out_bwd_s_kernel, output-layer weight gradient)
             CHK(ensure(m->wdec1.dlP, (size_t)Mp * Xp * 2, st));
-            a.YP = ptr<uint16_t>(m->wdec1.dlP); a.ldYP = Xp;
-            if (m->fake_s & 4) a.dbg = 32;
-            if (m->fake_s & 16) a.dbg |= 64;      // (the decoder kernel's tanh layers without their weight DMA)
-            if (m->fake_s & 32) a.dbg |= 128;     // (phase exits of the decoder kernel, for instruction counters: behind the prologue,
-            if (m->fake_s & 64) a.dbg |= 256;     //  behind both tanh layers,
-            if (m->fake_s & 128) a.dbg |= 512;    //  behind the first)
+            a.YP = ptr<uint16_t>(m->wdec1.dlP);
         }
         a.logits_out = nullptr;
-        a.pipe = m->allow_bern_pipe ? 1 : 0;
-        if (a.pipe && m->bern_qw) {      // the 16-wave / 200-row shape is one workgroup per CU: only where its last round is nearly full
-            const int nwg = (M + 199) / 200, ncu = std::max(1, m->num_cus);
-            const int rounds = (nwg + ncu - 1) / ncu;
-            if ((double)nwg >= 0.9 * (double)rounds * ncu || m->bern_qw_force) a.pipe = 2;
-        }
         if (want && want->logits) {
             CHK(ensure(m->scratch, (size_t)M * X * 4, st));
             a.logits_out = ptr<float>(m->scratch);
         }
-        // The whole decoder in one launch (bern_pipe_kernel<.., PRE>) where that kernel exists: the two tanh layers' activations
-        // stay in registers from layer to layer (z made in the kernel when the step runs on the device's noise).
-        bool fuse_dec = false;
-        if (m->allow_dec_fused && a.pipe && m->C == 0 && m->dec1[0].KT <= 4 && m->dec1[0].Kp32 == m->Dp[0] &&
-            m->dec1[0].Np32 == L.Kp32 && m->dec1[1].Kp32 == L.Kp32 && m->dec1[1].Np32 == L.Kp32) {
-            a.pre_img1 = m->dec1[0].imgF; a.pre_KT1 = m->dec1[0].KT; a.pre_img2 = m->dec1[1].imgF;
+        if (p.dec_fwd == DEC_PIPE) {      // the whole decoder in one launch
             a.pre_Z = ptr<uint16_t>(m->zP[0]);
             // g1, g2 are kept for the backward pass only: a forward-only call (val_step, the k = 5000 evaluator) never reads them back
             a.pre_G1 = (bwd && !(m->fake_s & 8)) ? ptr<uint16_t>(w.g1P) : nullptr; a.pre_G2 = (bwd && !(m->fake_s & 8)) ? ptr<uint16_t>(w.g2P) : nullptr;      // (fake_s & 8, DIAG builds: timing without the activation stores)
-            if (fuse_z) {
+            if (p.z_from == Z_DEC_PROLOGUE) {
                 a.zhead = zin.head; a.ldZH = zin.ldH; a.zeps = zin.eps.cache; a.zldE = zin.eps.ldC; a.zD = zin.D; a.zDp = zin.Dp;
                 a.ZPout = (bwd && !(m->fake_s & 8)) ? zin.ZP : nullptr; a.zlp = zin.lp_prior; a.zlq = zin.lq; a.zlq_dreg = zin.lq_dreg;      // (a forward-only call never reads z back)
             }
-            fuse_dec = bern_pipe_ok(a);
-            if (!fuse_dec) {
-                a.pre_img1 = a.pre_img2 = nullptr; a.pre_Z = nullptr; a.pre_G1 = a.pre_G2 = nullptr; a.pre_KT1 = 0;
-                a.zhead = nullptr; a.zeps = nullptr; a.ZPout = nullptr; a.zlp = a.zlq = nullptr; a.zlq_dreg = nullptr;
-            }
+        } else if (p.dec_fwd == DEC_DENSE) {
+            CHK(dense_fwd(m, m->dec1[0], EPI_TANH, ptr<uint16_t>(m->zP[0]), M, ptr<uint16_t>(w.g1P), nullptr, 0, p.z_from == Z_DENSE_ZIN ? &zin : nullptr));
+            CHK(dense_fwd(m, m->dec1[1], EPI_TANH, ptr<uint16_t>(w.g1P), M, ptr<uint16_t>(w.g2P), nullptr, 0));
+        } else {      // few rows: block_fwd_kernel on the two tanh layers, with z made in front and the output layer behind where the plan says so
+            BlockFwdArgs bf = p.dec_blk;
+            bf.X = ptr<uint16_t>(m->zP[0]); bf.H1 = ptr<uint16_t>(w.g1P); bf.H2 = ptr<uint16_t>(w.g2P);
+            if (p.z_from == Z_BLOCK) bf.S = zin;
+            if (p.dec_fwd == DEC_BLOCK_OUT) { bf.oXB = ptr<uint16_t>(m->xP); bf.oSP = p.s_mode ? ptr<uint16_t>(m->wdec1.dlP) : nullptr; bf.olpxz = lpxz; }
+            if (!block_fwd_ok(bf)) return fail(IWAE_ERR_STATE, "forward: the decoder's block_fwd_kernel launch lacks a buffer");
+            ScopedTimer tm(m, T_DEC_FWD);
+            launch_block_fwd(bf, st);
         }
-        if (fuse_z && zin.lq_dreg && !fuse_dec) { launch_sample(zin, st); fuse_z = false; }      // (dense_kernel's sampled-input mode has no DReG sum)
-        if (fuse_dec && sample_in_block) { launch_sample(zin, st); sample_in_block = false; }
-        bool out_done = false;
-        if (!fuse_dec) {
-            // few rows: the two tanh layers as ONE launch of block_fwd_kernel (a BasicBlock without its head: 16-row workgroups,
-            // weights straight from the L2-resident images) instead of two latency-bound dense_kernel launches
-            bool two_in_one = false;
-            if (m->allow_block_fused && !fuse_z && M <= 4096 && m->dec1[1].Np32 == m->dec1[0].Np32 && m->dec1[1].Kp32 == m->dec1[0].Np32) {
-                BlockFwdArgs bf;
-                memset(&bf, 0, sizeof(bf));
-                bf.X = ptr<uint16_t>(m->zP[0]); bf.ldX = m->dec1[0].Kp32; bf.img0 = m->dec1[0].imgF; bf.img1 = m->dec1[1].imgF; bf.img2 = m->dec1[1].imgF;
-                bf.KT0 = m->dec1[0].KT; bf.KT1 = m->dec1[1].KT; bf.NT1 = m->dec1[0].Np32 / 16; bf.NT2 = 0; bf.R = M;
-                bf.H1 = ptr<uint16_t>(w.g1P); bf.H2 = ptr<uint16_t>(w.g2P); bf.ldH = m->dec1[0].Np32;
-                bf.YF = nullptr; bf.ldYF = 0; bf.split = 1 << 30;
-                if (sample_in_block) { bf.sample = 1; bf.S = zin; }
-                if (out_in_block) {
-                    bf.oimg = L.imgF; bf.oXdim = X; bf.oH = L.Np32 >> 5; bf.oXB = ptr<uint16_t>(m->xP); bf.oldXB = Xinp; bf.ok = k;
-                    bf.oSP = m->s_mode ? ptr<uint16_t>(m->wdec1.dlP) : nullptr; bf.oldS = Xp; bf.olpxz = lpxz;
-                }
-                if (block_fwd_ok(bf)) {
-                    ScopedTimer tm(m, T_DEC_FWD);
-                    launch_block_fwd(bf, st); two_in_one = true; sample_in_block = false; out_done = out_in_block;
-                }
-            }
-            if (sample_in_block) { launch_sample(zin, st); sample_in_block = false; }      // (shapes the fused kernel does not cover)
-            if (!two_in_one) {
-                CHK(dense_fwd(m, m->dec1[0], EPI_TANH, ptr<uint16_t>(m->zP[0]), M, ptr<uint16_t>(w.g1P), nullptr, 0, fuse_z ? &zin : nullptr));
-                CHK(dense_fwd(m, m->dec1[1], EPI_TANH, ptr<uint16_t>(w.g1P), M, ptr<uint16_t>(w.g2P), nullptr, 0));
-            }
+        CHK(attach_dense_stamps(m, EPI_BERN, a));
+        CHK(lse_alloc(m));
+        if (p.lse_fused) {      // the decoder kernel does lse_kernel's work for its rows
+            lse_args(m, objective, bwd, want, a.lse);
+            // (the launch's guard, like block_fwd_ok above: the plan asked on shapes; the terms the prologue writes must be the ones lse_args names)
+            if (!bern_lse_ok(a)) return fail(IWAE_ERR_STATE, "forward: the decoder kernel's log-mean-exp terms are not the ones its prologue writes");
         }
-            CHK(attach_dense_stamps(m, EPI_BERN, a));
-            m->early_wout = bwd && m->s_mode && m->allow_early_wout && !dec_rows_step(m, M, B);      // (few data rows: no side-stream work in the backward pass at all)      // (round 3: the 2-layer model too -- its weight gradients are 220 us of kernels, on ONE side stream behind dec_bwd they ended 100 us after the main stream)
-            // Round 3: where the decoder kernel's workgroups own whole images (16-wave / 200-row shape, k a divisor of 200) it also does
-            // lse_kernel's work for them -- the backward pass starts right behind it: one launch (7 us) and one dispatch gap (6 us) less
-            // on the loop that sets the step, and no second lse_kernel on the side stream.
-            CHK(lse_args(la));
-            m->lse_fused = false;
-            if (!out_done && fuse_dec && m->allow_lse_fused && !m->want_stamps) {
-                a.lse = la; a.lse_on = 1;
-                if (bern_lse_ok(a)) m->lse_fused = true;
-                else { a.lse_on = 0; memset(&a.lse, 0, sizeof(a.lse)); }
-            }
-            // round 4: with the row weights made inside the decoder kernel, it also leaves g2w = bf16(g_r g2) -- the output layer's weight gradient
-            // (forked right behind this kernel) then needs no row weighting.  Needs a pad column in the hidden width for g_r itself (the bias gradient).
-            const bool g2w_now = m->lse_fused && m->early_wout && m->allow_g2w && m->s_mode && m->dec1[2].Kin < m->dec1[2].Kp32 && !two;
-            if (g2w_now) {
-                CHK(ensure(w.g2wP, (size_t)Mp * Hp * 2, st));
-                a.G2W = ptr<uint16_t>(w.g2wP); a.g2w_feat = m->dec1[2].Kin;
-            }
-            if (bwd && g2w_now != m->g2w) { m->g2w = g2w_now; m->descs_dirty = true; }      // (the layer table says where the output layer's bias sums are)
-            // s-mode training step: the output layer's weight gradient needs s, g2 and the row weights -- not out_bwd -- so the
-            // side stream forks early.  Round 2: it forks behind THIS kernel (event on its dispatch packet) and runs its own copy of
-            // lse_kernel (7 us, a few waves) for the row weights, instead of forking behind the main stream's lse_kernel: the ~12 us
-            // a cross-stream hand-off takes now pass beside the main stream's lse_kernel, not behind it.
-            m->lse_dup = m->early_wout && m->allow_lse_dup && m->px_parts == 1 && !out_done && !m->lse_fused;
-            const bool fork_here = m->lse_dup || (m->lse_fused && m->early_wout);
-            if (!out_done) { ScopedTimer tm(m, T_DEC_FWD); if (fork_here && !m->time_this) set_launch_stop_event(m->ev_lse); launch_dense(EPI_BERN, a, st); }
-            if (fork_here && m->time_this) HIPCHK(hipEventRecord(m->ev_lse, st));      // (a timed step: the timer's stop event sits behind the kernel)
+        if (p.g2w) {
+            CHK(ensure(w.g2wP, (size_t)Mp * Hp * 2, st));
+            a.G2W = ptr<uint16_t>(w.g2wP);
+        }
+        if (bwd && p.g2w != m->g2w_descs) m->descs_dirty = true;      // (the layer table says where the output layer's bias sums are)
+        // The side stream of an early output-layer weight gradient forks behind THIS kernel (event on its dispatch packet) where the row
+        // weights come from it or from the side stream's own copy of lse_kernel
+        const bool fork_here = p.lse_dup || (p.lse_fused && p.early_wout);
+        if (p.dec_fwd != DEC_BLOCK_OUT) { ScopedTimer tm(m, T_DEC_FWD); if (fork_here && !m->time_this) set_launch_stop_event(m->ev_lse); launch_dense(EPI_BERN, a, st); }
+        if (fork_here && m->time_this) HIPCHK(hipEventRecord(m->ev_lse, st));      // (a timed step: the timer's stop event sits behind the kernel)
         HIPCHK(hipGetLastError());
-        // The NEXT step's noise (speculating step + 1 with the same batch shape; the tag is checked on use): drawn now, on the side
-        // stream, idle until the backward pass forks -- enqueued behind the decoder kernel so that its dispatch does not delay that one
-        // (few rows, where the backward pass launches the decoder's weight gradients as one group on the SECOND side stream and `side` carries nothing
-        // that a later event would cover: the draw goes to that second stream, in front of the group and the decoder update whose event the next step waits for.
-        // Round 4 (advisor finding): the choice must follow what the backward pass will really use.  It touches `side2` only when the output layer's
-        // gradient forks early (early_wout, known here); without that -- hidden widths without a stored-s instantiation, options out_recompute /
-        // no_early_wout -- everything runs on `side`, the stream whose event the next step joins and which is re-ordered behind the main stream every
-        // step (the ring slot written here was last read by step t - 2's backward pass on the main stream).)
-        if (eps_multi) {      // the next GROUP of steps, once per group: into the buffer the current step does not read (main stream: this regime touches no other)
+        // The NEXT step's noise (speculating step + 1 with the same batch shape; the tag is checked on use): drawn now, on the stream the plan
+        // names (idle until the backward pass forks) -- enqueued behind the decoder kernel so that its dispatch does not delay that one
+        if (p.eps_multi) {      // the next GROUP of steps, once per group: into the buffer the current step does not read (main stream: this regime touches no other)
             if (epsm_find(m, m->noise_step + 1, M) < 0) CHK(draw_eps_multi(m, 1 - epsm_find(m, m->noise_step, M), m->noise_step + 1, M, st));
         } else
-        if (bwd && keep_eps && m->side)
-            CHK(draw_eps(m, (m->epsc_par + 1) % 3, m->noise_step + 1, M, eps_draw_stream(m, M), m->eps_blocks));
+        if (bwd && p.keep_eps && m->side)
+            CHK(draw_eps(m, (m->epsc_par + 1) % 3, m->noise_step + 1, M, on_stream(m, p.draw_on), m->opt.eps_blocks));
         if (want && want->logits) CHK(copy_out(m, want->logits, m->scratch.p, (size_t)M * X * 4));
     }
 
     // ---- log_w, log-mean-exp over k, objectives (iwae1.py:113-139)
-    {
-        LseArgs a = la;
-        if (m->px_parts > 1) a.term[0] = ptr<float>(m->px_part);
-        a.n_px_part = m->px_parts;
-        if (m->lse_fused) {      // the decoder kernel did it; the side stream (output layer's weight gradient) forks behind that kernel
-            if (m->early_wout) HIPCHK(hipStreamWaitEvent(m->side, m->ev_lse, 0));
-        } else {
+    if (p.lse_at == LSE_DECODER) {      // the decoder kernel did it; the side stream (output layer's weight gradient) forks behind that kernel
+        if (p.early_wout) HIPCHK(hipStreamWaitEvent(m->side, m->ev_lse, 0));
+    } else {
+        LseArgs a;
+        lse_args_parts(m, objective, bwd, want, a);
         // s-mode training step: the output layer's weight gradient needs s, g2 and the row weights lse_kernel leaves -- not
         // out_bwd -- so the side stream forks here (ev_lse on this kernel's dispatch packet), one kernel earlier, and the
         // gradient runs beside out_bwd (both read s)
-        // Few rows (round 4): the training step's log-mean-exp is done by the backward pass's first kernel (dec_bwd_rows_kernel, a wave per
-        // image in front of its own work): one dependent launch less on a chain of ~10 us launches
-        m->lse_pending = bwd && m->allow_lse_in_bwd && !m->lse_dup && !m->early_wout && dec_bwd_rows_planned(m, M);
-        if (m->lse_pending) m->lse_saved = a;
-        if (m->early_wout && !m->lse_dup) set_launch_stop_event(m->ev_lse);
-        if (!m->lse_pending) launch_lse(a, st);
-        if (m->lse_dup) {       // the side stream's copy: same inputs, its own outputs
+        if (p.early_wout && !p.lse_dup) set_launch_stop_event(m->ev_lse);
+        if (p.lse_at == LSE_FWD) launch_lse(a, st);      // (LSE_BWD_ROWS: the backward pass's first kernel does it)
+        if (p.lse_dup) {       // the side stream's copy: same inputs, its own outputs
             CHK(ensure(m->logw2, (size_t)Mp * 4, st));
             CHK(ensure(m->wn2, (size_t)Mp * 4, st));
             {
@@ -1312,10 +1428,9 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
             HIPCHK(hipStreamWaitEvent(m->side, m->ev_lse, 0));
             launch_lse(a2, m->side);
         }
-        }
-        // batch means: a training step folds them into its last kernel (backward_impl), a forward-only call takes them here
-        if (!bwd) launch_scalars(ptr<float>(m->per_b), B, two ? 1.f : beta, m->d_scalars, st);
     }
+    // batch means: a training step folds them into its last kernel (backward_impl), a forward-only call takes them here
+    if (!bwd) launch_scalars(ptr<float>(m->per_b), B, two ? 1.f : beta, m->d_scalars, st);
     HIPCHK(hipGetLastError());
     m->have_forward = true;
     m->fwd_was_f32 = false;
@@ -1335,17 +1450,32 @@ float adam_alpha(iwae_model* m, float lr) {      // keras Adam: lr_t = lr * sqrt
 int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool split = false, bool hold_early = false) {
     if (!m->have_forward) return fail(IWAE_ERR_STATE, "backward without forward");
     if (m->fwd_was_f32) return fail(IWAE_ERR_STATE, "the last forward ran in float32 mode");
+    const StepPlan& p = m->plan;
+    const StepOptions& o = m->opt;
     const bool two = m->cfg.n_layers == 2;
     const int B = m->B, k = m->k, M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X, Xp = m->Xp32;
-    hipStream_t st = m->stream;
+    // ---- the end of the step, from the plan and this call's own arguments (nothing further down decides anything)
+    const bool fuse = fused_lr >= 0.0f;
+    // the decoder's slab sums + Adam stay on the side stream and are NOT joined at the end of the step (join_side)
+    const bool defer = fuse && o.allow_defer && dec_layers_last(m) && !two && !p.dec_rows;      // (2-layer: the main stream needs the side-stream block gradients anyway)
+    // ... as one deferred update per side stream, each behind the weight gradients it carried (option defer_split)
+    const bool split_upd = defer && o.defer_split && p.hid_on == ON_SIDE2 && !p.group3 && p.early_wout;
+    // gradient only: the decoder's layers are summed into the flat gradient on the side stream, right behind their weight gradients
+    const bool early = !fuse && dec_layers_last(m) && !two && !p.dec_rows;
+    // 2-layer training step at large row counts (round 3): every layer behind the image encoder has its weight gradients on the side
+    // streams; their slab sums + Adam follow there, instead of the main stream waiting for both side streams and then summing all 94 MB itself
+    const bool defer2 = fuse && two && o.allow_defer && o.allow_defer2 && side_layers_from_enc2(m) && p.chain2_bwd && p.early_wout && o.use_side2 && !split;
+    // ... one update per side stream, each for the layers whose weight gradients IT carried
+    const bool defer2_split = defer2 && p.tail == ON_SIDE2 && o.allow_defer2_split && m->dec2[0].nsub == 1 && m->dec1[0].nsub == 1 && m->dec1[2].nsub == 1;
+    hipStream_t st = m->stream, tail = on_stream(m, p.tail);
     MlpWs& w = m->wdec1;
     const int Hp = m->dec1[0].Np32;
     CHK(ensure(w.dlP, (size_t)Mp * Xp * 2, st));
     CHK(ensure(w.d2P, (size_t)Mp * Hp * 2, st));
     CHK(ensure(w.d1P, (size_t)Mp * Hp * 2, st));
     CHK(ensure(w.dz, (size_t)Mp * m->Dp[0] * 4, st));
-    bool fused_dx = false, dz_half = false;
-    const bool dec_rows = dec_rows_step(m, M, B);      // the decoder's weight gradients ride in the encoder's wgrad_rows_kernel launch (few data rows)
+    const bool fused_dx = p.dx != DX_THREE;
+    const float* gx_out = ptr<float>(p.lse_dup ? m->gx2 : m->gx);      // the output layer's row weights on `side`: from the side stream's own lse_kernel where it ran one
     {
         Linear& L = m->dec1[2];
         OutBwdArgs a;
@@ -1355,10 +1485,9 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
         a.gx = ptr<float>(m->gx); a.XB = ptr<uint16_t>(m->xP); a.ldXB = m->Xinp; a.k = k;
         a.M = M; a.KT = L.KT; a.NG = L.MG;
         a.DPP = ptr<uint16_t>(w.d2P);
-        if (m->s_mode) a.SP = ptr<uint16_t>(w.dlP);     // dlP holds s: one product, no recompute
+        if (p.s_mode) a.SP = ptr<uint16_t>(w.dlP);     // dlP holds s: one product, no recompute
         if (m->fake_s & 1) a.dbg = 32;
-        const bool small_fused = m->small_dec_bwd && m->allow_dec_bwd && m->s_mode && M <= m->small_rows && out_bwd_has_s_mode(L.KT) && !m->want_stamps;      // dec_bwd_kernel at small row counts too
-        if (m->s_mode && M < 8192 && L.MG > 1 && !small_fused) {         // small row counts: one pixel group per block, partial sums + finish kernel
+        if (p.out_parts) {         // small row counts: one pixel group per block, partial sums + finish kernel
             a.gpb = 1;
             CHK(ensure(m->dg2_part, (size_t)L.MG * M * L.Kp32 * 4, st));
             a.part = ptr<float>(m->dg2_part);
@@ -1368,113 +1497,87 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
             CHK(ensure(m->stamps, (size_t)(Mp / 64) * 4 * 8 * 8, st));
             a.stamps = ptr<unsigned long long>(m->stamps);
         }
-            // One launch for out_bwd + dX of d2 + dX of d1 (dec_bwd_kernel) where it exists: large row counts, s kept by the forward
-            // pass, hidden width with an instantiation; dpre2 / dpre1 stay in registers from product to product.
-            fused_dx = m->allow_dec_bwd && m->s_mode && !a.part && (M >= 8192 || small_fused) && !a.stamps && L.kmajor && L.imgB && m->dec1[1].KT_B == L.KT && m->dec1[1].MG_B == (L.KT + 1) / 2 &&
-                       m->dec1[0].KT_B == L.KT && m->dec1[1].Kp32 == L.Kp32 && m->dec1[0].Np32 == L.Kp32;
-            bool rows_kernel = false;
-            if (fused_dx && M <= m->dec_rows_max && m->allow_block_fused && L.kmajor && L.imgB) {      // few rows: 16-row workgroups, weights straight from L2
-                DecBwdRowsArgs r;
-                memset(&r, 0, sizeof(r));
-                r.SP = ptr<uint16_t>(w.dlP); r.ldS = Xp; r.KTX = Xp / 32; r.imgK3 = L.imgB; r.MT3 = L.MT_B;
-                r.imgB2 = m->dec1[1].imgB; r.imgB1 = m->dec1[0].imgB; r.KT = L.KT; r.NT1 = L.Kp32 / 16; r.NT3 = m->dec1[0].Kp32 / 16; r.M = M;
-                r.G2 = ptr<uint16_t>(w.g2P); r.G1 = ptr<uint16_t>(w.g1P); r.ldH = L.Kp32; r.gx = ptr<float>(m->gx);
-                r.D2P = ptr<uint16_t>(w.d2P); r.D1P = ptr<uint16_t>(w.d1P); r.ldDZ = m->dec1[0].Kp32;
-                dz_half = !two && m->allow_dz_half;
-                r.DZ = ptr<float>(w.dz); r.DZH = dz_half ? (uint16_t*)w.dz.p : nullptr;
-                if (dec_bwd_rows_ok(r)) {
-                    if (m->lse_pending) { r.lse_on = 1; r.lse = m->lse_saved; m->lse_pending = false; }      // (forward_impl left the log-mean-exp to this kernel)
-                    ScopedTimer tm(m, T_DEC_BWD);
-                    if (!dec_rows) set_launch_stop_event(m->ev_fork2);
-                    launch_dec_bwd_rows(r, st);
-                    rows_kernel = true;
-                }
+        if (p.dx == DX_ROWS) {      // few rows: 16-row workgroups, weights straight from L2
+            DecBwdRowsArgs r = p.rows;
+            r.SP = ptr<uint16_t>(w.dlP); r.G2 = ptr<uint16_t>(w.g2P); r.G1 = ptr<uint16_t>(w.g1P); r.gx = ptr<float>(m->gx);
+            r.D2P = ptr<uint16_t>(w.d2P); r.D1P = ptr<uint16_t>(w.d1P);
+            r.DZ = ptr<float>(w.dz); r.DZH = p.dz_half ? (uint16_t*)w.dz.p : nullptr;
+            if (p.lse_at == LSE_BWD_ROWS) lse_args_parts(m, objective, true, nullptr, r.lse);      // (the forward pass left the log-mean-exp to this kernel)
+            ScopedTimer tm(m, T_DEC_BWD);
+            if (!p.dec_rows) set_launch_stop_event(m->ev_fork2);
+            launch_dec_bwd_rows(r, st);
+        } else if (p.dx == DX_DEC_BWD) {      // out_bwd + dX of d2 + dX of d1 in one launch
+            DecBwdArgs d;
+            memset(&d, 0, sizeof(d));
+            d.o = a;
+            d.imgB2 = m->dec1[1].imgB; d.G1 = ptr<uint16_t>(w.g1P); d.D1P = ptr<uint16_t>(w.d1P);
+            d.imgB1 = m->dec1[0].imgB; d.MG1 = m->dec1[0].MG_B; d.DZ = ptr<float>(w.dz); d.ldDZ = m->dec1[0].Kp32;
+            if (p.dz_half) d.DZH = (uint16_t*)w.dz.p;
+            d.nw = o.dec_bwd_nw;
+            if (m->dstamp_epi == 9) {      // diagnostic (STAMPS=1 build, option dense_stamps_epi = 9): phase stamps of dec_bwd_kernel
+                m->dstamp_waves = ((M + 127) / 128) * (L.KT == 7 ? o.dec_bwd_nw : 4);
+                CHK(ensure(m->dstamps, (size_t)m->dstamp_waves * 64, st));
+                d.o.stamps = ptr<unsigned long long>(m->dstamps);
             }
-            if (m->lse_pending) { launch_lse(m->lse_saved, st); m->lse_pending = false; }      // (the plan did not hold: lse_kernel after all, in front of everything that reads the row weights)
-            if (rows_kernel) {
-            } else if (fused_dx) {
-                DecBwdArgs d;
-                memset(&d, 0, sizeof(d));
-                d.o = a;
-                d.imgB2 = m->dec1[1].imgB; d.G1 = ptr<uint16_t>(w.g1P); d.D1P = ptr<uint16_t>(w.d1P);
-                d.imgB1 = m->dec1[0].imgB; d.MG1 = m->dec1[0].MG_B; d.DZ = ptr<float>(w.dz); d.ldDZ = m->dec1[0].Kp32;
-                // 1-layer model: dz has one reader (latent_bwd_kernel): bf16 halves its 26 MB each way (the 2-layer model adds two more
-                // float32 terms to it there and keeps float32)
-                dz_half = !two && m->allow_dz_half;
-                if (dz_half) d.DZH = (uint16_t*)w.dz.p;
-                d.nw = m->dec_bwd_nw;
-                if (m->dstamp_epi == 9) {      // diagnostic (STAMPS=1 build, option dense_stamps_epi = 9): phase stamps of dec_bwd_kernel
-                    m->dstamp_waves = ((M + 127) / 128) * (L.KT == 7 ? m->dec_bwd_nw : 4);
-                    CHK(ensure(m->dstamps, (size_t)m->dstamp_waves * 64, st));
-                    d.o.stamps = ptr<unsigned long long>(m->dstamps);
-                }
-                ScopedTimer tm(m, T_DEC_BWD);
-                if (!dec_rows) set_launch_stop_event(m->ev_fork2);          // dpre2, dpre1 and the last read of the decoder's weight images: one event
-                launch_dec_bwd(d, st);
-            } else {
+            ScopedTimer tm(m, T_DEC_BWD);
+            if (!p.dec_rows) set_launch_stop_event(m->ev_fork2);          // dpre2, dpre1 and the last read of the decoder's weight images: one event
+            launch_dec_bwd(d, st);
+        } else {
             // (forked behind lse_kernel already: the side stream then needs nothing from the main stream until dX of d1 is done)
-            { ScopedTimer tm(m, T_OUT_BWD); if (!m->early_wout) set_launch_stop_event(m->ev_fork); launch_out_bwd(a, st); }
-            }
+            { ScopedTimer tm(m, T_OUT_BWD); if (!p.early_wout) set_launch_stop_event(m->ev_fork); launch_out_bwd(a, st); }
+        }
         HIPCHK(hipGetLastError());
     }
     // fork: the decoder weight gradients only need what out_bwd produced (dl, dpre2) plus forward activations, so
     // they start on the side stream right behind it and fill the machine next to the dz -> encoder chain; the
     // first decoder layer's gradient additionally waits for dpre1 (second event).
     hipStream_t sd = m->side;
-    // Few rows (round 3): the decoder's three weight gradients as ONE grouped launch behind the dX chain (the B = 20 step is bound by the host's
-    // launches and the streams' hand-offs, not by these kernels: 13 -> 11 launches, two events less)
-    bool group3 = false, split_upd = false;
-    WgradPGroup g3;
-    if (!dec_rows && m->allow_wg3 && M <= 4096 && fused_dx && m->early_wout && m->use_side2 && m->s_mode) {
+    if (p.dec_rows) {
+        if (!fused_dx) {      // (the dX chain as three launches; their weight gradients follow in wgrad_rows_kernel, further down the main stream)
+            { ScopedTimer tm(m, T_DX_HID); CHK(dense_dx(m, m->dec1[1], ptr<uint16_t>(w.d2P), M, ptr<uint16_t>(w.g1P), ptr<uint16_t>(w.d1P), nullptr)); }
+            { ScopedTimer tm(m, T_DX_LAT); CHK(dense_dx(m, m->dec1[0], ptr<uint16_t>(w.d1P), M, nullptr, nullptr, ptr<float>(w.dz))); }
+        }
+    } else if (p.group3) {      // few rows: the decoder's three weight gradients as ONE grouped launch behind the dX chain
+        WgradPGroup g3;
         memset(&g3, 0, sizeof(g3));
         Linear* ls[3] = {&m->dec1[2], &m->dec1[1], &m->dec1[0]};
         const uint16_t* xs[3] = {ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.g1P), ptr<uint16_t>(m->zP[0])};
         const uint16_t* gs[3] = {ptr<uint16_t>(w.dlP), ptr<uint16_t>(w.d2P), ptr<uint16_t>(w.d1P)};
         int ns[3], nw[3];
-        group3 = true;
         for (int i = 0; i < 3; ++i) {
             CHK(wgradp_plan(m, *ls[i], xs[i], gs[i], M, g3.a[i], ns[i], nw[i]));
-            group3 = group3 && nw[i] == 8;
             g3.gx[i] = (ls[i]->JT + 7) / 8; g3.gy[i] = (ls[i]->IT + 15) / 16;
             g3.zbeg[i + 1] = g3.zbeg[i] + ns[i];
         }
         g3.n = 3;
         g3.a[0].rowscale = ptr<float>(m->gx);      // (the main stream's row weights: this group waits for ev_fork2, i.e. for the main stream -- never the side stream's copy)
-    }
-    if (dec_rows) {
-        if (!fused_dx) {      // (the dX chain as three launches; their weight gradients follow in wgrad_rows_kernel, further down the main stream)
-            { ScopedTimer tm(m, T_DX_HID); CHK(dense_dx(m, m->dec1[1], ptr<uint16_t>(w.d2P), M, ptr<uint16_t>(w.g1P), ptr<uint16_t>(w.d1P), nullptr)); }
-            { ScopedTimer tm(m, T_DX_LAT); CHK(dense_dx(m, m->dec1[0], ptr<uint16_t>(w.d1P), M, nullptr, nullptr, ptr<float>(w.dz))); }
-        }
-        m->tail = m->side;
-    } else if (group3) {
         HIPCHK(hipStreamWaitEvent(m->side2, m->ev_fork2, 0));
         { ScopedTimer tm(m, T_WGRAD_OUT, m->side2); launch_wgradp_group(g3, m->side2); }
         HIPCHK(hipGetLastError());
-        m->tail = m->side2;
     } else {
-    if (m->early_wout && (m->lse_dup || m->lse_fused)) {}                            // forked behind the decoder kernel already (forward_impl)
-    else if (m->early_wout) HIPCHK(hipStreamWaitEvent(m->side, m->ev_lse, 0));            // forked behind lse_kernel (forward_impl)
+    const bool wout_beside = p.early_wout && p.hid_on == ON_SIDE2;      // the output layer's gradient on `side`, the hidden layers' beside it on `side2`
+    if (p.early_wout && (p.lse_dup || p.lse_fused)) {}                            // forked behind the decoder kernel already (forward_impl)
+    else if (p.early_wout) HIPCHK(hipStreamWaitEvent(m->side, m->ev_lse, 0));            // forked behind lse_kernel (forward_impl)
     else HIPCHK(hipStreamWaitEvent(m->side, fused_dx ? m->ev_fork2 : m->ev_fork, 0));  // the event rode on out_bwd's / dec_bwd's dispatch packet
     {   // (its completion event ev_s2 rides on the dispatch packet: the stream that later picks `side` up waits ~8 us less than behind a record)
         ScopedTimer tm(m, T_WGRAD_OUT, sd);
-        const bool two_part = m->wout_split > 0 && m->s_mode && !m->g2w && m->early_wout && m->use_side2 && fused_dx && M >= 8192 && m->dec1[2].IT <= 14 && m->allow_wg7 && !(m->abl_skip & 1);
-        if (two_part) {
+        if (p.wout_two_part) {
             WgradPArgs a1, a2;
             int n1 = 1, n2 = 1;
-            CHK(wgradp_two_plan(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, ptr<float>(m->lse_dup ? m->gx2 : m->gx), a1, n1, a2, n2));
+            CHK(wgradp_two_plan(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, gx_out, a1, n1, a2, n2));
             launch_wgradp(a1, n1, 7, sd);
             HIPCHK(hipStreamWaitEvent(sd, m->ev_fork2, 0));      // (the late part starts behind dec_bwd_kernel, beside the hidden layers' gradients)
             set_launch_stop_event(m->ev_s2);
             launch_wgradp(a2, n2, 7, sd);
             HIPCHK(hipGetLastError());
-        } else
-        if (m->abl_skip & 1) { if (m->early_wout && m->use_side2) HIPCHK(hipEventRecord(m->ev_s2, sd)); }
-        else if (m->early_wout && m->use_side2) set_launch_stop_event(m->ev_s2);
-        if (two_part) {} else
-        if (m->abl_skip & 1) { WgradPArgs a0; int n0 = 1, w0 = 8; CHK(wgradp_plan(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, a0, n0, w0)); }      // (slabs allocated: the reduction still reads them)
-        else if (m->g2w) CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2wP), ptr<uint16_t>(w.dlP), M, sd, nullptr));      // (pre-weighted X operand: the unweighted kernel)
-        else CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, sd, m->s_mode ? ptr<float>(m->lse_dup ? m->gx2 : m->gx) : nullptr));
+        } else if (m->abl_skip & 1) {      // (DIAG builds, timing only: slabs allocated, the reduction still reads them)
+            if (wout_beside) HIPCHK(hipEventRecord(m->ev_s2, sd));
+            WgradPArgs a0; int n0 = 1, w0 = 8; CHK(wgradp_plan(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, a0, n0, w0));
+        } else {
+            if (wout_beside) set_launch_stop_event(m->ev_s2);
+            if (p.g2w) CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2wP), ptr<uint16_t>(w.dlP), M, sd, nullptr));      // (pre-weighted X operand: the unweighted kernel)
+            else CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, sd, p.s_mode ? gx_out : nullptr));
+        }
     }
     if (!fused_dx) {
         { ScopedTimer tm(m, T_DX_HID); CHK(dense_dx(m, m->dec1[1], ptr<uint16_t>(w.d2P), M, ptr<uint16_t>(w.g1P), ptr<uint16_t>(w.d1P), nullptr)); }
@@ -1485,24 +1588,18 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
     // decoder update further down the side stream must come after dX of d1, the last reader of the decoder's weight images.
     // Forked early, the side stream is busy with the output layer's gradient until after that: ONE wait then covers everything,
     // and out_bwd carries no event at all -- one bubble less on the main stream, one wait less on the side stream.
-    // The hidden layers' weight gradients need dpre2 / dpre1 (ev_fork2), not the output layer's gradient: forked early, that one
-    // keeps `side` busy well past the end of the dX chain, so they go to a second side stream and run beside it -- as ONE grouped
-    // launch where both take the specialised-wave shape.  They finish last, so that stream (`tail`) also carries what follows the
+    // The hidden layers' weight gradients go to the stream the plan names (p.hid_on: beside the output layer's on `side2`, or behind it) -- as
+    // ONE grouped launch where both take the specialised-wave shape.  They finish last, so that stream (`tail`) also carries what follows the
     // weight gradients (the decoder's slab reduction [+ exchange] + Adam): it picks up `side` (ev_s2, recorded behind the output
     // layer's gradient, long complete by then) instead of `side` picking up the later of the two.
-    hipStream_t ws = sd;
-    m->tail = sd;
-    if (m->early_wout && m->use_side2) {
-        HIPCHK(hipStreamWaitEvent(m->side2, m->ev_fork2, 0));
-        ws = m->side2;
-        m->tail = m->side2;
-    } else if (m->early_wout) HIPCHK(hipStreamWaitEvent(m->side, m->ev_fork2, 0));
+    hipStream_t ws = on_stream(m, p.hid_on);
+    if (p.early_wout) HIPCHK(hipStreamWaitEvent(ws, m->ev_fork2, 0));
     {
         WgradPArgs ah, al;
         int nsh = 1, nsl = 1, shh = 8, shl = 8;
         CHK(wgradp_plan(m, m->dec1[1], ptr<uint16_t>(w.g1P), ptr<uint16_t>(w.d2P), M, ah, nsh, shh));
         CHK(wgradp_plan(m, m->dec1[0], ptr<uint16_t>(m->zP[0]), ptr<uint16_t>(w.d1P), M, al, nsl, shl));
-        if (shh == 7 && shl == 7 && m->allow_wg_group && (m->early_wout || fused_dx)) {      // (both inputs ready: one launch)
+        if (p.hid_group) {
             WgradPGroup g;
             memset(&g, 0, sizeof(g));
             g.n = 2; g.a[0] = ah; g.a[1] = al;
@@ -1512,19 +1609,15 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
             launch_wgradws_group(g, ws);
         } else {
             if (!(m->abl_skip & 2)) { ScopedTimer tm(m, T_WGRAD_HID, ws); launch_wgradp(ah, nsh, shh, ws); }
-            if (!m->early_wout && !fused_dx) HIPCHK(hipStreamWaitEvent(m->side, m->ev_fork2, 0));
+            if (!p.early_wout && !fused_dx) HIPCHK(hipStreamWaitEvent(m->side, m->ev_fork2, 0));
             if (!(m->abl_skip & 2)) { ScopedTimer tm(m, T_WGRAD_LAT, ws); launch_wgradp(al, nsl, shl, ws); }
         }
         HIPCHK(hipGetLastError());
     }
-    if (m->defer_split && m->descs_dirty) CHK(build_descs(m));      // (early_first comes from the table)
-    split_upd = m->defer_split && fused_lr >= 0.0f && m->allow_defer && m->early_first > 0 && !two && ws == m->side2 && m->early_wout;
-    if (ws == m->side2 && !split_upd) HIPCHK(hipStreamWaitEvent(m->side2, m->ev_s2, 0));
+    if (p.hid_on == ON_SIDE2 && !split_upd) HIPCHK(hipStreamWaitEvent(m->side2, m->ev_s2, 0));
     }      // (!group3)
-    const bool fuse = fused_lr >= 0.0f;
     const float alpha = fuse ? adam_alpha(m, fused_lr) : 0.0f;
     if (m->descs_dirty) CHK(build_descs(m));
-    const bool defer = fuse && m->allow_defer && m->early_first > 0 && !two && !dec_rows;      // (2-layer: the main stream needs the side-stream block gradients anyway)
 
     const float* dz1 = ptr<float>(w.dz);
     const float *dz1_b = nullptr, *dz1_c = nullptr;
@@ -1532,7 +1625,7 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
     if (two) {
         // ---- p(z1|z2) head, dec2, q(z2|z1) head, enc2
         CHK(ensure(m->dzdir, (size_t)Mp * m->Dp[0] * 4, st));
-        if (m->chain2_bwd) {
+        if (p.chain2_bwd) {
             // one launch per block: the head recomputed from h2, its gradient, the block's dX chain (gblock_bwd_kernel); the second one
             // also sums the three terms of dz1 (bf16, in dzdir) -- latent_bwd_kernel reads that like the 1-layer step's dz
             GBlockBwdArgs gb;
@@ -1556,7 +1649,7 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
             set_launch_stop_event(m->ev_blk);
             launch_gblock_bwd(1, gb, st);
             // (the encode block's weight gradients on the second side stream, free by now: beside the decode block's, not behind them)
-            CHK(block_bwd(m, m->enc2, m->wenc2, ptr<uint16_t>(m->zP[0]), M, false, true, true, (m->early_wout && m->use_side2) ? m->side2 : nullptr));
+            CHK(block_bwd(m, m->enc2, m->wenc2, ptr<uint16_t>(m->zP[0]), M, false, true, true, p.hid_on == ON_SIDE2 ? m->side2 : nullptr));
             HIPCHK(hipGetLastError());
             dz1 = nullptr; dz_sum_half = true;
         } else {
@@ -1582,12 +1675,11 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
         }
     }
     LatentBwdArgs lat_args;
-    bool lat_fuse = false;
     {
         LatentBwdArgs a;
         memset(&a, 0, sizeof(a));
         a.dz = dz1; a.dz2 = dz1_b; a.dz3 = dz1_c; a.ldDZ = m->Dp[0];
-        if (dz_half) a.dzh = (const uint16_t*)w.dz.p;
+        if (p.dz_half) a.dzh = (const uint16_t*)w.dz.p;
         if (dz_sum_half) a.dzh = (const uint16_t*)m->dzdir.p;
         a.head = ptr<float>(m->wenc1.head); a.ldH = 2 * m->Dp[0]; a.D = m->D[0]; a.Dp = m->Dp[0];
         a.cf = ptr<float4>(m->cf); a.eps = eps_src(m, 0);
@@ -1595,44 +1687,22 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
         a.kmu = a.ksig = (objective == OBJ_VAE_ELBO_KL) ? m->beta / (float)B : 0.f;
         a.DHP = ptr<uint16_t>(m->wenc1.dheadP);
         if (m->has_prior) { a.prior_head = ptr<float>(m->wprior.head); a.DHP2 = ptr<uint16_t>(m->wprior.dheadP); }
-        // Few images and samples (round 4): these per-image sums are made inside the encoder's block_bwd_kernel (a wave per image in front of
-        // its dX chain) -- one dependent launch less; the separate kernel (256 threads per image) stays for many samples per image
         lat_args = a;
-        // (measured, end-to-end us per step with / without: B = 20, k = 1: 67.7 / 70.0; B = 20, k = 5: 67.5 / 69.3; B = 100, k = 5: 72.1 / 73.4; B = 20, k = 50: 88.2 / 78.5 --
-        // one wave walking 50 samples is slower than latent_bwd_kernel's 256 threads: up to 16 samples per image)
-        // (round 5, option lat_rows4: beyond 16 samples per image block_bwd_kernel<4> -- 4 images per workgroup, an image's samples over four waves --
-        // can take the sums on 4 x the workgroups; measured no faster than the two launches in the step, see allow_lat_rows4)
-        lat_fuse = m->allow_lat_in_block && !m->has_prior && B <= 1024 && (k <= 16 || (m->allow_lat_rows4 && B >= 64)) && m->allow_block_fused;
-        if (!lat_fuse && !(m->abl_skip & 8)) { ScopedTimer tm(m, T_LATENT_BWD); launch_latent_bwd(a, st); }
+        // (few images and samples: the encoder's block_bwd_kernel makes these sums itself, below)
+        if (!p.lat_fuse && !(m->abl_skip & 8)) { ScopedTimer tm(m, T_LATENT_BWD); launch_latent_bwd(a, st); }
     }
     if (m->has_prior) CHK(block_bwd(m, m->prior, m->wprior, ptr<uint16_t>(m->condP), B, false, false));
-    // Round 4: on few rows the image encoder's weight gradients, their sum over ALL rows and (fused step) the Adam update are one launch
-    // (wgrad_rows_kernel) -- the encoder's layers (the head of the table) then need no slabs and no share of reduce_grads_kernel
-    const bool rows_enc = wgrad_rows_ok(m, m->enc1, B);
-    if (lat_fuse) {
-        bool taken = false;
-        CHK(block_bwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, false, false, false, nullptr, rows_enc, &lat_args, &taken));
-        if (!taken) {      // (shapes block_bwd_kernel does not cover: the separate kernel after all, then the block's backward pass)
-            { ScopedTimer tm(m, T_LATENT_BWD); launch_latent_bwd(lat_args, st); }
-            CHK(block_bwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, false, false, false, nullptr, rows_enc));
-        }
-    } else
-    CHK(block_bwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, false, false, false, nullptr, rows_enc));
+    CHK(block_bwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, false, false, false, nullptr, p.rows_enc, p.lat_fuse ? &lat_args : nullptr));
     if (m->descs_dirty) CHK(build_descs(m));      // (the encoder's splits were planned after the first build)
     const int enc_end = m->enc1[2].sub[m->enc1[2].nsub - 1] + 1;      // first table entry behind the image encoder's layers
-    const int rb_lo = !rows_enc ? 0 : enc_end < (int)m->descs.size() ? m->descs[enc_end].rblock_begin : m->reduce_blocks;
+    const int rb_lo = !p.rows_enc ? 0 : enc_end < (int)m->descs.size() ? m->descs[enc_end].rblock_begin : m->reduce_blocks;
     // split (data-parallel step, iwae_forward_backward_split): the decoder's layers are summed into the flat gradient on the
     // side stream, right behind their weight gradients, and NOT joined here -- the caller's all-reduce of that segment is
     // ordered behind the side stream and runs beside the encoder's backward pass; join_side() (every later entry point) joins.
     // Without split (iwae_forward_backward: gradient only, e.g. the one-message data-parallel step) the same early decoder
     // reduction runs on the side stream and the main stream joins it behind its own, shorter, encoder reduction.
-    const bool early = !fuse && m->early_first > 0 && !two && !dec_rows;
-    // 2-layer training step at large row counts (round 3): every layer behind the image encoder has its weight gradients on the side
-    // streams; their slab sums + Adam follow there (one launch on `tail`, which picks `side` up), instead of the main stream waiting for
-    // both side streams and then summing all 94 MB itself.  The next forward joins in front of z1 (join_side).  The image rewrite is safe
-    // for the same reason as in the 1-layer step: the side streams' weight gradients wait for the events behind the dX chains
-    // (ev_fork2, ev_blk), the last readers of those images.
-    const bool defer2 = fuse && two && m->allow_defer && m->allow_defer2 && m->early_first2 > 0 && m->chain2_bwd && m->early_wout && m->use_side2 && !split;
+    // (2-layer deferred update: the next forward joins in front of z1 (join_side).  The image rewrite is safe for the same reason as in the 1-layer
+    // step: the side streams' weight gradients wait for the events behind the dX chains (ev_fork2, ev_blk), the last readers of those images.)
     m->split_offset = m->nparam;
     m->early_held = false;
     if (early) {
@@ -1640,38 +1710,38 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
         else {
         set_launch_stop_event(m->ev_dec);
         launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                            m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, m->tail);
+                            m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, tail);
         }
         m->dec_pending = true;
         if (split) m->split_offset = m->descs[m->dec1[0].sub[0]].offW;
     } else if (defer2) {       // (the side streams' layers are summed and updated there, further down: nothing to join)
-    } else if (dec_rows) {     // (nothing ran on a side stream)
+    } else if (p.dec_rows) {     // (nothing ran on a side stream)
     } else if (!defer) {       // join: every weight gradient launched on the side stream is in its slabs
-        HIPCHK(hipEventRecord(m->ev_join, m->tail));
+        HIPCHK(hipEventRecord(m->ev_join, tail));
         HIPCHK(hipStreamWaitEvent(st, m->ev_join, 0));
-        if (two && m->tail != m->side) {      // the per-sample blocks' weight gradients went to `side` behind the output layer's: both side streams join
+        if (two && tail != m->side) {      // the per-sample blocks' weight gradients went to `side` behind the output layer's: both side streams join
             HIPCHK(hipEventRecord(m->ev_join2, m->side));
             HIPCHK(hipStreamWaitEvent(st, m->ev_join2, 0));
         }
     }
     {
         // the main stream's share of the table: [rb_lo, rb_hi) -- empty when wgrad_rows_kernel took the encoder and everything else is
-        // deferred to the side streams (the full-size 1- and 2-layer steps) or rode in the same launch (few data rows: dec_rows); that
+        // deferred to the side streams (the full-size 1- and 2-layer steps) or rode in the same launch (few data rows: p.dec_rows); that
         // kernel's extra block makes the batch means whenever it runs
         const int rb_hi = (defer || early) ? m->early_first : defer2 ? m->early_first2 : m->reduce_blocks;
-        const int rb_d0 = dec_rows ? m->descs[m->dec1[0].sub[0]].rblock_begin : rb_hi;        // (dec_rows: the decoder's three layers drop out of the range)
+        const int rb_d0 = p.dec_rows ? m->descs[m->dec1[0].sub[0]].rblock_begin : rb_hi;        // (p.dec_rows: the decoder's three layers drop out of the range)
         const int d_end = m->dec1[2].sub[0] + 1;
-        const int rb_d1 = !dec_rows ? rb_hi : d_end < (int)m->descs.size() ? m->descs[d_end].rblock_begin : m->reduce_blocks;
+        const int rb_d1 = !p.dec_rows ? rb_hi : d_end < (int)m->descs.size() ? m->descs[d_end].rblock_begin : m->reduce_blocks;
         ScopedTimer tm_red(m, T_REDUCE);
-        if (rows_enc) CHK(block_wgrad_rows(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, alpha, fuse, true, dec_rows));
+        if (p.rows_enc) CHK(block_wgrad_rows(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, alpha, fuse, true, p.dec_rows));
         const int n1 = std::max(0, std::min(rb_d0, rb_hi) - rb_lo), n2 = std::max(0, rb_hi - rb_d1);
-        if (!rows_enc || n1 + n2 > 0)
+        if (!p.rows_enc || n1 + n2 > 0)
             launch_reduce_grads(m->d_descs, (int)m->descs.size(), rb_lo, n1, m->grad, m->param, m->mom, m->vel,
-                                alpha, m->adam_b1, m->adam_b2, m->adam_eps, fuse ? 1 : 0, rows_enc ? nullptr : ptr<float>(m->per_b), B, two ? 1.f : m->beta, m->d_scalars, st,
+                                alpha, m->adam_b1, m->adam_b2, m->adam_eps, fuse ? 1 : 0, p.rows_enc ? nullptr : ptr<float>(m->per_b), B, two ? 1.f : m->beta, m->d_scalars, st,
                                 rb_d1, n2);
     }
     if (early && !split) CHK(join_side(m));
-    if (defer2 && m->tail == m->side2 && m->tail != m->side && m->allow_defer2_split && m->dec2[0].nsub == 1 && m->dec1[0].nsub == 1 && m->dec1[2].nsub == 1) {
+    if (defer2_split) {
         // each side stream sums and updates the layers whose weight gradients IT carried, as soon as its own chain ends: the second one the
         // encode block q(z2|z1) and the decoder's two tanh layers, the first one the decode block p(z1|z2) and the output layer (two block
         // ranges per launch: table order enc2 | dec2 | dec1).  The next forward waits for both events (join_side).
@@ -1684,16 +1754,16 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
                             m->adam_eps, 1, nullptr, 0, 0.f, nullptr, m->side, b_out, m->reduce_blocks - b_out);
         m->dec_pending = true; m->dec2_pending = true;
     } else if (defer2) {
-        if (m->tail != m->side) {
+        if (tail != m->side) {
             HIPCHK(hipEventRecord(m->ev_join2, m->side));
-            HIPCHK(hipStreamWaitEvent(m->tail, m->ev_join2, 0));
+            HIPCHK(hipStreamWaitEvent(tail, m->ev_join2, 0));
         }
         set_launch_stop_event(m->ev_dec);
         launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first2, m->reduce_blocks - m->early_first2, m->grad, m->param, m->mom,
-                            m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, m->tail);
+                            m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, tail);
         m->dec_pending = true;
     }
-    if (defer && split_upd && m->early_first > 0) {
+    if (split_upd) {
         // Round 5: one deferred update per side stream, each behind the weight gradients it carried -- no hand-off between the two side
         // streams in front of the update, and the output layer's share (54 % of the decoder's slabs) is done ~20 us before the hidden layers'
         // gradients end.  The output layer's gradient forked behind the decoder FORWARD: its update rewrites the W3 image dec_bwd_kernel
@@ -1712,11 +1782,11 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
         // (which wait for ev_fork2, i.e. for dX of d1, the last reader of the decoder's weight images -- without that order
         // the trajectory test caught a stale-image race), joined by the next user of the decoder (join_side): it runs beside
         // the encoder's backward pass / update and the next step's encoder forward.
-        if (m->abl_skip & 4) HIPCHK(hipEventRecord(m->ev_dec, m->tail));
+        if (m->abl_skip & 4) HIPCHK(hipEventRecord(m->ev_dec, tail));
         else {
         set_launch_stop_event(m->ev_dec);
         launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                            m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, m->tail);
+                            m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, tail);
         }
         m->dec_pending = true;
     }
@@ -1819,11 +1889,11 @@ int f32_gemm(iwae_model* m, const float* A, long sam, long sak, const float* B, 
         hipStream_t s_ = st ? st : m->stream;
         // (no_ksplit, iwae_eval_llh: the split depends on how many images a launch holds, and an image's estimate must not -- the evaluator's
         // encoder is 419 rows beside 2^21 decoder rows, nothing to gain there: test_eval_llh_images_per_launch_are_invisible)
-        const int ns = no_ksplit ? 1 : gemm_f32_fewrows_split(m->gemm_f32, M, N, K);
+        const int ns = no_ksplit ? 1 : gemm_f32_fewrows_split(m->opt.gemm_f32, M, N, K);
         if (ns > 1 && !brow_scale) {
             a.avec = a.bvec = 0;
             CHK(ensure(m->f32.kslab, (size_t)ns * M * N * 4, s_));
-            launch_gemm_f32_fewrows(m->gemm_f32, a, ptr<float>(m->f32.kslab), s_);
+            launch_gemm_f32_fewrows(m->opt.gemm_f32, a, ptr<float>(m->f32.kslab), s_);
             HIPCHK(hipGetLastError());
             return IWAE_OK;
         }
@@ -1835,7 +1905,7 @@ int f32_gemm(iwae_model* m, const float* A, long sam, long sak, const float* B, 
         a.stamps = ptr<unsigned long long>(m->dstamps);
     }
 #endif
-    launch_gemm_f32(m->gemm_f32, a, 1, st ? st : m->stream);
+    launch_gemm_f32(m->opt.gemm_f32, a, 1, st ? st : m->stream);
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
@@ -1877,15 +1947,15 @@ int f32_flush_reductions(iwae_model* m, int seg = -1) {
 int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const float* G, long ldg, int rows, const float* rowscale = nullptr, int seg = 0, int tile_mode = 0) {
     hipStream_t st = seg == 1 ? m->side : m->stream;
     // row splits: enough workgroups to fill the machine (~1 000 tiles of 64 x 64 or 128 x 128), at least 64 rows per split
-    const int tiles = (int)gemm_f32_tiles(m->gemm_f32, kl.Kin + 1, kl.Nout, tile_mode);      // (+ 1: the row of ones whose product row is the bias gradient)
-    const int slots = std::min(m->f32_dw_tiles, gemm_f32_slots(m->gemm_f32, kl.Kin + 1, kl.Nout, tile_mode));
-    int nsplit = std::max(1, std::min(std::min(256, rows / m->f32_dw_min_rows), slots / tiles));      // (rounded DOWN: 1 027 workgroups on 1 024 slots are a second round of 3)
+    const int tiles = (int)gemm_f32_tiles(m->opt.gemm_f32, kl.Kin + 1, kl.Nout, tile_mode);      // (+ 1: the row of ones whose product row is the bias gradient)
+    const int slots = std::min(m->opt.f32_dw_tiles, gemm_f32_slots(m->opt.gemm_f32, kl.Kin + 1, kl.Nout, tile_mode));
+    int nsplit = std::max(1, std::min(std::min(256, rows / m->opt.f32_dw_min_rows), slots / tiles));      // (rounded DOWN: 1 027 workgroups on 1 024 slots are a second round of 3)
     while (nsplit > 8 && (tiles * nsplit) % 8 != 0) --nsplit;      // (a multiple of 8 workgroups: gemm_f32_v2_kernel then keeps a split's tiles on one XCD)
     const size_t nW = (size_t)kl.Kin * kl.Nout;
     // (round 5: the slabs of every gradient of the step stay until ONE reduction launch at the end of the backward pass; the buffer is sized for a
     // whole step -- a step that outgrows it falls back to the reduction per tensor, and the buffer grows for the next step)
     const size_t need = ((size_t)nsplit * (nW + kl.Nout) + 3) & ~(size_t)3;      // (a multiple of 4 floats: the next gradient's slabs stay 16-byte aligned)
-    const bool queue = m->allow_f32_multi_reduce && nsplit > 1 && (m->f32_slab_used + need) * 4 <= m->f32.slab.cap && m->f32_pending.size() + 2 <= REDUCE_SLABS_MAX_JOBS;
+    const bool queue = m->opt.allow_f32_multi_reduce && nsplit > 1 && (m->f32_slab_used + need) * 4 <= m->f32.slab.cap && m->f32_pending.size() + 2 <= REDUCE_SLABS_MAX_JOBS;
     if (!queue) {
         if (!m->f32_pending.empty()) CHK(f32_flush_reductions(m));      // (queued jobs still read the buffer ensure() may replace)
         if (m->f32_side_active) { HIPCHK(hipStreamSynchronize(m->side)); HIPCHK(hipStreamSynchronize(m->stream)); }      // (first steps only: the buffer is still growing)
@@ -1903,7 +1973,7 @@ int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const 
     // the bias gradient = the column sums of (weighted) G = the product row of a row of ONES appended to X^T (GemmF32Args.Cones): no pass of its own
     if (ns == 1) {
         a.C = m->grad + kl.offW; a.ldc = kl.Nout; a.slab_stride = 0; a.Cones = m->grad + kl.offb; a.cones_stride = 0;
-        launch_gemm_f32(m->gemm_f32, a, 1, st);
+        launch_gemm_f32(m->opt.gemm_f32, a, 1, st);
     } else {
         a.C = slabW; a.ldc = kl.Nout; a.slab_stride = nW; a.Cones = slabB; a.cones_stride = (size_t)kl.Nout;
 #ifdef IWAE_DENSE_STAMPS
@@ -1913,7 +1983,7 @@ int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const 
             a.stamps = ptr<unsigned long long>(m->dstamps);
         }
 #endif
-        launch_gemm_f32(m->gemm_f32, a, ns, st);
+        launch_gemm_f32(m->opt.gemm_f32, a, ns, st);
         if (queue) {
             m->f32_pending.push_back({(size_t)(slabW - ptr<float>(m->f32.slab)), nW, nW, m->grad + kl.offW, ns, seg});
             m->f32_pending.push_back({(size_t)(slabB - ptr<float>(m->f32.slab)), (size_t)kl.Nout, (size_t)kl.Nout, m->grad + kl.offb, ns, seg});
@@ -2065,13 +2135,14 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
     df.XB = xd; df.k = k; df.lpxz = lpxz; df.zero = m->d_zero; df.ldg = H; df.ldS = X;
     // (round 5: a TRAINING step takes the three GEMM launches again -- with gemm_f32_v2_kernel they are faster than the fused kernel once g1, g2 and s
     // have to be stored anyway: 1.280 -> 1.248 ms; option f32_dec_fused_train = 1 for the fused kernel)
-    const bool fused_dec = m->allow_f32_dec_fused && (!bwd || m->f32_dec_fused_train) && !(want && want->logits) && M >= 4096 && dec_fwd_f32_ok(df);
+    int px_parts = 1;      // > 1: log p(x|z) arrives in px_part as that many partial sums per row
+    const bool fused_dec = m->opt.allow_f32_dec_fused && (!bwd || m->opt.f32_dec_fused_train) && !(want && want->logits) && M >= 4096 && dec_fwd_f32_ok(df);
     if (bwd || !fused_dec) {
         CHK(ensure(m->f32.g1, (size_t)M * H * 4, st));
         CHK(ensure(m->f32.g2, (size_t)M * H * 4, st));
     }
     if (fused_dec) {
-        m->px_parts = 1;
+        px_parts = 1;
         m->f32_keeps_s = false;
         if (bwd) {
             CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
@@ -2093,12 +2164,12 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
     // logits (1.6 GB per launch of 2^19 rows) are neither written nor read back; per 64-column half tile a partial sum that lse_kernel adds
     // Round 3, training step: the same epilogue also leaves s = x - sigmoid(l) where the logits would have gone -- the backward pass reads s and
     // takes the row weight g_r inside its two consumers (f32_dw / f32_dx with rowscale) instead of a pass that rewrites 160 MB into dl = g_r s.
-    const bool fuse_bern = m->allow_f32_bern_fused && !(want && want->logits) && gemm_f32_takes_big(M, X, 1);
-    m->px_parts = 1;
+    const bool fuse_bern = m->opt.allow_f32_bern_fused && !(want && want->logits) && gemm_f32_takes_big(M, X, 1);
+    px_parts = 1;
     m->f32_keeps_s = false;
     if (fuse_bern) {
-        m->px_parts = 2 * ((X + 127) / 128);
-        CHK(ensure(m->px_part, (size_t)m->px_parts * Mp * 4, st));
+        px_parts = 2 * ((X + 127) / 128);
+        CHK(ensure(m->px_part, (size_t)px_parts * Mp * 4, st));
         GemmF32Args ga;
         memset(&ga, 0, sizeof(ga));
         ga.A = ptr<float>(m->f32.g2); ga.sam = H; ga.sak = 1; ga.B = m->param + d3->offW; ga.sbk = d3->Nout; ga.sbn = 1; ga.M = M; ga.N = X; ga.K = H;
@@ -2109,7 +2180,7 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
             m->f32_keeps_s = true;
         }
         ga.XB = xd; ga.bern_k = k; ga.bern_X = X; ga.part = ptr<float>(m->px_part); ga.part_stride = (size_t)Mp;
-        launch_gemm_f32(m->gemm_f32, ga, 1, st);
+        launch_gemm_f32(m->opt.gemm_f32, ga, 1, st);
     } else {
     CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
     CHK(f32_fwd(m, *d3, ptr<float>(m->f32.g2), H, M, ptr<float>(m->f32.logits), X, GEMM_EPI_NONE, nks));
@@ -2146,8 +2217,8 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
         a.lme_only = (!bwd && call.log_w_only && !want) ? 1 : 0;
         a.logw = ptr<float>(m->logw); a.wn = ptr<float>(m->wn); a.gx = ptr<float>(m->gx);
         a.cf = ptr<float4>(m->cf); a.per_b = ptr<float>(m->per_b);
-        a.n_px_part = m->px_parts; a.px_stride = (size_t)Mp; a.term0_out = lpxz;
-        if (m->px_parts > 1) a.term[0] = ptr<float>(m->px_part);      // (the fused Bernoulli epilogue's per-half-tile partial sums)
+        a.n_px_part = px_parts; a.px_stride = (size_t)Mp; a.term0_out = lpxz;
+        if (px_parts > 1) a.term[0] = ptr<float>(m->px_part);      // (the fused Bernoulli epilogue's per-half-tile partial sums)
         launch_lse(a, st);
         launch_scalars(ptr<float>(m->per_b), B, two ? 1.f : beta, m->d_scalars, st);
     }
@@ -2182,14 +2253,14 @@ int backward_f32(iwae_model* m, int objective, float fused_lr = -1.0f) {
     CHK(ensure(m->wdec1.dz, (size_t)Mp * Dp0 * 4, st));
     if (m->descs_dirty) CHK(build_descs(m));
     // (the conditional prior's block sits BEHIND the decoder in the flat parameters: its gradient is made on the main stream -- one stream for that model)
-    const bool use_side = m->allow_f32_side && m->side && !m->has_prior && M >= 4096 && b_dec1 + 3 == (int)m->klayers.size();
+    const bool use_side = m->opt.allow_f32_side && m->side && !m->has_prior && M >= 4096 && b_dec1 + 3 == (int)m->klayers.size();
     m->f32_side_active = use_side;
     const int sg = use_side ? 1 : 0;
-    const bool dw_last = use_side && m->f32_dw_last > 0;      // option: every decoder weight gradient behind the dX chain, beside the main stream's few-row tail
+    const bool dw_last = use_side && m->opt.f32_dw_last > 0;      // option: every decoder weight gradient behind the dX chain, beside the main stream's few-row tail
     if (use_side) {
         HIPCHK(hipEventRecord(m->ev_fork, st));      // s, g1, g2, z, the row weights
         HIPCHK(hipStreamWaitEvent(m->side, m->ev_fork, 0));
-        if (m->f32_wout_first && !dw_last) CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw, 1));
+        if (m->opt.f32_wout_first && !dw_last) CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw, 1));
     } else {
         CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw));
     }
@@ -2201,11 +2272,11 @@ int backward_f32(iwae_model* m, int objective, float fused_lr = -1.0f) {
     if (!dw_last) {
         CHK(f32_dw(m, *d1, ptr<float>(m->f32.z[0]), D0 + m->C, ptr<float>(m->f32.d1), H, M, nullptr, sg));
         if (use_side) { HIPCHK(hipEventRecord(m->ev_join, m->side)); m->f32_z_pending = true; }      // (z is free for the next step's sampling)
-        if (use_side && !m->f32_wout_first) CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw, 1));
+        if (use_side && !m->opt.f32_wout_first) CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw, 1));
     }
     CHK(f32_dx(m, *d1, ptr<float>(m->f32.d1), H, M, ptr<float>(m->wdec1.dz), Dp0, nullptr, 0, false));
     if (dw_last) {
-        const int tmode = m->f32_dw_last - 1;      // (1: tiles as picked, 2: 4-wave tiles, 3: 4-wave tiles at 3 waves per SIMD)
+        const int tmode = m->opt.f32_dw_last - 1;      // (1: tiles as picked, 2: 4-wave tiles, 3: 4-wave tiles at 3 waves per SIMD)
         HIPCHK(hipEventRecord(m->ev_blk, st));
         HIPCHK(hipStreamWaitEvent(m->side, m->ev_blk, 0));
         CHK(f32_dw(m, *d1, ptr<float>(m->f32.z[0]), D0 + m->C, ptr<float>(m->f32.d1), H, M, nullptr, 1, tmode));
@@ -2299,8 +2370,8 @@ int dp_finish(iwae_model* m, float lr) {
     const size_t n = m->nparam, off = m->split_offset;
     if (m->early_held && !(off < n && m->dec_pending)) {      // (cannot happen on today's call paths -- nothing joins between backward_impl and here --; kept correct anyway: the held reduction runs now, joined)
         launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                            m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, m->tail);
-        HIPCHK(hipEventRecord(m->ev_join, m->tail));
+                            m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, on_stream(m, m->plan.tail));
+        HIPCHK(hipEventRecord(m->ev_join, on_stream(m, m->plan.tail)));
         HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
         m->early_held = false;
     }
@@ -2318,18 +2389,18 @@ int dp_finish(iwae_model* m, float lr) {
         // which backward_impl left to this function (early_held) -- i.e. right behind the wait for the output layer's gradient it performs
         // there anyway, ~15 us before the decoder's exchange instead of directly in front of it (a barrier packet costs its 6-10 us wherever
         // its event stands; here it falls into the shadow of the hidden layers' gradients).  Measured in the one-rank rehearsal: see DESIGN.md 8.
-        if (!m->dp_concurrent) set_launch_stop_event(m->ev_ar);
+        if (!m->opt.dp_concurrent) set_launch_stop_event(m->ev_ar);
         launch_adam(m->d_descs, (int)m->descs.size(), b0, m->param, m->grad, m->mom, m->vel, alpha, gs, m->adam_b1, m->adam_b2, m->adam_eps, 1, m->stream, 0);
-        if (!m->dp_concurrent) HIPCHK(hipStreamWaitEvent(m->tail, m->ev_ar, 0));
+        if (!m->opt.dp_concurrent) HIPCHK(hipStreamWaitEvent(on_stream(m, m->plan.tail), m->ev_ar, 0));
         if (m->early_held) {
             launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                                m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, m->tail);
+                                m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, on_stream(m, m->plan.tail));
             m->early_held = false;
         }
-        { ScopedTimer tm(m, T_AR_DEC, m->tail); NCCLCHK(g_rccl.AllReduce(m->grad + off, m->grad + off, n - off, ncclFloat32, ncclSum, m->comm_side, m->tail)); }
+        { ScopedTimer tm(m, T_AR_DEC, on_stream(m, m->plan.tail)); NCCLCHK(g_rccl.AllReduce(m->grad + off, m->grad + off, n - off, ncclFloat32, ncclSum, m->comm_side, on_stream(m, m->plan.tail))); }
         set_launch_stop_event(m->ev_dec);           // join_side() now waits for the decoder's UPDATE, not just its gradient
         launch_adam(m->d_descs, (int)m->descs.size(), m->elem_blocks - b0, m->param, m->grad, m->mom, m->vel, alpha, gs, m->adam_b1, m->adam_b2, m->adam_eps, 1,
-                    m->tail, b0);
+                    on_stream(m, m->plan.tail), b0);
     } else {
         CHK(join_side(m));
         { ScopedTimer tm(m, T_AR_ENC); NCCLCHK(g_rccl.AllReduce(m->grad, m->grad, n, ncclFloat32, ncclSum, m->comm_main, m->stream)); }
@@ -2407,7 +2478,6 @@ int iwae_create(const iwae_config* cfg, iwae_handle* out) {
         prio = least;
         HIPCHK(hipStreamCreateWithPriority(&m->side2, hipStreamNonBlocking, prio));
         HIPCHK(hipEventCreateWithFlags(&m->ev_s2, hipEventDisableTiming));
-        m->tail = m->side;
     }
     HIPCHK(hipEventCreateWithFlags(&m->ev_lse, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
@@ -2663,7 +2733,7 @@ int iwae_forward_backward_split(iwae_handle m, const float* x, int32_t B, int32_
         CHK(forward_impl(m, x, B, k, beta, eps, objective, true, nullptr, FwdCall{m->batch_offset}));
         CHK(backward_impl(m, objective, -1.0f, true));
     }
-    *side_stream = (void*)m->tail;
+    *side_stream = (void*)on_stream(m, m->plan.tail);
     *side_offset = m->split_offset;
     m->noise_step += 1;
     return IWAE_OK;
@@ -2698,73 +2768,73 @@ int iwae_set_option(iwae_handle m, const char* name, int64_t value) {
     const bool on = value != 0;
     const int iv = (int)value;
     const std::string n(name);
-    if (n == "out_recompute") m->allow_s_mode = !on;                  // recompute the logits in out_bwd instead of keeping s
-    else if (n == "no_defer") m->allow_defer = !on;                   // join the decoder update at the end of every step
-    else if (n == "wout_split") m->wout_split = std::max(0, std::min(95, iv));      // percent of the rows in the output layer's EARLY gradient launch (0: one launch)
-    else if (n == "wout_wg1") m->wout_wg1 = std::max(1, iv);          // ... its workgroups / those of the late launch
-    else if (n == "wout_wg2") m->wout_wg2 = std::max(1, iv);
-    else if (n == "defer_split") m->defer_split = on;                 // 1-layer step: one deferred decoder update per side stream
-    else if (n == "no_eps_multi") m->allow_eps_multi = !on;           // few rows: one noise-draw launch per step instead of one per 8 steps
-    else if (n == "no_zin") m->allow_zin = !on;                       // always the separate sampling kernel
-    else if (n == "zin_eval") m->allow_zin_eval = on;                 // forward-only calls: z made in the decoder kernel's prologue (measured slower)
-    else if (n == "no_chain2_bwd") m->allow_chain2_bwd = !on;         // ... only their backward unfused
-    else if (n == "no_chain2") m->allow_chain2 = !on;                 // 2-layer model: the per-sample blocks unfused
-    else if (n == "no_dec_bwd") m->allow_dec_bwd = !on;               // the decoder's dX chain as three launches
-    else if (n == "no_defer2_split") m->allow_defer2_split = !on;     // ... one deferred update on `tail` instead of one per side stream
-    else if (n == "no_defer2") m->allow_defer2 = !on;                 // 2-layer step: one reduction + update of all layers on the main stream
-    else if (n == "f32_dw_tiles") m->f32_dw_tiles = std::max(1, iv);
-    else if (n == "f32_dw_min_rows") m->f32_dw_min_rows = std::max(16, iv);
-    else if (n == "f32_gemm_dbg") m->gemm_f32.dbg = iv;                // DIAG builds: timing ablations of gemm_f32_v2_kernel (1 no fetch, 2 no stash, 4 no MFMAs, 16 no barrier)
-    else if (n == "f32_gemm_small_min") m->gemm_f32.v2_small_min = std::max(1, iv);
-    else if (n == "f32_ksplit_min_tiles") m->gemm_f32.ksplit_min_tiles = std::max(1, iv);     // ... only from that many 64 x 64 output tiles on
-    else if (n == "f32_no_ksplit") m->gemm_f32.ksplit = !on;           // ... few-row products as one 64-tile launch
-    else if (n == "f32_gemm_small_v1") m->gemm_f32.v2_small = !on;     // ... the round-3 64-tile kernel for every 64 x 64-tiled product
-    else if (n == "f32_gemm_w4") m->gemm_f32.w8 = !on;                 // ... without the 8-wave tiles (A/B only)
-    else if (n == "f32_gemm_v1") m->gemm_f32.v2 = !on;                 // float32 GEMMs with the round-3 k loop (A/B only)
-    else if (n == "no_f32_side") m->allow_f32_side = !on;             // float32 step on one stream (no side-stream weight gradients, no deferred decoder update)
-    else if (n == "f32_dw_last") m->f32_dw_last = iv;                 // float32 step: all decoder weight gradients behind the dX chain (1: tiles as picked, 2: 4-wave tiles, 3: ... at 3 waves per SIMD)
-    else if (n == "f32_wout_last") m->f32_wout_first = !on;           // ... with the output layer's gradient last on the side stream (beside the encoder's few-row kernels) instead of first (beside the dX chain)
-    else if (n == "no_f32_multi_reduce") m->allow_f32_multi_reduce = !on;      // float32 mode: a slab reduction launch per gradient tensor instead of one per step
-    else if (n == "f32_dec_fused_train") m->f32_dec_fused_train = on;   // float32 training step: the decoder forward as dec_fwd_f32_kernel (round 4) instead of three GEMM launches
-    else if (n == "no_f32_dec_fused") m->allow_f32_dec_fused = !on;   // float32 mode: the decoder forward as three GEMM launches
-    else if (n == "no_f32_bern_fused") m->allow_f32_bern_fused = !on; // float32 mode: logits to memory, bern_f32_kernel / dl_f32_kernel as their own passes
-    else if (n == "no_dec_rows") m->allow_dec_rows = !on;             // few data rows: the decoder's weight gradients as the grouped launch on the side stream + deferred reduction
-    else if (n == "no_wgrad_rows") m->allow_wgrad_rows = !on;         // few rows: the encoder's weight gradients as the grouped launch + slabs + reduce_grads_kernel
-    else if (n == "no_wg3") m->allow_wg3 = !on;                       // few rows: the decoder's weight gradients as three launches on two streams
-    else if (n == "g2w") m->allow_g2w = on;                           // the decoder kernel leaves bf16(g_r g2); the output layer's weight gradient runs unweighted on it (measured slower)
-    else if (n == "lat_rows4") m->allow_lat_rows4 = on;               // many samples per image: latent_bwd_kernel's sums inside block_bwd_kernel<4> (measured no faster)
-    else if (n == "no_lat_in_block") m->allow_lat_in_block = !on;     // few images: latent_bwd_kernel as its own launch in front of the encoder's backward pass
-    else if (n == "no_lse_in_bwd") m->allow_lse_in_bwd = !on;         // few rows: lse_kernel as its own launch between decoder forward and backward
-    else if (n == "no_lse_fused") m->allow_lse_fused = !on;           // lse_kernel as its own launch behind the decoder kernel
-    else if (n == "no_lse_dup") m->allow_lse_dup = !on;               // one lse_kernel, the side stream forks behind it
-    else if (n == "dz_f32") m->allow_dz_half = !on;                   // dec_bwd_kernel leaves dz as float32
-    else if (n == "no_small_dec_bwd") m->small_dec_bwd = !on;         // per-pixel-group out_bwd + finish + two dX launches below 8 192 rows
-    else if (n == "small_rows") m->small_rows = iv;
-    else if (n == "dec_rows") m->dec_rows_max = iv;                   // dec_bwd_rows_kernel up to this many rows
-    else if (n == "no_wg7") m->allow_wg7 = !on;                       // the 16-wave weight-gradient shapes everywhere
-    else if (n == "wg9") m->wg_shape9 = iv;                           // bit mask: layers that take the 8 + 8-wave / 128-feature wgradws shape
-    else if (n == "grid_chunk") m->grid_chunk = iv > 0 ? std::max(16, iv) : 0;      // iwae_grid_posterior: grid points per chunk (0: the default)
-    else if (n == "eval_rows") m->eval_rows = iv > 0 ? std::max(64, iv) : 0;       // data rows per evaluator launch
-    else if (n == "no_bern_pipe") m->allow_bern_pipe = !on;           // the Bernoulli forward on dense_kernel<EPI_BERN>
-    else if (n == "no_block_fused") m->allow_block_fused = !on;       // a BasicBlock on few rows as three dense_kernel launches
-    else if (n == "no_out_in_block") m->allow_out_in_block = !on;     // the few-row decoder's output layer as its own launch
-    else if (n == "no_dec_fused") m->allow_dec_fused = !on;           // the decoder's tanh layers as dense_kernel launches
-    else if (n == "no_bern_qw") m->bern_qw = !on;                     // the decoder kernel's 8-wave / 128-row shape
-    else if (n == "bern_qw_force") m->bern_qw_force = on;             // the 16-wave / 200-row shape at every row count
-    else if (n == "dense_g1") m->dense_g1_mask = (unsigned)iv;        // EPI bit mask of the 8-wave x 16-row dense shape
-    else if (n == "wg8") m->wg_target8 = std::max(1, iv);             // workgroup targets of the weight-gradient launches
-    else if (n == "wg8_few") m->wg_target8_few = std::max(1, iv);
-    else if (n == "wg16") m->wg_target16 = std::max(1, iv);
-    else if (n == "wg16_1") m->wg_target16_1 = std::max(1, iv);
-    else if (n == "eps_blocks") m->eps_blocks = std::max(0, iv);      // blocks of the ahead-of-time noise draw
-    else if (n == "dec_bwd_nw") m->dec_bwd_nw = iv == 8 ? 8 : 4;
-    else if (n == "no_side2") m->use_side2 = !on;                     // the hidden layers' weight gradients behind the output layer's
-    else if (n == "wg_group") m->allow_wg_group = on;                 // ... as one grouped launch
-    else if (n == "no_early_wout") m->allow_early_wout = !on;         // the output layer's weight gradient forks behind out_bwd
-    else if (n == "dp_concurrent") m->dp_concurrent = on;             // data-parallel step: no device-side order between its two all-reduces
+    if (n == "out_recompute") m->opt.allow_s_mode = !on;                  // recompute the logits in out_bwd instead of keeping s
+    else if (n == "no_defer") m->opt.allow_defer = !on;                   // join the decoder update at the end of every step
+    else if (n == "wout_split") m->opt.wout_split = std::max(0, std::min(95, iv));      // percent of the rows in the output layer's EARLY gradient launch (0: one launch)
+    else if (n == "wout_wg1") m->opt.wout_wg1 = std::max(1, iv);          // ... its workgroups / those of the late launch
+    else if (n == "wout_wg2") m->opt.wout_wg2 = std::max(1, iv);
+    else if (n == "defer_split") m->opt.defer_split = on;                 // 1-layer step: one deferred decoder update per side stream
+    else if (n == "no_eps_multi") m->opt.allow_eps_multi = !on;           // few rows: one noise-draw launch per step instead of one per 8 steps
+    else if (n == "no_zin") m->opt.allow_zin = !on;                       // always the separate sampling kernel
+    else if (n == "zin_eval") m->opt.allow_zin_eval = on;                 // forward-only calls: z made in the decoder kernel's prologue (measured slower)
+    else if (n == "no_chain2_bwd") m->opt.allow_chain2_bwd = !on;         // ... only their backward unfused
+    else if (n == "no_chain2") m->opt.allow_chain2 = !on;                 // 2-layer model: the per-sample blocks unfused
+    else if (n == "no_dec_bwd") m->opt.allow_dec_bwd = !on;               // the decoder's dX chain as three launches
+    else if (n == "no_defer2_split") m->opt.allow_defer2_split = !on;     // ... one deferred update on `tail` instead of one per side stream
+    else if (n == "no_defer2") m->opt.allow_defer2 = !on;                 // 2-layer step: one reduction + update of all layers on the main stream
+    else if (n == "f32_dw_tiles") m->opt.f32_dw_tiles = std::max(1, iv);
+    else if (n == "f32_dw_min_rows") m->opt.f32_dw_min_rows = std::max(16, iv);
+    else if (n == "f32_gemm_dbg") m->opt.gemm_f32.dbg = iv;                // DIAG builds: timing ablations of gemm_f32_v2_kernel (1 no fetch, 2 no stash, 4 no MFMAs, 16 no barrier)
+    else if (n == "f32_gemm_small_min") m->opt.gemm_f32.v2_small_min = std::max(1, iv);
+    else if (n == "f32_ksplit_min_tiles") m->opt.gemm_f32.ksplit_min_tiles = std::max(1, iv);     // ... only from that many 64 x 64 output tiles on
+    else if (n == "f32_no_ksplit") m->opt.gemm_f32.ksplit = !on;           // ... few-row products as one 64-tile launch
+    else if (n == "f32_gemm_small_v1") m->opt.gemm_f32.v2_small = !on;     // ... the round-3 64-tile kernel for every 64 x 64-tiled product
+    else if (n == "f32_gemm_w4") m->opt.gemm_f32.w8 = !on;                 // ... without the 8-wave tiles (A/B only)
+    else if (n == "f32_gemm_v1") m->opt.gemm_f32.v2 = !on;                 // float32 GEMMs with the round-3 k loop (A/B only)
+    else if (n == "no_f32_side") m->opt.allow_f32_side = !on;             // float32 step on one stream (no side-stream weight gradients, no deferred decoder update)
+    else if (n == "f32_dw_last") m->opt.f32_dw_last = iv;                 // float32 step: all decoder weight gradients behind the dX chain (1: tiles as picked, 2: 4-wave tiles, 3: ... at 3 waves per SIMD)
+    else if (n == "f32_wout_last") m->opt.f32_wout_first = !on;           // ... with the output layer's gradient last on the side stream (beside the encoder's few-row kernels) instead of first (beside the dX chain)
+    else if (n == "no_f32_multi_reduce") m->opt.allow_f32_multi_reduce = !on;      // float32 mode: a slab reduction launch per gradient tensor instead of one per step
+    else if (n == "f32_dec_fused_train") m->opt.f32_dec_fused_train = on;   // float32 training step: the decoder forward as dec_fwd_f32_kernel (round 4) instead of three GEMM launches
+    else if (n == "no_f32_dec_fused") m->opt.allow_f32_dec_fused = !on;   // float32 mode: the decoder forward as three GEMM launches
+    else if (n == "no_f32_bern_fused") m->opt.allow_f32_bern_fused = !on; // float32 mode: logits to memory, bern_f32_kernel / dl_f32_kernel as their own passes
+    else if (n == "no_dec_rows") m->opt.allow_dec_rows = !on;             // few data rows: the decoder's weight gradients as the grouped launch on the side stream + deferred reduction
+    else if (n == "no_wgrad_rows") m->opt.allow_wgrad_rows = !on;         // few rows: the encoder's weight gradients as the grouped launch + slabs + reduce_grads_kernel
+    else if (n == "no_wg3") m->opt.allow_wg3 = !on;                       // few rows: the decoder's weight gradients as three launches on two streams
+    else if (n == "g2w") m->opt.allow_g2w = on;                           // the decoder kernel leaves bf16(g_r g2); the output layer's weight gradient runs unweighted on it (measured slower)
+    else if (n == "lat_rows4") m->opt.allow_lat_rows4 = on;               // many samples per image: latent_bwd_kernel's sums inside block_bwd_kernel<4> (measured no faster)
+    else if (n == "no_lat_in_block") m->opt.allow_lat_in_block = !on;     // few images: latent_bwd_kernel as its own launch in front of the encoder's backward pass
+    else if (n == "no_lse_in_bwd") m->opt.allow_lse_in_bwd = !on;         // few rows: lse_kernel as its own launch between decoder forward and backward
+    else if (n == "no_lse_fused") m->opt.allow_lse_fused = !on;           // lse_kernel as its own launch behind the decoder kernel
+    else if (n == "no_lse_dup") m->opt.allow_lse_dup = !on;               // one lse_kernel, the side stream forks behind it
+    else if (n == "dz_f32") m->opt.allow_dz_half = !on;                   // dec_bwd_kernel leaves dz as float32
+    else if (n == "no_small_dec_bwd") m->opt.small_dec_bwd = !on;         // per-pixel-group out_bwd + finish + two dX launches below 8 192 rows
+    else if (n == "small_rows") m->opt.small_rows = iv;
+    else if (n == "dec_rows") m->opt.dec_rows_max = iv;                   // dec_bwd_rows_kernel up to this many rows
+    else if (n == "no_wg7") m->opt.allow_wg7 = !on;                       // the 16-wave weight-gradient shapes everywhere
+    else if (n == "wg9") m->opt.wg_shape9 = iv;                           // bit mask: layers that take the 8 + 8-wave / 128-feature wgradws shape
+    else if (n == "grid_chunk") m->opt.grid_chunk = iv > 0 ? std::max(16, iv) : 0;      // iwae_grid_posterior: grid points per chunk (0: the default)
+    else if (n == "eval_rows") m->opt.eval_rows = iv > 0 ? std::max(64, iv) : 0;       // data rows per evaluator launch
+    else if (n == "no_bern_pipe") m->opt.allow_bern_pipe = !on;           // the Bernoulli forward on dense_kernel<EPI_BERN>
+    else if (n == "no_block_fused") m->opt.allow_block_fused = !on;       // a BasicBlock on few rows as three dense_kernel launches
+    else if (n == "no_out_in_block") m->opt.allow_out_in_block = !on;     // the few-row decoder's output layer as its own launch
+    else if (n == "no_dec_fused") m->opt.allow_dec_fused = !on;           // the decoder's tanh layers as dense_kernel launches
+    else if (n == "no_bern_qw") m->opt.bern_qw = !on;                     // the decoder kernel's 8-wave / 128-row shape
+    else if (n == "bern_qw_force") m->opt.bern_qw_force = on;             // the 16-wave / 200-row shape at every row count
+    else if (n == "dense_g1") m->opt.dense_g1_mask = (unsigned)iv;        // EPI bit mask of the 8-wave x 16-row dense shape
+    else if (n == "wg8") m->opt.wg_target8 = std::max(1, iv);             // workgroup targets of the weight-gradient launches
+    else if (n == "wg8_few") m->opt.wg_target8_few = std::max(1, iv);
+    else if (n == "wg16") m->opt.wg_target16 = std::max(1, iv);
+    else if (n == "wg16_1") m->opt.wg_target16_1 = std::max(1, iv);
+    else if (n == "eps_blocks") m->opt.eps_blocks = std::max(0, iv);      // blocks of the ahead-of-time noise draw
+    else if (n == "dec_bwd_nw") m->opt.dec_bwd_nw = iv == 8 ? 8 : 4;
+    else if (n == "no_side2") m->opt.use_side2 = !on;                     // the hidden layers' weight gradients behind the output layer's
+    else if (n == "wg_group") m->opt.allow_wg_group = on;                 // ... as one grouped launch
+    else if (n == "no_early_wout") m->opt.allow_early_wout = !on;         // the output layer's weight gradient forks behind out_bwd
+    else if (n == "dp_concurrent") m->opt.dp_concurrent = on;             // data-parallel step: no device-side order between its two all-reduces
 #ifdef IWAE_DIAG
     // diagnostic builds only (DIAG=1 ./build.sh): in-kernel phase stamps and the weight-gradient ablations -- results are wrong or slower
-    else if (n == "stamps") { m->want_stamps = on; if (on) { m->allow_s_mode = false; m->allow_bern_pipe = false; m->allow_block_fused = false; m->allow_dec_fused = false; } }
+    else if (n == "stamps") { m->want_stamps = on; if (on) { m->opt.allow_s_mode = false; m->opt.allow_bern_pipe = false; m->opt.allow_block_fused = false; m->opt.allow_dec_fused = false; } }
     else if (n == "dense_stamps_epi") m->dstamp_epi = iv;
     else if (n == "dense_stamps_kt") m->dstamp_kt = iv;
     else if (n == "wg_debug") m->wg_debug = iv;
@@ -2926,8 +2996,8 @@ int iwae_eval_llh(iwae_handle m, const float* x, int32_t N, int32_t k, int32_t c
     // hidden width, and neither of the fused paths switched off; the 2-layer model and the unfused float32 path keep per-row tensors: 2^19)
     const bool eval_f32 = m->eval_precision == IWAE_PREC_FP32;
     const bool one_launch_dec = m->cfg.n_layers == 1 && m->dec1[2].KT == 7 && m->C == 0 && !m->has_prior &&
-                                (eval_f32 ? (m->allow_f32_dec_fused && m->allow_f32_bern_fused) : (m->allow_bern_pipe && m->allow_dec_fused));
-    const int eval_rows = m->eval_rows > 0 ? m->eval_rows : (one_launch_dec ? 1 << 21 : 1 << 19);
+                                (eval_f32 ? (m->opt.allow_f32_dec_fused && m->opt.allow_f32_bern_fused) : (m->opt.allow_bern_pipe && m->opt.allow_dec_fused));
+    const int eval_rows = m->opt.eval_rows > 0 ? m->opt.eval_rows : (one_launch_dec ? 1 << 21 : 1 << 19);
     const int kc = std::min(k, eval_rows);
     if (chunk <= 0) chunk = std::max(1, eval_rows / kc);
     chunk = std::min(chunk, N);
@@ -3098,7 +3168,7 @@ int iwae_grid_posterior(iwae_handle m, const float* x, int32_t N, const float* z
     if (q_mu) HIPCHK(hipMemcpy2DAsync(q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
     if (q_sigma) HIPCHK(hipMemcpy2DAsync(q_sigma, (size_t)D * 4, head + Dp, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
     // ---- G in chunks: decoder logits -> prep -> score -> merge into the running per-image state
-    const int chunk = m->grid_chunk > 0 ? m->grid_chunk : GRID_CHUNK_DEFAULT;
+    const int chunk = m->opt.grid_chunk > 0 ? m->opt.grid_chunk : GRID_CHUNK_DEFAULT;
     const int gmax = std::min(chunk, (int)G), gmaxp = round_up(gmax, 128), H = m->H[0], Hp = m->dec1[0].Np32;
     CHK(ensure(w.run, (size_t)N * GRID_ST * 8, st));
     CHK(ensure(w.lpx, (size_t)N * 8, st));
@@ -3216,7 +3286,7 @@ int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, co
         const Linear* e2 = m->enc2;
         const bool fused = !f32 && act_chain_ok(e2[0].KT, e2[1].KT, m->Dp[1] / 32) && e2[0].Kp32 == Dp0 && e2[0].Np32 == 32 * e2[1].KT &&
                            e2[1].Np32 == e2[0].Np32 && e2[2].KT == e2[1].KT && e2[2].Np32 == 2 * m->Dp[1] && ldh == 2 * Dp0;
-        const int eval_rows = m->eval_rows > 0 ? m->eval_rows : 1 << 19;
+        const int eval_rows = m->opt.eval_rows > 0 ? m->opt.eval_rows : 1 << 19;
         // (bf16 composed path: at most 4096 rows, where block_fwd is one block_fwd_kernel launch on any row count -- a row's mu2 does not
         // depend on how many rows share its launch)
         const int cap = (!f32 && !fused) ? std::min(eval_rows, 4096) : eval_rows;
