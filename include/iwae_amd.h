@@ -247,6 +247,39 @@ int iwae_latent_activity(iwae_handle h, const float* x, int32_t N,   /* [N, x_di
                          double* data_mean,                          /* [D1 (+ D2)] or NULL: mean over x of E_q[u|x] */
                          float* post_mean);                          /* [N, D1 (+ D2)] or NULL: E_q[u|x] per image */
 
+/* Aggregate-posterior decomposition of the KL term the model trains on (Hoffman & Johnson 2016, "ELBO surgery"; Chen et al. 2018,
+ * beta-TCVAE; no reference counterpart).  With q(z) = (1/N) sum_m q(z|x_m) over the N images given,
+ *   (1/N) sum_n KL(q(z|x_n) || p(z)) = I_q(n; z) + KL(q(z) || prod_d q(z_d)) + sum_d KL(q(z_d) || p(z_d)) = mi + tc + dim_kl,
+ * estimated exactly in the components (all N, the own one included) from S draws per image, z_{s,n} = mu_n + sigma_n eps_{s,n}; the heads
+ * mu, sigma (src/iwae1.py:39-42) in the eval precision (iwae_set_eval_precision).  With c = log(2 pi)/2 and
+ *   l(s,n|m,d)     = -((z_{s,n,d} - mu_{m,d}) / sigma_{m,d})^2 / 2 - log sigma_{m,d} - c
+ *   log_qzd[s,n,d] = LSE_m l(s,n|m,d) - log N              log_qz[s,n] = LSE_m sum_d l(s,n|m,d) - log N
+ *   lq_own[s,n,d]  = -eps^2/2 - log sigma_{n,d} - c         lp[s,n,d]   = -z^2/2 - c
+ *   unit_mi[d] = mean_{s,n}(lq_own_d - log_qzd_d)           unit_kl[d]  = mean_{s,n}(log_qzd_d - lp_d)
+ *   summary = { mi = mean(sum_d lq_own - log_qz), tc = mean(log_qz - sum_d log_qzd), dim_kl = sum_d unit_kl[d], kl = mean(sum_d lq_own - sum_d lp) }
+ * (kl is summed on its own; kl = mi + tc + dim_kl holds to double rounding).  The N^2 S D per-unit terms l(s,n|m,d) behind log_qzd are
+ * float32; behind log_qz the difference z - mu is float32 and its scaling, square and the sum over d are double (a float32 sum of 100 unit
+ * terms is off by ~1e-5, more than mi = 0 at N = 1 allows); lq_own, lp and every sum over samples are double; log_qz and log_qzd are
+ * returned and summed as float32.  mi <= log N; a collapsed unit has unit_kl and unit_mi near 0.
+ * Models: 1-layer unconditional only (the 2-layer q(z2|x) is not Gaussian and its p(z1) not N(0,1)): a 2-layer handle or cond_dim > 0 is
+ * IWAE_ERR_ARG.  N <= 0, S <= 0, x or summary NULL, or N > 2^24 or N * S > 2^27 (the launch grids' index range, not a memory bound):
+ * IWAE_ERR_ARG, nothing launched, the noise step unchanged.  The workspace is about 4 (2 Dpad + 1) N S + 4 (ceil(N/512) + 2) (Dpad + 3) min(N S, 16 384)
+ * + 20 N Dpad bytes, Dpad = D rounded up to 16 (0.1 GB at N = 10 000, S = 1, D = 100; 1 GB at S = 10); a call that does not fit fails with
+ * IWAE_ERR_NOMEM like any other.
+ * Draws: eps == NULL uses exactly what iwae_debug_eps(N, S, 0) returns at the current step and offset (latent stream 0, row
+ * (batch_offset + n) S + s) and then advances the noise step by one; with eps given the step is left alone.
+ * Determinism: a sample's log_qz / log_qzd depend only on the N heads (in their order) and that sample's eps -- not on S, the sample's
+ * position or the other draws -- and repeat bitwise; summary, unit_kl and unit_mi are reduced in double in an order fixed by (N, S).
+ * Numerical domain: finite and accurate for |eps| <= 8 and log sigma spread over +-6 across the images: the joint density carries a running
+ * maximum, a unit's density is shifted by the sample's own component (its sum is >= 1, its largest term exp(eps^2/2 + log(sigma_own/sigma_m))
+ * <= e^44).  x, eps: host or device; every output: host or device, NULL = not wanted (log_qz / log_qzd: only copied out when asked). */
+int iwae_aggregate_posterior(iwae_handle h, const float* x, int32_t N,   /* [N, x_dim], host or device */
+                             int32_t S, const float* eps,                /* draws per image; eps [S, N, D] (reference order) or NULL */
+                             double* summary,                            /* [4] required: mi, tc, dim_kl, kl */
+                             double* unit_kl, double* unit_mi,           /* [D] each or NULL */
+                             float* q_mu, float* q_sigma,                /* [N, D] encoder heads or NULL */
+                             float* log_qz, float* log_qzd);             /* [S, N] / [S, N, D] or NULL: only materialised when asked */
+
 /* Gradient moments of the training estimator (Rainforth et al. 2018, arXiv 1802.04537; Tucker et al. 2019, arXiv 1810.04152): the
  * per-parameter mean and unbiased (M - 1) variance, in double, of M draws of the flat float32 gradient.  Draw j (0 <= j < M) is exactly
  * the gradient iwae_forward_backward(h, x, B, k, beta, objective, NULL, ...) leaves after iwae_set_step(s0 + j, batch_offset), s0 the

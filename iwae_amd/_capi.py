@@ -73,6 +73,7 @@ SYMBOLS = {
     "iwae_decode": (C.c_int, [_P, _P, C.c_int32, _P]),
     "iwae_grid_posterior": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "iwae_latent_activity": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "iwae_aggregate_posterior": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P, _P]),
     "iwae_grad_moments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "iwae_dataset_upload": (C.c_int, [_P, _P, C.c_int32]),
     "iwae_dataset_begin_epoch": (C.c_int, [_P, C.c_uint32, _P, C.c_int32]),
@@ -89,7 +90,7 @@ SYMBOLS = {
 
 _lib = None
 
-_ID_SOURCES = ("activity_kernels.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "model.hip", "moments_kernels.hip",
+_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "model.hip", "moments_kernels.hip",
                os.path.join("..", "..", "include", "iwae_amd.h"))
 
 

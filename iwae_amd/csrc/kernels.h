@@ -483,4 +483,47 @@ struct MomentsFinalizeArgs {          // moments_finalize_kernel: out_var = M2 /
 void launch_moments_fold(const MomentsFoldArgs& a, hipStream_t st);
 void launch_moments_finalize(const MomentsFinalizeArgs& a, hipStream_t st);
 
+// ---- aggregate posterior (aggregate_kernels.hip; iwae_aggregate_posterior): log q(z) and its per-unit marginals at the samples of q(z|x_n).
+// Sample i = s N + n; a launch group handles samples [i0, i0 + T) against all N components, cut into ranges of AGG_RANGE components (their
+// number depends on N only) and, for the per-unit sums, into groups of AGG_DC units.  Dpad = round_up(D, AGG_DC) <= 128.
+#define AGG_DC 16               // units per agg_dim_kernel block; the padded unit width
+#define AGG_RANGE 512           // components per partial
+#define AGG_TILE 16384          // samples per launch group (bounds the partial buffers)
+struct AggCompArgs {                  // agg_comp_kernel: heads [N][ldh] (mu | sigma at soff) -> tables [N][Dpad] in log2 units
+    const float* head; int ldh, soff, N, D, Dpad;
+    float *mu, *inv, *nls;            // mu, sqrt(log2(e)/2) / sigma, -log2(e) (log sigma + log(2 pi)/2)
+    double *invd, *nls_sum;           // the scale in double; [N] sum_d -log2(e) (log sigma + log(2 pi)/2) in double (the joint density's)
+};
+struct AggSampleArgs {                // agg_sample_kernel: z and the own-component term of samples [i0, i0 + T), transposed [Dpad][T]
+    const float* head; int ldh, soff, N, D, Dpad;
+    const float* eps;                 // [S][N][D]
+    const float *mu, *inv, *nls;
+    long i0; int T;
+    float *zT, *shT;
+};
+struct AggMainArgs {                  // agg_dim_kernel + agg_joint_kernel
+    const float *mu, *inv, *nls; const double *invd, *nls_sum; int N, Dpad;
+    const float *zT, *shT; int T;
+    float* dim_part;                  // [P][Dpad][T] per-unit sums of exp2(term - own term)
+    double* joint_max; float* joint_sum;   // [P][T] running maximum (log2 units) and sum of the joint density
+};
+struct AggMergeArgs {                 // agg_merge_kernel: partials of P ranges -> log_qz [SN] and log_qzdT [Dpad][ldo] at column i0
+    const float* dim_part; const double* joint_max; const float *joint_sum, *shT; int P, Dpad, T;
+    double log_n;
+    float* log_qz; float* log_qzdT; long ldo, i0;
+};
+struct AggReduceArgs {                // agg_reduce_kernel + agg_finish_kernel
+    const float* head; int ldh, soff, N, D;
+    const float* eps; long SN;
+    const float *log_qz, *log_qzdT;   // [SN], [Dpad][SN]
+    double* part;                     // [(D + 1)][5] block sums
+    double *summary, *unit_kl, *unit_mi;
+};
+void launch_agg_comp(const AggCompArgs& a, hipStream_t st);
+void launch_agg_sample(const AggSampleArgs& a, hipStream_t st);
+void launch_agg_main(const AggMainArgs& a, hipStream_t st);
+void launch_agg_merge(const AggMergeArgs& a, hipStream_t st);
+void launch_agg_untranspose(const float* src, long SN, int D, float* dst, hipStream_t st);
+void launch_agg_reduce(const AggReduceArgs& a, hipStream_t st);
+
 }  // namespace iwae

@@ -287,6 +287,9 @@ struct iwae_model {
     struct ActWs { DevBuf x, xP, head, eps, z, rows, part, pm, act, dm; BlockWs blk; F32Block f32; } act;
     // iwae_grad_moments' buffers: the images (uploaded once per call), the Welford mean and M2 [nparam] in double
     struct MomWs { DevBuf x, mean, m2; } mom_ws;
+    // iwae_aggregate_posterior's buffers: the images, heads and draws, the component tables, a sample tile's z / own terms and range partials,
+    // the per-sample densities (log_qzd transposed [Dpad][S N]) and the double sums
+    struct AggWs { DevBuf x, xP, head, eps, mu, inv, invd, nls, nls_sum, zT, shT, dim_part, jmax, jsum, lqz, lqzdT, lqzd, part, out; } agg;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
@@ -2557,6 +2560,12 @@ void iwae_destroy(iwae_handle m) {
         DevBuf* bb[] = {&m->mom_ws.x, &m->mom_ws.mean, &m->mom_ws.m2};
         for (DevBuf* b : bb) free_buf(*b);
     }
+    {
+        iwae_model::AggWs& g = m->agg;
+        DevBuf* bb[] = {&g.x, &g.xP, &g.head, &g.eps, &g.mu, &g.inv, &g.invd, &g.nls, &g.nls_sum, &g.zT, &g.shT, &g.dim_part, &g.jmax, &g.jsum, &g.lqz, &g.lqzdT,
+                        &g.lqzd, &g.part, &g.out};
+        for (DevBuf* b : bb) free_buf(*b);
+    }
     BlockWs* bw[] = {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior};
     for (BlockWs* w : bw) {
         DevBuf* bb[] = {&w->h1P, &w->h2P, &w->head, &w->dheadP, &w->d2P, &w->d1P, &w->dx};
@@ -3373,6 +3382,111 @@ int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, co
     if (data_mean) CHK(copy_out(m, data_mean, w.dm.p, (size_t)Dt * 8));
     if (post_mean) CHK(copy_out(m, post_mean, w.pm.p, (size_t)N * Dt * 4));
     HIPCHK(hipStreamSynchronize(st));
+    m->have_forward = false;
+    return IWAE_OK;
+}
+
+// Aggregate-posterior decomposition (Hoffman & Johnson 2016; Chen et al. 2018): the samples z = mu_n + sigma_n eps_{s,n} of every image
+// against the mixture of all N encoder posteriors, in sample tiles of AGG_TILE; DESIGN.md section 14
+int iwae_aggregate_posterior(iwae_handle m, const float* x, int32_t N, int32_t S, const float* eps, double* summary, double* unit_kl, double* unit_mi,
+                             float* q_mu, float* q_sigma, float* log_qz, float* log_qzd) {
+    if (!m || !x || !summary) return fail(IWAE_ERR_ARG, "aggregate_posterior: need x and summary");
+    if (N <= 0 || S <= 0) return fail(IWAE_ERR_ARG, "aggregate_posterior: N and S must be positive");
+    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "aggregate_posterior: only the 1-layer model (the 2-layer q(z2|x) is not Gaussian, its p(z1) not N(0,1))");
+    if (m->C != 0) return fail(IWAE_ERR_ARG, "aggregate_posterior: only the unconditional model (cond_dim = 0)");
+    if (N > 1 << 24 || (int64_t)N * S > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "aggregate_posterior: too large (N > 2^24 images or N * S > 2^27 samples)");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CHK(join_side(m));      // the parameters a deferred update may still be writing
+    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
+    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
+    hipStream_t st = m->stream;
+    iwae_model::AggWs& w = m->agg;
+    const int D = m->D[0], Dp = m->Dp[0], Dpad = round_up(D, AGG_DC);
+    const long SN = (long)S * N;
+    const int P = (N + AGG_RANGE - 1) / AGG_RANGE, Tmax = (int)std::min<long>(SN, AGG_TILE);
+    const float* xd = x;
+    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * m->X * 4)); xd = ptr<float>(w.x); }
+    // ---- encoder heads mu, sigma of the N images (src/iwae1.py:39-42), in the eval precision
+    const float* head;
+    int ldh;
+    CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
+    if (q_mu) HIPCHK(hipMemcpy2DAsync(q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
+    if (q_sigma) HIPCHK(hipMemcpy2DAsync(q_sigma, (size_t)D * 4, head + Dp, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
+    // ---- the draws [S][N][D]: the caller's, or what iwae_debug_eps(N, S, 0) returns at this step and offset
+    const float* ed = eps;
+    if (!eps) {
+        CHK(ensure(w.eps, (size_t)SN * D * 4, st));
+        EpsSrc e;
+        e.user = nullptr; e.B = N; e.seed = m->cfg.seed; e.row_offset = (uint64_t)m->batch_offset * (uint64_t)S; e.step = m->noise_step; e.stream = 0;
+        launch_eps_dump(e, N, S, D, ptr<float>(w.eps), st);
+        HIPCHK(hipGetLastError());
+        ed = ptr<float>(w.eps);
+    } else if (!is_device_ptr(eps, m->cfg.device)) {
+        CHK(copy_in(m, w.eps, eps, (size_t)SN * D * 4));
+        ed = ptr<float>(w.eps);
+    }
+    CHK(ensure(w.mu, (size_t)N * Dpad * 4, st));
+    CHK(ensure(w.inv, (size_t)N * Dpad * 4, st));
+    CHK(ensure(w.nls, (size_t)N * Dpad * 4, st));
+    CHK(ensure(w.invd, (size_t)N * Dpad * 8, st));
+    CHK(ensure(w.nls_sum, (size_t)N * 8, st));
+    CHK(ensure(w.zT, (size_t)Dpad * Tmax * 4, st));
+    CHK(ensure(w.shT, (size_t)Dpad * Tmax * 4, st));
+    CHK(ensure(w.dim_part, (size_t)P * Dpad * Tmax * 4, st));
+    CHK(ensure(w.jmax, (size_t)P * Tmax * 8, st));
+    CHK(ensure(w.jsum, (size_t)P * Tmax * 4, st));
+    CHK(ensure(w.lqz, (size_t)SN * 4, st));
+    CHK(ensure(w.lqzdT, (size_t)Dpad * SN * 4, st));
+    CHK(ensure(w.part, (size_t)(D + 1) * 5 * 8, st));
+    CHK(ensure(w.out, (size_t)(4 + 2 * D) * 8, st));
+    AggCompArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.head = head; ca.ldh = ldh; ca.soff = Dp; ca.N = N; ca.D = D; ca.Dpad = Dpad;
+    ca.mu = ptr<float>(w.mu); ca.inv = ptr<float>(w.inv); ca.nls = ptr<float>(w.nls);
+    ca.invd = ptr<double>(w.invd); ca.nls_sum = ptr<double>(w.nls_sum);
+    launch_agg_comp(ca, st);
+    HIPCHK(hipGetLastError());
+    for (long i0 = 0; i0 < SN; i0 += AGG_TILE) {
+        const int T = (int)std::min<long>(AGG_TILE, SN - i0);
+        AggSampleArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.head = head; sa.ldh = ldh; sa.soff = Dp; sa.N = N; sa.D = D; sa.Dpad = Dpad; sa.eps = ed;
+        sa.mu = ca.mu; sa.inv = ca.inv; sa.nls = ca.nls; sa.i0 = i0; sa.T = T; sa.zT = ptr<float>(w.zT); sa.shT = ptr<float>(w.shT);
+        launch_agg_sample(sa, st);
+        AggMainArgs ma;
+        memset(&ma, 0, sizeof(ma));
+        ma.mu = ca.mu; ma.inv = ca.inv; ma.nls = ca.nls; ma.invd = ca.invd; ma.nls_sum = ca.nls_sum; ma.N = N; ma.Dpad = Dpad;
+        ma.zT = sa.zT; ma.shT = sa.shT; ma.T = T;
+        ma.dim_part = ptr<float>(w.dim_part); ma.joint_max = ptr<double>(w.jmax); ma.joint_sum = ptr<float>(w.jsum);
+        launch_agg_main(ma, st);
+        AggMergeArgs ga;
+        memset(&ga, 0, sizeof(ga));
+        ga.dim_part = ma.dim_part; ga.joint_max = ma.joint_max; ga.joint_sum = ma.joint_sum; ga.shT = sa.shT; ga.P = P; ga.Dpad = Dpad; ga.T = T;
+        ga.log_n = log((double)N); ga.log_qz = ptr<float>(w.lqz); ga.log_qzdT = ptr<float>(w.lqzdT); ga.ldo = SN; ga.i0 = i0;
+        launch_agg_merge(ga, st);
+        HIPCHK(hipGetLastError());
+    }
+    AggReduceArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.head = head; ra.ldh = ldh; ra.soff = Dp; ra.N = N; ra.D = D; ra.eps = ed; ra.SN = SN;
+    ra.log_qz = ptr<float>(w.lqz); ra.log_qzdT = ptr<float>(w.lqzdT); ra.part = ptr<double>(w.part);
+    ra.summary = ptr<double>(w.out); ra.unit_kl = ra.summary + 4; ra.unit_mi = ra.unit_kl + D;
+    launch_agg_reduce(ra, st);
+    HIPCHK(hipGetLastError());
+    CHK(copy_out(m, summary, ra.summary, 4 * 8));
+    if (unit_kl) CHK(copy_out(m, unit_kl, ra.unit_kl, (size_t)D * 8));
+    if (unit_mi) CHK(copy_out(m, unit_mi, ra.unit_mi, (size_t)D * 8));
+    if (log_qz) CHK(copy_out(m, log_qz, w.lqz.p, (size_t)SN * 4));
+    if (log_qzd) {
+        float* dst = log_qzd;
+        const bool dev = is_device_ptr(log_qzd, m->cfg.device);
+        if (!dev) { CHK(ensure(w.lqzd, (size_t)SN * D * 4, st)); dst = ptr<float>(w.lqzd); }
+        launch_agg_untranspose(ptr<float>(w.lqzdT), SN, D, dst, st);
+        HIPCHK(hipGetLastError());
+        if (!dev) CHK(copy_out(m, log_qzd, dst, (size_t)SN * D * 4));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (!eps) m->noise_step += 1;
     m->have_forward = false;
     return IWAE_OK;
 }

@@ -65,3 +65,12 @@ class IWAE(BaseIWAE):
         Returns (counts per layer, activity per layer): ([count], [A float64 [D]])."""
         act = self._net.latent_activity(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim))["activity"]
         return [utils.count_active(a, threshold) for a in act], act
+
+    # ---- aggregate-posterior decomposition of the KL term (Hoffman & Johnson 2016; Chen et al. 2018)
+    def aggregate_posterior(self, X, n_samples=1):
+        """mean_n KL(q(z|x_n) || p(z)) over the images X split into mi + tc + dim_kl (iwae_aggregate_posterior), with the per-unit
+        unit_kl[d] = KL(q(z_d) || p(z_d)) and unit_mi[d] = I(n; z_d): both near 0 for a collapsed unit.  Returns the binding's dict."""
+        if self._net.cond_dim:
+            raise NotImplementedError("the aggregate posterior covers the unconditional 1-layer model only (q(z|x, y) and a learned p(z|y) "
+                                      "need a label per image)")
+        return self._net.aggregate_posterior(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), n_samples=n_samples)

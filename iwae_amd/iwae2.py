@@ -35,3 +35,7 @@ class IWAE(BaseIWAE):
         E_q[z2|x] = the mean of mu2(z1) over n_samples draws of z1 ~ q(z1|x).  Returns ([count z1, count z2], [A z1, A z2])."""
         act = self._net.latent_activity(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), k=n_samples)["activity"]
         return [utils.count_active(a, threshold) for a in act], act
+
+    def aggregate_posterior(self, X, n_samples=1):
+        raise NotImplementedError("the aggregate posterior covers the 1-layer model only: q(z2|x) of the 2-layer model is not Gaussian and "
+                                  "its p(z1) is not N(0,1)")

@@ -318,6 +318,35 @@ class NativeModel:
             out["post_mean"] = [np.ascontiguousarray(pm[:, cut[i]:cut[i + 1]]) for i in range(len(dims))]
         return out
 
+    def aggregate_posterior(self, x, n_samples=1, eps=None, per_sample=False):
+        """iwae_aggregate_posterior: the split of the mean KL(q(z|x_n) || p(z)) over the images x [N, x_dim] into mi = I_q(n; z),
+        tc = KL(q(z) || prod_d q(z_d)) and dim_kl = sum_d KL(q(z_d) || p(z_d)), q(z) the mixture of all N encoder posteriors, from
+        n_samples draws per image: the device's (eps=None; advances the noise step) or eps [n_samples, N, D].  Returns float64 scalars
+        mi, tc, dim_kl, kl, log_n, arrays unit_kl, unit_mi [D] (float64) and q_mu, q_sigma [N, D]; with per_sample=True also log_qz
+        [n_samples, N] and log_qzd [n_samples, N, D]."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        N, D, S = x.shape[0], self.n_latent[0], int(n_samples)
+        e = None
+        if eps is not None:
+            e = _f32(eps)
+            if e.shape != (S, N, D):
+                raise ValueError("aggregate_posterior: eps must be [n_samples, N, %d] = %s, got %s" % (D, (S, N, D), e.shape))
+        summary = np.empty(4, dtype=np.float64)
+        ukl, umi = np.empty(D, dtype=np.float64), np.empty(D, dtype=np.float64)
+        qmu, qsg = np.empty((N, D), dtype=np.float32), np.empty((N, D), dtype=np.float32)
+        lqz = np.empty((max(S, 0), N), dtype=np.float32) if per_sample else None
+        lqzd = np.empty((max(S, 0), N, D), dtype=np.float32) if per_sample else None
+        dp = C.POINTER(C.c_double)
+        check(self.lib.iwae_aggregate_posterior(self.h, x.ctypes.data, N, S, e.ctypes.data if e is not None else None,
+                                                summary.ctypes.data_as(dp), ukl.ctypes.data_as(dp), umi.ctypes.data_as(dp),
+                                                qmu.ctypes.data, qsg.ctypes.data,
+                                                lqz.ctypes.data if per_sample else None, lqzd.ctypes.data if per_sample else None))
+        out = {"mi": summary[0], "tc": summary[1], "dim_kl": summary[2], "kl": summary[3], "log_n": np.float64(np.log(N)),
+               "unit_kl": ukl, "unit_mi": umi, "q_mu": qmu, "q_sigma": qsg}
+        if per_sample:
+            out["log_qz"], out["log_qzd"] = lqz, lqzd
+        return out
+
     def grad_moments(self, x, k, draws, beta=1.0, objective="iwae_elbo"):
         """iwae_grad_moments: the per-parameter mean and unbiased variance (float64 [P] each) of `draws` gradient draws of the training
         estimator on the images x [B, x_dim].  Draw j is the gradient forward_backward(x, k, beta, objective) leaves after
