@@ -16,68 +16,19 @@ import pytest
 
 from oracle import iwae_np as O, philox_np
 import make_golden as MG
+from _parity_common import (EMU_ROW_ATOL, EMU_SCALAR_ATOL, EMU_GRAD_REL, EXACT_SCALAR_ATOL, EXACT_GRAD_REL, F32_SCALAR_REL, F32_GRAD_REL,
+                            F32_ROW_ATOL, _grad_rel_errors, _densities_at_device_head, _densities_at_device_heads_2layer)
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-EMU_ROW_ATOL, EMU_SCALAR_ATOL, EMU_GRAD_REL = 0.03, 0.02, 1e-2
 O_ID = {"vae_elbo": 0, "iwae_elbo": 1, "iwae_eq14": 2, "vae_elbo_kl": 3, "dreg": 4}
-EXACT_SCALAR_ATOL, EXACT_GRAD_REL = 0.15, 3e-2
 
 
 def _model(n_layers, nh, nl, x_dim=784, options=None):
     """options: kernel-selection switches (iwae_set_option) -- the library does not read the environment."""
     from iwae_amd.native import NativeModel
     return NativeModel(n_layers, nh, nl, x_dim=x_dim, seed=123, options=options)
-
-
-def _grad_rel_errors(flat, grads):
-    out, off = [], 0
-    for dW, db in grads:
-        for g in (dW, db):
-            got = flat[off:off + g.size].reshape(g.shape).astype(np.float64)
-            off += g.size
-            out.append(np.linalg.norm(got - g) / (np.linalg.norm(g) + 1e-30))
-    return out
-
-
-def _densities_at_device_head(m, P, x, eps, nl):
-    """Per-row log p(x|z), log p(z), log q(z|x) of the 1-layer model evaluated by the ORACLE at the DEVICE's own encoder head
-    (mu, sigma as float32, iwae_debug_tensor "enc.head") and the given draws: removes the one sensitivity the per-row comparison with
-    the pure oracle has -- a bf16 ulp flip of one encoder activation moves an image's mu, hence log p(z) of all its samples -- so the
-    usual per-row bound holds for EVERY row (src/iwae1.py:59,105-111)."""
-    head = m.debug_tensor("enc.head").astype(np.float64)
-    Dp = head.shape[1] // 2
-    mu, sig = head[:, :nl], head[:, Dp:Dp + nl]
-    z = mu[None] + sig[None] * np.asarray(eps, dtype=np.float64)
-    dec = O._MLP3(P[4:7], O.bf16_round)
-    lpxz = np.sum(O.bernoulli_log_prob(np.asarray(x, dtype=np.float64)[None], dec.fwd(O.bf16_round(z))), axis=-1)
-    lpz = np.sum(O.normal_log_prob(z, 0.0, 1.0), axis=-1)
-    lqzx = np.sum(O.normal_log_prob(z, mu[None], sig[None]), axis=-1)
-    return {"lpxz": lpxz, "lpz": lpz, "lqzx": lqzx, "mu": mu, "sigma": sig}
-
-
-def _densities_at_device_heads_2layer(m, eps1, eps2, B, k, nl, P=None, x=None):
-    """The 2-layer model's four latent log-densities (src/iwae2.py:118-124) evaluated by the oracle at the DEVICE's own three Gaussian
-    heads (float32: "enc.head" on the images, "enc2.head" / "dec2.head" per sample; device rows are image-major, r = b*k + s) and the given
-    draws.  A bf16 ulp flip in one hidden activation moves a head, and log p(z1|z2) divides by sigma_p^2: evaluated at the device's heads
-    the comparison is free of that and holds per row at float32-level tolerances."""
-    def split(name, D):
-        h = m.debug_tensor(name).astype(np.float64)
-        Dp = h.shape[1] // 2
-        return h[:, :D], h[:, Dp:Dp + D]
-    km = lambda a: a.reshape(B, k, -1).transpose(1, 0, 2)      # [M, D] image-major -> [k, B, D]
-    mu1, sig1 = split("enc.head", nl[0])
-    mu2, sig2 = [km(a) for a in split("enc2.head", nl[1])]
-    mup, sigp = [km(a) for a in split("dec2.head", nl[0])]
-    z1 = mu1[None] + sig1[None] * np.asarray(eps1, dtype=np.float64)
-    z2 = mu2 + sig2 * np.asarray(eps2, dtype=np.float64)
-    out = {"lpz2": np.sum(O.normal_log_prob(z2, 0.0, 1.0), axis=-1), "lqz2z1": np.sum(O.normal_log_prob(z2, mu2, sig2), axis=-1),
-           "lpz1z2": np.sum(O.normal_log_prob(z1, mup, sigp), axis=-1), "lqz1x": np.sum(O.normal_log_prob(z1, mu1[None], sig1[None]), axis=-1)}
-    if P is not None:      # log p(x|z1) through the oracle's decoder (the last three layers) at the device's own z1 (src/iwae2.py:96,121)
-        dec = O._MLP3(P[-3:], O.bf16_round)
-        out["lpxz1"] = np.sum(O.bernoulli_log_prob(np.asarray(x, dtype=np.float64)[None], dec.fwd(O.bf16_round(z1))), axis=-1)
-    return out
 
 
 CASES_1L = [  # (B, k, objective, beta, n_hidden, n_latent, x_dim)
@@ -1075,7 +1026,6 @@ def test_eval_llh_images_per_launch_are_invisible(gpu):
 # ---------------------------------------------------------------- float32 mode (iwae_config.precision = IWAE_PREC_FP32)
 # "fp32 kernels rel 1e-5 on scalars / 1e-4 on grads vs fp64 oracle".  The reference computes in float32
 # (Keras Dense defaults, src/iwae1.py:31-34,72-75); every GEMM of this mode is an exact-f32 MFMA (v_mfma_f32_16x16x4_f32).
-F32_SCALAR_REL, F32_GRAD_REL, F32_ROW_ATOL = 1e-5, 1e-4, 2e-3
 
 CASES_F32 = [  # (layers, B, k, objective, beta, n_hidden, n_latent, x_dim)
     (1, 20, 1, "vae_elbo", 1.0, 200, 100, 784),          # BASELINE configs[0]
