@@ -293,6 +293,72 @@ int iwae_grad_moments(iwae_handle h, const float* x, int32_t B, int32_t k, float
                       int32_t M,                                         /* draws, >= 2 */
                       double* mean, double* var);                        /* [P] each, host or device */
 
+/* Annealed importance sampling estimate of log p(x) with HMC transitions (Neal 2001; Wu, Burda, Salakhutdinov & Grosse 2017, "On the
+ * quantitative analysis of decoder-based generative models"; no reference counterpart -- its README points to an annealed-IWAE repository).
+ * Image n has C chains.  Base density p0 = q(z|x_n) (IWAE_AIS_INIT_ENCODER; heads mu, sigma of src/iwae1.py:39-42 in the eval precision) or
+ * N(0, I) (IWAE_AIS_INIT_PRIOR: mu = 0, sigma = 1).  The chain state is the standardised e, z = mu + sigma e, so HMC runs with the identity
+ * mass matrix at unit scale whatever sigma is.  With c = log(2 pi)/2,
+ *   lj(e) = log p(x|z) + sum_d (-z_d^2/2 - c)   (src/iwae1.py:105-111)        l0(e) = sum_d (-e_d^2/2 - log sigma_d - c)
+ *   for t = 1..T:  log_w += (betas[t] - betas[t-1]) (lj - l0)(e)               (float32 product terms, double accumulator per chain)
+ *                  one HMC transition that leaves f_t ~ exp(-U_t) invariant, U_t(e) = -[(1 - b) l0(e) + b lj(e)], b = betas[t]:
+ *                  grad U_t = (1 - b) e - b sigma (grad_z log p(x|z) - z)
+ *                  p ~ N(0, I);  p -= (h/2) grad U;  L times { e += h p;  p -= h grad U (the last: h/2) }
+ *                  dH = ((U_t(e') + |p'|^2/2) - U_t(e)) - |p|^2/2  (float32);  accept iff logf(u) < -dH  (a NaN dH rejects)
+ *   log_px[n] = LSE_c log_w[c,n] - log C  (double)        ess[n] = (sum_c w)^2 / sum_c w^2
+ * betas: any T + 1 values in [0,1]; ascending 0 -> 1 is the forward run (log_px is a stochastic lower bound of log p(x) in expectation),
+ * descending 1 -> 0 started from exact posterior samples (z0) the reverse run of bidirectional Monte Carlo (Grosse et al. 2015), whose
+ * E[exp(log_w)] = 1/p(x).  T = 1, betas = {0, 1}, encoder init: log_w is exactly the importance weight of iwae_eval_llh at k = C.
+ * step_size h > 0; adapt != 0: each chain keeps its own h, multiplied after every transition by 1.02 if the chain's running acceptance
+ * mean (accepts so far / transitions so far) exceeds 0.65, else by 0.98, and clamped to [1e-4, 0.5] (Wu et al.'s rule).  ADAPTATION MAKES
+ * THE TRANSITION DEPEND ON THE CHAIN'S HISTORY: the kernel is then no longer Markov and the estimator's unbiasedness argument holds only
+ * approximately; adapt = 0 is the exact scheme.
+ * Noise: with eps0 = mom = unif = NULL the device Philox generator, counter (row lo, row hi, stream << 24 | d4, step), row = (batch_offset + n) C + c,
+ * s0 = the handle's noise step: e_0 stream 0 at step s0 (exactly what iwae_debug_eps(N, C, 0) returns and iwae_eval_llh uses at k = C), the
+ * momentum of transition t stream 3 at step s0 + t, its accept uniform stream 4 at step s0 + t (d4 = 0, word 0, u = ((r >> 8) + 0.5) 2^-24);
+ * the call advances the noise step by T + 1.  With z0 [C,N,D] given, e_0 = (z0 - mu) / sigma and nothing is drawn at step s0 (the step still
+ * advances by T + 1).  The caller's noise: eps0 [C,N,D], mom [T,C,N,D], unif [T,C,N] in the reference's order, all three or none (eps0 is
+ * ignored beside z0), the step is left alone.
+ * Models: the 1-layer unconditional model with n_hidden <= 208 only; a 2-layer handle, cond_dim > 0 or cond_prior: IWAE_ERR_ARG.  N, C, T or
+ * L <= 0, a beta outside [0,1], step_size <= 0, some but not all noise pointers, a wrong struct_size, x / opt / out / betas / log_px NULL or
+ * N C > 2^27: IWAE_ERR_ARG before any launch, the noise step unchanged.
+ * Arithmetic: the chain is float32 (v_mfma_f32_16x16x4_f32) whatever iwae_set_eval_precision says; only the heads follow it.
+ * Workspace: 4 N C (D + 4) bytes of chain state, two padded copies of the decoder's weights (about 2 x 4 (D H + H H + H X) bytes), and per
+ * output asked for its own size (accept_rate: N C T bytes of flags; with the caller's noise on the host its copy, 4 T N C (D + 1) bytes).
+ * Determinism: a chain's results depend only on the weights, its image and that image's heads, its own noise and the schedule -- not on N,
+ * C, its position, the other chains or the launch chunking (option ais_t_chunk: transitions per launch) -- and repeat bitwise; log_px and
+ * ess are reduced over an image's chains in chain order.
+ * x, betas, z0, eps0, mom, unif: host or device.  Outputs: each host or device, NULL = not wanted and never materialised. */
+typedef enum { IWAE_AIS_INIT_ENCODER = 0, IWAE_AIS_INIT_PRIOR = 1 } iwae_ais_init;
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(iwae_ais_options) (72); ABI guard like iwae_config's */
+    int32_t C;                 /* chains per image */
+    int32_t T;                 /* transitions (temperatures beyond the first) */
+    int32_t L;                 /* leapfrog steps per transition */
+    const float* betas;        /* [T + 1] */
+    float step_size;           /* h */
+    int32_t adapt;             /* 0: fixed h; else per-chain adaptation (see above) */
+    int32_t init;              /* iwae_ais_init */
+    int32_t reserved;          /* 0 */
+    const float* z0;           /* [C,N,D] initial states in z space, or NULL */
+    const float* eps0;         /* [C,N,D]   the caller's noise: all three or none */
+    const float* mom;          /* [T,C,N,D] */
+    const float* unif;         /* [T,C,N]   in (0,1) */
+} iwae_ais_options;
+typedef struct {
+    double* log_px;            /* [N]      required */
+    double* log_w;             /* [C,N] */
+    float* ess;                /* [N] */
+    float* accept_rate;        /* [T]      mean over the N C chains */
+    float* z;                  /* [C,N,D]  final states mu + sigma e */
+    float* step_out;           /* [C,N]    final step sizes */
+    float* q_mu;               /* [N,D]    (prior init: 0) */
+    float* q_sigma;            /* [N,D]    (prior init: 1) */
+    float* dH;                 /* [T,C,N] */
+    uint8_t* accepted;         /* [T,C,N]  0 / 1 */
+} iwae_ais_outputs;
+int iwae_ais(iwae_handle h, const float* x, int32_t N,                     /* [N, x_dim], host or device, any values in [0,1] */
+             const iwae_ais_options* opt, const iwae_ais_outputs* out);
+
 /* Data pipeline on the device (main.py:59-65,117-120 + src/utils.py:26-27): the grey-level training set
  * stays resident in HBM as uint8 [n, x_dim]; every epoch gets a visiting order (tf.data shuffle) and a
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),
@@ -317,7 +383,7 @@ int iwae_train_step_dataset(iwae_handle h, int32_t start, int32_t B, int32_t k, 
  * step (an event record costs a few us of stream bubble, so bench.py samples rather than timing every launch); 0 switches
  * it off.  name: "decoder_fwd" (whole decoder forward + log-likelihood), "out_bwd" (output-layer backward), "decoder_bwd" (the decoder's whole dX chain where it is one launch), "wgrad_out",
  * "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent" (the decoder's other backward kernels), "latent_bwd",
- * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam).  A kernel a configuration does not launch reports 0 launches. */
+ * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on).  A kernel a configuration does not launch reports 0 launches. */
 int iwae_enable_timing(iwae_handle h, int32_t enable);
 int iwae_kernel_time(iwae_handle h, const char* name, double* avg_us, int64_t* launches);
 

@@ -35,6 +35,24 @@ class Tensors(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TENSOR_FIELDS]
 
 
+class AisOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("C", C.c_int32), ("T", C.c_int32), ("L", C.c_int32), ("betas", C.c_void_p),
+                ("step_size", C.c_float), ("adapt", C.c_int32), ("init", C.c_int32), ("reserved", C.c_int32),
+                ("z0", C.c_void_p), ("eps0", C.c_void_p), ("mom", C.c_void_p), ("unif", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(AisOptions)   # the ABI guard iwae_ais checks
+
+
+AIS_OUTPUT_FIELDS = ("log_px", "log_w", "ess", "accept_rate", "z", "step_out", "q_mu", "q_sigma", "dH", "accepted")
+AIS_INITS = {"encoder": 0, "prior": 1}
+
+
+class AisOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in AIS_OUTPUT_FIELDS]
+
+
 # every symbol include/iwae_amd.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -74,6 +92,7 @@ SYMBOLS = {
     "iwae_grid_posterior": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "iwae_latent_activity": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "iwae_aggregate_posterior": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P, _P]),
+    "iwae_ais": (C.c_int, [_P, _P, C.c_int32, C.POINTER(AisOptions), C.POINTER(AisOutputs)]),
     "iwae_grad_moments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "iwae_dataset_upload": (C.c_int, [_P, _P, C.c_int32]),
     "iwae_dataset_begin_epoch": (C.c_int, [_P, C.c_uint32, _P, C.c_int32]),
@@ -90,7 +109,7 @@ SYMBOLS = {
 
 _lib = None
 
-_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "model.hip", "moments_kernels.hip",
+_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "model.hip", "moments_kernels.hip",
                os.path.join("..", "..", "include", "iwae_amd.h"))
 
 

@@ -1,0 +1,450 @@
+// Annealed importance sampling with HMC transitions (iwae_ais, include/iwae_amd.h; Neal 2001; Wu, Burda, Salakhutdinov & Grosse 2017): DESIGN.md section 15.
+//   ais_pad_kernel      a Keras kernel of the float32 master parameters -> both orientations, padded to multiples of 16 with zeros
+//   ais_init_kernel     chain state: e_0 (from z0 when given), log_w = 0, h = step_size, accept count = 0
+//   ais_chain_kernel    transitions [t0, t1) of 64 chain rows per workgroup, everything between two launches in one: per leapfrog step the
+//                       decoder forward, log p(x|z), the residual s = x - sigmoid(l) consumed at once into s W3^T, the two tanh-derivative
+//                       products, W1^T and the leapfrog update; Philox momenta and uniforms, accept step, log_w increment, step adaptation
+//   ais_finish_kernel   z = mu + sigma e, log_px = LSE_c log_w - log C (double), effective sample size
+//   ais_accept_rate_kernel   mean of the accept flags per transition, fixed order
+// Blocking: a wave owns 16 chain rows through every layer, forward and backward (v_mfma_f32_16x16x4_f32: the products are float32 fmaf chains
+// in k order, so a row's numbers do not depend on the rows beside it); its activations z, g1, g2 live in a private LDS strip each and are
+// overwritten in place by the backward pass (d2 over g2, d1 over g1, the residual tile over z); the workgroup's four waves share the weight
+// slabs (16 in-features x <= 208 out-features), fetched from L2 into registers one slab ahead and handed over through LDS between two
+// barriers.  Every loop has a host-known trip count; rows beyond R repeat row R - 1 and store nothing.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "kernels.h"
+
+namespace iwae {
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) float f32x4v;
+#define AIS_LOG2E 1.4426950408889634f
+#define AIS_LN2 0.6931471805599453f
+#define AIS_HALF_LOG_2PI 0.9189385332046727f
+constexpr int AIS_THREADS = 256;
+
+__host__ __device__ inline int ais_pz(int Dp) { return (Dp > 16 * AIS_TPO ? Dp : 16 * AIS_TPO) + 4; }      // pitch of the z strip (also holds a residual tile)
+
+// tanh through one hardware exp2 (fp32_kernels.hip's tanh_f32): absolute error <= ~1.5e-7
+__device__ __forceinline__ float ais_tanh(float x) {
+    const float t = __expf(2.0f * fabsf(x));
+    return __builtin_copysignf(1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f), x);
+}
+
+// Philox4x32-10 + Box-Muller exactly as kernels.hip draws them: counter = (row_lo, row_hi, (stream << 24) | d4, step), key = seed
+__device__ __forceinline__ void ais_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)c0 * 0xD2511F53ull, p1 = (unsigned long long)c2 * 0xCD9E8D57ull;
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__device__ __forceinline__ void ais_normal4(uint64_t grow, uint32_t d4, uint32_t stream, uint32_t step, uint64_t seed, float n[4]) {
+    uint32_t r[4];
+    ais_philox((uint32_t)grow, (uint32_t)(grow >> 32), (stream << 24) | d4, step, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    const float s24 = 5.9604644775390625e-08f;   // 2^-24
+    const float u0 = ((float)(r[0] >> 8) + 0.5f) * s24, u1 = ((float)(r[1] >> 8) + 0.5f) * s24;
+    const float u2 = ((float)(r[2] >> 8) + 0.5f) * s24, u3 = ((float)(r[3] >> 8) + 0.5f) * s24;
+    const float ra = __builtin_amdgcn_sqrtf(-2.0f * __logf(u0)), rb = __builtin_amdgcn_sqrtf(-2.0f * __logf(u2));
+    n[0] = ra * __builtin_amdgcn_cosf(u1); n[1] = ra * __builtin_amdgcn_sinf(u1);
+    n[2] = rb * __builtin_amdgcn_cosf(u3); n[3] = rb * __builtin_amdgcn_sinf(u3);
+}
+__device__ __forceinline__ float ais_uniform(uint64_t grow, uint32_t step, uint64_t seed) {
+    uint32_t r[4];
+    ais_philox((uint32_t)grow, (uint32_t)(grow >> 32), 4u << 24, step, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    return ((float)(r[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+}
+
+__device__ __forceinline__ float ais_rowsum(float v) {      // over the 16 lanes n16 of a quad group: every lane gets the same bits
+    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
+    return v;
+}
+
+__global__ __launch_bounds__(AIS_THREADS) void ais_pad_kernel(AisPrepArgs a) {
+    const long idx = (long)blockIdx.x * AIS_THREADS + threadIdx.x;
+    if (idx >= (long)a.Kp * a.Np) return;
+    const int k = (int)(idx / a.Np), n = (int)(idx - (long)k * a.Np);
+    const float v = (k < a.K && n < a.N) ? a.src[(size_t)k * a.N + n] : 0.0f;
+    a.dst[idx] = v;
+    if (a.dstT) a.dstT[(size_t)n * a.Kp + k] = v;
+}
+
+__global__ __launch_bounds__(AIS_THREADS) void ais_init_kernel(AisInitArgs a) {
+    const long r = (long)blockIdx.x * AIS_THREADS + threadIdx.x;
+    if (r >= a.R) return;
+    a.log_w[r] = 0.0;
+    a.h[r] = a.step;
+    a.nacc[r] = 0;
+    if (a.z0) {
+        const int n = (int)(r % a.N);
+        for (int d = 0; d < a.D; ++d) {
+            const float z = a.z0[(size_t)r * a.D + d];
+            a.e[(size_t)r * a.D + d] = a.head ? (z - a.head[(size_t)n * a.ldh + d]) / a.head[(size_t)n * a.ldh + a.soff + d] : z;
+        }
+    }
+}
+
+// acc[t] += strip[16 rows][16 nkb] * W[16 nkb rows][16 cnt columns], t < cnt: W row-major with ldw floats per row, already at its first row and
+// column.  Whole workgroup: the slab of 16 weight rows goes global -> registers (one slab ahead) -> LDS between two barriers.
+__device__ __forceinline__ void ais_wg_gemm(const float* strip, int pa, int nkb, const float* W, int ldw, int cnt, float* slab,
+                                            f32x4v (&acc)[AIS_NT], int tid, int n16, int q) {
+    const int gpr = 4 * cnt;                     // 16-byte granules per slab row
+    int goff[4], soff[4];
+    bool ok[4];
+    float4 pre[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int g = tid + AIS_THREADS * u, r = g / gpr, cq = g - r * gpr;
+        ok[u] = r < 16;
+        goff[u] = r * ldw + 4 * cq;
+        soff[u] = r * AIS_SLABP + 4 * cq;
+        pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok[u]) pre[u] = *(const float4*)(W + goff[u]);
+    }
+    for (int kb = 0; kb < nkb; ++kb) {
+        __syncthreads();          // every wave has left the previous slab (and the strips of the layer before are written)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (ok[u]) *(float4*)(slab + soff[u]) = pre[u];
+        __syncthreads();
+        if (kb + 1 < nkb) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (ok[u]) pre[u] = *(const float4*)(W + (size_t)(kb + 1) * 16 * ldw + goff[u]);
+        }
+        const float4 av = *(const float4*)(strip + n16 * pa + 16 * kb + 4 * q);      // row n16, k = 16 kb + 4 q + j at .j
+        const float a4[4] = {av.x, av.y, av.z, av.w};
+        const float* sl = slab + 4 * q * AIS_SLABP + n16;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int t = 0; t < AIS_NT; ++t)
+                if (t < cnt) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], sl[j * AIS_SLABP + 16 * t], acc[t], 0, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem_ais[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n16 = lane & 15, q = lane >> 4;
+    const int PZ = ais_pz(a.Dp), PH = a.Hp + 4, WST = 16 * (PZ + 2 * PH);
+    float* zs = smem_ais + wave * WST;            // z rows, later a 64-pixel tile of the residual s
+    float* g1s = zs + 16 * PZ;                    // g1, later dpre1
+    float* g2s = g1s + 16 * PH;                   // g2, later dpre2
+    float* slab = smem_ais + 4 * WST;
+    const int dt = a.Dp >> 4, ht = a.Hp >> 4, xt = a.Xp >> 4, npass = (xt + AIS_TPO - 1) / AIS_TPO;
+    const long m0 = (long)blockIdx.x * 64 + wave * 16;
+
+    // the lane's four rows 4q + r: storage row (clamped) and image.  e and p stay in registers in the accumulator layout (row 4q + r,
+    // feature 16 t + n16); mu and sigma are re-read where they are used (the heads of <= 16 images: L1 hits) -- 64 registers the MFMA
+    // accumulators need more
+    long row[4]; bool live[4]; const float* xrow[4]; const float* hrow[4];
+    float e[AIS_DT][4], p[AIS_DT][4];
+    float lsum[4], hstep[4]; int nacc[4];
+    auto mu_at = [&](int r, int col) { return a.head ? hrow[r][col] : 0.0f; };
+    auto sg_at = [&](int r, int col) { return a.head ? hrow[r][a.soff + col] : 1.0f; };
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long rr = m0 + 4 * q + r;
+        live[r] = rr < a.R;
+        row[r] = live[r] ? rr : a.R - 1;
+        const int n = (int)(row[r] % a.N);
+        xrow[r] = a.x + (size_t)n * a.X;
+        hrow[r] = a.head + (size_t)n * a.ldh;
+        float ls = 0.0f;
+#pragma unroll
+        for (int t = 0; t < AIS_DT; ++t) {
+            const int col = 16 * t + n16;
+            const bool in = t < dt && col < a.D;
+            e[t][r] = in ? a.e[(size_t)row[r] * a.D + col] : 0.0f;
+            p[t][r] = 0.0f;
+            if (in) ls += __logf(sg_at(r, col));
+        }
+        lsum[r] = ais_rowsum(ls);                 // sum_d log sigma_d
+        hstep[r] = a.h[row[r]];
+        nacc[r] = a.nacc[row[r]];
+    }
+    const float dc = (float)a.D * AIS_HALF_LOG_2PI;
+
+    // lj = log p(x|z) + log p(z) and l0 = log N(e; 0, I) - sum log sigma at z = mu + sigma e, then the kick p -= hh grad U_t with
+    // grad U_t = (1 - bt) e - bt sigma (grad_z log p(x|z) - z)
+    auto eval_kick = [&](float (&lj)[4], float (&l0)[4], const float bt, const float (&hh)[4]) {
+        f32x4v acc[AIS_NT], dg2[AIS_NT];
+        float sz[4] = {0.f, 0.f, 0.f, 0.f}, se[4] = {0.f, 0.f, 0.f, 0.f}, lp[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < AIS_DT; ++t) {
+            if (t < dt) {
+                const int col = 16 * t + n16;
+                const bool in = col < a.D;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float z = in ? fmaf(sg_at(r, col), e[t][r], mu_at(r, col)) : 0.0f;
+                    zs[(4 * q + r) * PZ + col] = z;
+                    sz[r] = fmaf(z, z, sz[r]);
+                    se[r] = fmaf(e[t][r], e[t][r], se[r]);
+                }
+            }
+        }
+        // ---- g1 = tanh(z W1 + b1), g2 = tanh(g1 W2 + b2)
+#pragma unroll
+        for (int t = 0; t < AIS_NT; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+        ais_wg_gemm(zs, PZ, dt, a.W1, a.Hp, ht, slab, acc, tid, n16, q);
+#pragma unroll
+        for (int t = 0; t < AIS_NT; ++t) {
+            if (t < ht) {
+                const float b = a.b1[16 * t + n16];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) g1s[(4 * q + r) * PH + 16 * t + n16] = ais_tanh(acc[t][r] + b);
+                acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        ais_wg_gemm(g1s, PH, ht, a.W2, a.Hp, ht, slab, acc, tid, n16, q);
+#pragma unroll
+        for (int t = 0; t < AIS_NT; ++t) {
+            if (t < ht) {
+                const float b = a.b2[16 * t + n16];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) g2s[(4 * q + r) * PH + 16 * t + n16] = ais_tanh(acc[t][r] + b);
+            }
+            dg2[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+        }
+        // ---- output layer, 64 pixels at a time: logits -> log p(x|z) and s = x - sigmoid(l) -> dg2 += s W3^T (s never leaves the workgroup)
+        for (int pass = 0; pass < npass; ++pass) {
+            const int c0 = 16 * AIS_TPO * pass, cnt = min(AIS_TPO, xt - AIS_TPO * pass);
+#pragma unroll
+            for (int t = 0; t < AIS_TPO; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            ais_wg_gemm(g2s, PH, ht, a.W3 + c0, a.Xp, cnt, slab, acc, tid, n16, q);
+            // sum_n x l - softplus(l) = sum_n (x - 1/2) l - |l| / 2 - log(1 + e^-|l|), the logarithms as one log2 of the product (dec_fwd_f32_kernel's form)
+            float s_xl[4] = {0.f, 0.f, 0.f, 0.f}, s_al[4] = {0.f, 0.f, 0.f, 0.f}, prod[4] = {1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+            for (int t = 0; t < AIS_TPO; ++t) {
+                if (t < cnt) {
+                    const int col = c0 + 16 * t + n16;
+                    const bool in = col < a.X;
+                    const float b = a.b3[col];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float x1 = in ? xrow[r][col] : 0.0f;
+                        const float l = in ? acc[t][r] + b : 0.0f, xm = in ? x1 - 0.5f : 0.0f;
+                        const float ex = __builtin_amdgcn_exp2f(-fabsf(l) * AIS_LOG2E);      // exp(-|l|)
+                        s_xl[r] = fmaf(xm, l, s_xl[r]);
+                        s_al[r] += fabsf(l);
+                        prod[r] = in ? fmaf(prod[r], ex, prod[r]) : prod[r];
+                        zs[(4 * q + r) * PZ + 16 * t + n16] = in ? xm - __builtin_copysignf(__builtin_amdgcn_rcpf(1.0f + ex) - 0.5f, l) : 0.0f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lp[r] += s_xl[r] - 0.5f * s_al[r] - AIS_LN2 * __builtin_amdgcn_logf(prod[r]);
+            ais_wg_gemm(zs, PZ, cnt, a.W3T + (size_t)c0 * a.Hp, a.Hp, ht, slab, dg2, tid, n16, q);
+        }
+        // ---- dpre2 = dg2 (1 - g2^2) over g2; dpre1 = (dpre2 W2^T)(1 - g1^2) over g1; dz = dpre1 W1^T
+#pragma unroll
+        for (int t = 0; t < AIS_NT; ++t) {
+            if (t < ht) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float* at = g2s + (4 * q + r) * PH + 16 * t + n16;
+                    const float y = *at;
+                    *at = dg2[t][r] * (1.0f - y * y);
+                }
+            }
+            acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+        }
+        ais_wg_gemm(g2s, PH, ht, a.W2T, a.Hp, ht, slab, acc, tid, n16, q);
+#pragma unroll
+        for (int t = 0; t < AIS_NT; ++t) {
+            if (t < ht) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float* at = g1s + (4 * q + r) * PH + 16 * t + n16;
+                    const float y = *at;
+                    *at = acc[t][r] * (1.0f - y * y);
+                }
+                acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        ais_wg_gemm(g1s, PH, ht, a.W1T, a.Dp, dt, slab, acc, tid, n16, q);
+#pragma unroll
+        for (int t = 0; t < AIS_DT; ++t) {
+            if (t < dt) {
+                const int col = 16 * t + n16;
+                if (col < a.D) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float sg = sg_at(r, col), z = fmaf(sg, e[t][r], mu_at(r, col));
+                        p[t][r] -= hh[r] * ((1.0f - bt) * e[t][r] - bt * (sg * (acc[t][r] - z)));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            lj[r] = ais_rowsum(lp[r]) + (-0.5f * ais_rowsum(sz[r]) - dc);
+            l0[r] = -0.5f * ais_rowsum(se[r]) - lsum[r] - dc;
+        }
+    };
+    auto kinetic = [&](float (&kin)[4]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float s = 0.0f;
+#pragma unroll
+            for (int t = 0; t < AIS_DT; ++t) s = fmaf(p[t][r], p[t][r], s);
+            kin[r] = 0.5f * ais_rowsum(s);
+        }
+    };
+
+    for (int tt = a.t0; tt < a.t1; ++tt) {
+        const float bt = a.betas[tt + 1], bp = a.betas[tt];
+        float lj[4], l0[4], u0[4], k0[4], half[4];
+        // momentum of transition tt + 1: the caller's, or Philox stream 3 at step0 + tt + 1 -- one draw of four features per lane and turn,
+        // handed to the lanes that own them through the wave's z strip (free between two evaluations)
+        if (!a.mom) {
+            const int dq = a.Dp >> 2;
+#pragma unroll 1
+            for (int idx = lane; idx < 16 * dq; idx += 64) {
+                const int rr = idx / dq, d4 = idx - rr * dq;
+                const long rw = min(m0 + rr, a.R - 1);
+                float nrm[4];
+                ais_normal4(a.row_offset + (uint64_t)(rw % a.N) * (uint64_t)a.C + (uint64_t)(rw / a.N), (uint32_t)d4, 3u, a.step0 + (uint32_t)tt + 1u, a.seed, nrm);
+                *(float4*)(zs + rr * PZ + 4 * d4) = make_float4(nrm[0], nrm[1], nrm[2], nrm[3]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < AIS_DT; ++t) {
+            const int col = 16 * t + n16;
+            const bool in = t < dt && col < a.D;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = 0.0f;
+                if (in) v = a.mom ? a.mom[((size_t)tt * a.R + row[r]) * a.D + col] : zs[(4 * q + r) * PZ + col];
+                p[t][r] = v;
+            }
+        }
+        kinetic(k0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) half[r] = 0.5f * hstep[r];
+        // evaluation 0 at the transition's start (weight increment, U_t(e), first half kick), then L leapfrog steps
+        for (int l = 0; l <= a.L; ++l) {
+            if (l > 0) {
+#pragma unroll
+                for (int t = 0; t < AIS_DT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e[t][r] = fmaf(hstep[r], p[t][r], e[t][r]);
+            }
+            float hh[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) hh[r] = (l == 0 || l == a.L) ? half[r] : hstep[r];
+            eval_kick(lj, l0, bt, hh);
+            if (l == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (live[r] && n16 == 0) a.log_w[row[r]] += (double)(bt - bp) * (double)(lj[r] - l0[r]);
+                    u0[r] = -((1.0f - bt) * l0[r] + bt * lj[r]);
+                }
+            }
+        }
+        float k1[4];
+        kinetic(k1);
+        if (!a.unif && lane < 16) {      // the accept uniforms of the wave's 16 rows (Philox stream 4), one per lane, through the strip
+            const long rw = min(m0 + lane, a.R - 1);
+            zs[lane * PZ] = ais_uniform(a.row_offset + (uint64_t)(rw % a.N) * (uint64_t)a.C + (uint64_t)(rw / a.N), a.step0 + (uint32_t)tt + 1u, a.seed);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float u1 = -((1.0f - bt) * l0[r] + bt * lj[r]);
+            const float dH = ((u1 + k1[r]) - u0[r]) - k0[r];
+            const float un = a.unif ? a.unif[(size_t)tt * a.R + row[r]] : zs[(4 * q + r) * PZ];
+            const bool take = logf(un) < -dH;             // (a NaN dH rejects)
+            if (live[r] && n16 == 0) {
+                if (a.dH) a.dH[(size_t)tt * a.R + row[r]] = dH;
+                if (a.accepted) a.accepted[(size_t)tt * a.R + row[r]] = take ? 1 : 0;
+            }
+            // the state in HBM is the chain's position between transitions: stored on accept, read back on reject
+#pragma unroll
+            for (int t = 0; t < AIS_DT; ++t) {
+                const int col = 16 * t + n16;
+                if (t < dt && col < a.D) {
+                    float* at = a.e + (size_t)row[r] * a.D + col;
+                    if (take) { if (live[r]) *at = e[t][r]; }
+                    else e[t][r] = *at;
+                }
+            }
+            nacc[r] += take ? 1 : 0;
+            if (a.adapt) {
+                const float mean = (float)nacc[r] / (float)(tt + 1);
+                hstep[r] = fminf(fmaxf(hstep[r] * (mean > 0.65f ? 1.02f : 0.98f), 1e-4f), 0.5f);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (live[r] && n16 == 0) { a.h[row[r]] = hstep[r]; a.nacc[row[r]] = nacc[r]; }
+    }
+}
+
+__global__ __launch_bounds__(AIS_THREADS) void ais_z_kernel(AisFinishArgs a) {
+    const long idx = (long)blockIdx.x * AIS_THREADS + threadIdx.x;
+    if (idx >= a.R * a.D) return;
+    const long r = idx / a.D;
+    const int d = (int)(idx - r * a.D), n = (int)(r % a.N);
+    const float ev = a.e[idx];
+    a.z[idx] = a.head ? fmaf(a.head[(size_t)n * a.ldh + a.soff + d], ev, a.head[(size_t)n * a.ldh + d]) : ev;
+}
+// one thread per image, its C chains in chain order
+__global__ __launch_bounds__(AIS_THREADS) void ais_finish_kernel(AisFinishArgs a) {
+    const int n = blockIdx.x * AIS_THREADS + threadIdx.x;
+    if (n >= a.N) return;
+    double mx = -INFINITY;
+    for (int c = 0; c < a.C; ++c) mx = fmax(mx, a.log_w[(size_t)c * a.N + n]);
+    double s1 = 0.0, s2 = 0.0;
+    for (int c = 0; c < a.C; ++c) {
+        const double w = exp(a.log_w[(size_t)c * a.N + n] - mx);
+        s1 += w; s2 += w * w;
+    }
+    a.log_px[n] = mx + log(s1) - log((double)a.C);
+    if (a.ess) a.ess[n] = (float)(s1 * s1 / s2);
+}
+// one workgroup per transition: the R flags summed as integers (exact, so the order is immaterial), then one division
+__global__ __launch_bounds__(AIS_THREADS) void ais_accept_rate_kernel(const uint8_t* accepted, long R, float* rate) {
+    __shared__ int part[AIS_THREADS];
+    const uint8_t* f = accepted + (size_t)blockIdx.x * R;
+    int s = 0;
+    for (long i = threadIdx.x; i < R; i += AIS_THREADS) s += f[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = AIS_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) rate[blockIdx.x] = (float)part[0] / (float)R;
+}
+
+}  // namespace
+
+size_t ais_chain_lds_bytes(int Dp, int Hp) { return ((size_t)4 * 16 * (ais_pz(Dp) + 2 * (Hp + 4)) + (size_t)16 * AIS_SLABP) * 4; }
+void launch_ais_pad(const AisPrepArgs& a, hipStream_t st) {
+    const long n = (long)a.Kp * a.Np;
+    hipLaunchKernelGGL(ais_pad_kernel, dim3((unsigned)((n + AIS_THREADS - 1) / AIS_THREADS)), dim3(AIS_THREADS), 0, st, a);
+}
+void launch_ais_init(const AisInitArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(ais_init_kernel, dim3((unsigned)((a.R + AIS_THREADS - 1) / AIS_THREADS)), dim3(AIS_THREADS), 0, st, a);
+}
+void launch_ais_chain(const AisChainArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(ais_chain_kernel, dim3((unsigned)((a.R + 63) / 64)), dim3(AIS_THREADS), ais_chain_lds_bytes(a.Dp, a.Hp), st, a);
+}
+void launch_ais_finish(const AisFinishArgs& a, hipStream_t st) {
+    if (a.z) hipLaunchKernelGGL(ais_z_kernel, dim3((unsigned)((a.R * a.D + AIS_THREADS - 1) / AIS_THREADS)), dim3(AIS_THREADS), 0, st, a);
+    hipLaunchKernelGGL(ais_finish_kernel, dim3((a.N + AIS_THREADS - 1) / AIS_THREADS), dim3(AIS_THREADS), 0, st, a);
+}
+void launch_ais_accept_rate(const uint8_t* accepted, int T, long R, float* rate, hipStream_t st) {
+    hipLaunchKernelGGL(ais_accept_rate_kernel, dim3(T), dim3(AIS_THREADS), 0, st, accepted, R, rate);
+}
+
+}  // namespace iwae

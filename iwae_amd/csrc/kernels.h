@@ -526,4 +526,49 @@ void launch_agg_merge(const AggMergeArgs& a, hipStream_t st);
 void launch_agg_untranspose(const float* src, long SN, int D, float* dst, hipStream_t st);
 void launch_agg_reduce(const AggReduceArgs& a, hipStream_t st);
 
+// ---- annealed importance sampling (ais_kernels.hip; iwae_ais): C HMC chains per image through T temperatures, float32.  Chain row
+// r = c N + n (the reference's [C, N] order) keeps its state e [R][D], log_w [R] (double), step size h [R] and accept count [R] in HBM between
+// launches; ais_chain_kernel runs transitions [t0, t1) of 64 rows per workgroup, a wave owning 16 rows.  Philox row of chain (n, c):
+// row_offset + n C + c (iwae_eval_llh's at k = C).
+#define AIS_NT 13               // out-feature tiles (16 each) a wave accumulates: hidden width <= 208
+#define AIS_DT 8                // latent tiles: n_latent <= 128
+#define AIS_TPO 4               // pixel tiles per pass of the output layer (the residual tile that feeds s W3^T)
+#define AIS_SLABP 212           // weight slab pitch in floats (16 in-features x <= 208 out-features)
+struct AisPrepArgs {                  // ais_pad_kernel: src [K][N] (Keras kernel inside the master parameters) -> dst [Kp][Np] and dstT [Np][Kp], pads zero
+    const float* src; int K, N, Kp, Np;
+    float *dst, *dstT;                // dstT null: not wanted (biases: K = 1)
+};
+struct AisInitArgs {                  // ais_init_kernel: log_w = 0, h = step, accepts = 0; with z0: e = (z0 - mu) / sigma
+    const float* z0;                  // [R][D] or null (e already holds the draws)
+    const float* head; int ldh, soff; // encoder heads per image, or null (prior init: mu = 0, sigma = 1)
+    int N, D; long R;
+    float step;
+    float* e; double* log_w; float* h; int* nacc;
+};
+struct AisChainArgs {
+    const float *W1, *W1T, *W2, *W2T, *W3, *W3T, *b1, *b2, *b3;      // padded to multiples of 16 (ais_pad_kernel): W [in][out], WT [out][in]
+    int D, H, X, Dp, Hp, Xp;
+    const float* x;                   // [N][X]
+    const float* head; int ldh, soff; // mu at head[n ldh + d], sigma soff further; null: prior init
+    int N, C; long R;
+    const float* betas;               // [T + 1] on the device
+    int t0, t1, L, adapt;
+    const float* mom; const float* unif;      // the caller's noise [T][R][D], [T][R] or null: Philox streams 3 / 4 at step0 + t
+    uint64_t seed, row_offset; uint32_t step0;
+    float* e; double* log_w; float* h; int* nacc;
+    float* dH; uint8_t* accepted;     // [T][R] or null
+};
+struct AisFinishArgs {                // ais_finish_kernel: z = mu + sigma e; per image log_px = LSE_c log_w - log C and the effective sample size
+    const float* head; int ldh, soff;
+    int N, C, D; long R;
+    const float* e; const double* log_w;
+    float* z; double* log_px; float* ess;      // z, ess: null = not wanted
+};
+size_t ais_chain_lds_bytes(int Dp, int Hp);
+void launch_ais_pad(const AisPrepArgs& a, hipStream_t st);
+void launch_ais_init(const AisInitArgs& a, hipStream_t st);
+void launch_ais_chain(const AisChainArgs& a, hipStream_t st);
+void launch_ais_finish(const AisFinishArgs& a, hipStream_t st);
+void launch_ais_accept_rate(const uint8_t* accepted, int T, long R, float* rate, hipStream_t st);
+
 }  // namespace iwae

@@ -23,6 +23,8 @@ using namespace iwae;
 static_assert(sizeof(iwae_config) == 64 && offsetof(iwae_config, struct_size) == 0 && offsetof(iwae_config, seed) == 32 && offsetof(iwae_config, cond_dim) == 48 &&
               offsetof(iwae_config, cond_prior) == 52 && offsetof(iwae_config, precision) == 56, "iwae_config layout is part of the ABI (iwae_amd/_capi.py)");
 static_assert(sizeof(iwae_scalars) == 64 && sizeof(iwae_tensors) == 12 * sizeof(void*), "ABI struct layout");
+static_assert(sizeof(iwae_ais_options) == 72 && offsetof(iwae_ais_options, betas) == 16 && offsetof(iwae_ais_options, step_size) == 24 && offsetof(iwae_ais_options, z0) == 40 &&
+              offsetof(iwae_ais_options, unif) == 64 && sizeof(iwae_ais_outputs) == 10 * sizeof(void*), "iwae_ais_options / iwae_ais_outputs layout is part of the ABI (iwae_amd/_capi.py)");
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -112,10 +114,11 @@ static int load_rccl() {
     } while (0)
 
 // kernels iwae_enable_timing brackets with HIP events (on the stream each is launched on); names: iwae_kernel_time
-enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_COUNT };
+enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_COUNT };
 static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgrad_out", "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent",
                                                  "latent_bwd", "encoder_fwd", "reduce_adam", "decoder_bwd",
-                                                 "allreduce_enc", "allreduce_dec"};      // (the data-parallel step's two ncclAllReduce calls, each on its own stream)
+                                                 "allreduce_enc", "allreduce_dec",       // (the data-parallel step's two ncclAllReduce calls, each on its own stream)
+                                                 "ais_chain"};                           // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
 
 // What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
 // images and samples in chunks and needs log_w only.
@@ -203,6 +206,7 @@ struct StepOptions {
     bool allow_f32_bern_fused = true;      // float32 mode: log p(x|z) (and, in a training step, s) in the output layer's GEMM epilogue (option no_f32_bern_fused)
     int eval_rows = 0;                        // data rows per evaluator launch (option eval_rows): images x samples, k chunked beyond it; 0 = eval_rows_auto()
     int grid_chunk = 0;                       // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT)
+    int ais_t_chunk = 0;                      // iwae_ais: transitions per launch of ais_chain_kernel (option ais_t_chunk; 0 = AIS_T_CHUNK_DEFAULT)
 };
 
 // The kernels and streams of one bf16 step.  plan_step decides all of it from shapes and options before forward_impl launches or allocates
@@ -290,6 +294,9 @@ struct iwae_model {
     // iwae_aggregate_posterior's buffers: the images, heads and draws, the component tables, a sample tile's z / own terms and range partials,
     // the per-sample densities (log_qzd transposed [Dpad][S N]) and the double sums
     struct AggWs { DevBuf x, xP, head, eps, mu, inv, invd, nls, nls_sum, zT, shT, dim_part, jmax, jsum, lqz, lqzdT, lqzd, part, out; } agg;
+    // iwae_ais's buffers: the images, heads, the decoder's padded weights, the schedule, the chain state (e, log_w, h, accept counts), the
+    // caller's noise and initial states when they arrive on the host, and the outputs
+    struct AisWs { DevBuf x, xP, head, wpad, betas, e, logw, h, nacc, z0, mom, unif, dH, acc, rate, z, lpx, ess; } ais;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
@@ -2566,6 +2573,11 @@ void iwae_destroy(iwae_handle m) {
                         &g.lqzd, &g.part, &g.out};
         for (DevBuf* b : bb) free_buf(*b);
     }
+    {
+        iwae_model::AisWs& g = m->ais;
+        DevBuf* bb[] = {&g.x, &g.xP, &g.head, &g.wpad, &g.betas, &g.e, &g.logw, &g.h, &g.nacc, &g.z0, &g.mom, &g.unif, &g.dH, &g.acc, &g.rate, &g.z, &g.lpx, &g.ess};
+        for (DevBuf* b : bb) free_buf(*b);
+    }
     BlockWs* bw[] = {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior};
     for (BlockWs* w : bw) {
         DevBuf* bb[] = {&w->h1P, &w->h2P, &w->head, &w->dheadP, &w->d2P, &w->d1P, &w->dx};
@@ -2823,6 +2835,7 @@ int iwae_set_option(iwae_handle m, const char* name, int64_t value) {
     else if (n == "no_wg7") m->opt.allow_wg7 = !on;                       // the 16-wave weight-gradient shapes everywhere
     else if (n == "wg9") m->opt.wg_shape9 = iv;                           // bit mask: layers that take the 8 + 8-wave / 128-feature wgradws shape
     else if (n == "grid_chunk") m->opt.grid_chunk = iv > 0 ? std::max(16, iv) : 0;      // iwae_grid_posterior: grid points per chunk (0: the default)
+    else if (n == "ais_t_chunk") m->opt.ais_t_chunk = iv > 0 ? iv : 0;                 // iwae_ais: transitions per launch (0: the default)
     else if (n == "eval_rows") m->opt.eval_rows = iv > 0 ? std::max(64, iv) : 0;       // data rows per evaluator launch
     else if (n == "no_bern_pipe") m->opt.allow_bern_pipe = !on;           // the Bernoulli forward on dense_kernel<EPI_BERN>
     else if (n == "no_block_fused") m->opt.allow_block_fused = !on;       // a BasicBlock on few rows as three dense_kernel launches
@@ -3487,6 +3500,150 @@ int iwae_aggregate_posterior(iwae_handle m, const float* x, int32_t N, int32_t S
     }
     HIPCHK(hipStreamSynchronize(st));
     if (!eps) m->noise_step += 1;
+    m->have_forward = false;
+    return IWAE_OK;
+}
+
+// Transitions per launch of ais_chain_kernel (option ais_t_chunk).  Measured at the timing workload (N = 1 000, C = 16, L = 10, reference
+// dims; profiles/ais_time.txt): one transition takes 4.37 ms there, a launch of 4 takes 17.5 ms -- well under the 50 ms a launch may hold a
+// shared machine -- and the 125 launches of a T = 500 run cost nothing measurable (2.187 s in the kernel of 2.188 s wall).
+#define AIS_T_CHUNK_DEFAULT 4
+
+// Annealed importance sampling with HMC chains (Neal 2001; Wu et al. 2017): DESIGN.md section 15
+int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o, const iwae_ais_outputs* out) {
+    if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "ais: need x, options and outputs");
+    if (o->struct_size != sizeof(iwae_ais_options)) return fail(IWAE_ERR_ARG, "ais: iwae_ais_options.struct_size must be sizeof(iwae_ais_options) = " + std::to_string(sizeof(iwae_ais_options)));
+    if (!out->log_px || !o->betas) return fail(IWAE_ERR_ARG, "ais: betas and log_px are required");
+    if (N <= 0 || o->C <= 0 || o->T <= 0 || o->L <= 0) return fail(IWAE_ERR_ARG, "ais: N, C, T and L must be positive");
+    if (!(o->step_size > 0.0f)) return fail(IWAE_ERR_ARG, "ais: step_size must be positive");
+    if (o->init != IWAE_AIS_INIT_ENCODER && o->init != IWAE_AIS_INIT_PRIOR) return fail(IWAE_ERR_ARG, "ais: init must be IWAE_AIS_INIT_ENCODER or IWAE_AIS_INIT_PRIOR");
+    const int given = (o->eps0 != nullptr) + (o->mom != nullptr) + (o->unif != nullptr);
+    if (given != 0 && given != 3) return fail(IWAE_ERR_ARG, "ais: eps0, mom and unif come all three or not at all");
+    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "ais: only the 1-layer model");
+    if (m->C != 0 || m->has_prior) return fail(IWAE_ERR_ARG, "ais: only the unconditional model (cond_dim = 0, no learned prior)");
+    if ((int64_t)N * o->C > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "ais: too large (N * C > 2^27 chains)");
+    const int D = m->D[0], H = m->H[0], X = m->X, Dp = round_up(D, 16), Hp = round_up(H, 16), Xp = round_up(X, 16), Dh = m->Dp[0];
+    if (Hp > 16 * AIS_NT || Dp > 16 * AIS_DT) return fail(IWAE_ERR_ARG, "ais: needs n_hidden <= " + std::to_string(16 * AIS_NT) + " and n_latent <= " + std::to_string(16 * AIS_DT));
+    HIPCHK(hipSetDevice(m->cfg.device));
+    const int T = o->T, C = o->C;
+    const long R = (long)N * C;
+    std::vector<float> betas(T + 1);
+    HIPCHK(hipMemcpy(betas.data(), o->betas, (size_t)(T + 1) * 4, hipMemcpyDefault));
+    for (float b : betas) if (!(b >= 0.0f && b <= 1.0f)) return fail(IWAE_ERR_ARG, "ais: every beta must lie in [0, 1]");
+    CHK(join_side(m));      // the parameters a deferred update may still be writing
+    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
+    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
+    hipStream_t st = m->stream;
+    iwae_model::AisWs& w = m->ais;
+    const bool user_noise = given == 3, prior = o->init == IWAE_AIS_INIT_PRIOR;
+    const float* xd = x;
+    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * X * 4)); xd = ptr<float>(w.x); }
+    // ---- base density: the encoder heads in the eval precision, or N(0, I)
+    const float* head = nullptr;
+    int ldh = 0;
+    if (!prior) {
+        CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
+        if (out->q_mu) HIPCHK(hipMemcpy2DAsync(out->q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
+        if (out->q_sigma) HIPCHK(hipMemcpy2DAsync(out->q_sigma, (size_t)D * 4, head + Dh, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
+    } else if (out->q_mu || out->q_sigma) {
+        CHK(ensure(w.head, (size_t)N * D * 4, st));
+        if (out->q_mu) { HIPCHK(hipMemsetAsync(w.head.p, 0, (size_t)N * D * 4, st)); CHK(copy_out(m, out->q_mu, w.head.p, (size_t)N * D * 4)); }
+        if (out->q_sigma) { HIPCHK(hipMemsetD32Async((hipDeviceptr_t)w.head.p, 0x3f800000, (size_t)N * D, st)); CHK(copy_out(m, out->q_sigma, w.head.p, (size_t)N * D * 4)); }
+    }
+    // ---- the decoder's weights in both orientations, padded to multiples of 16 (src/iwae1.py:72-75; Keras kernels [in][out])
+    const KerasLayer* d1 = &m->klayers[m->dec1[0].sub[0]];
+    const size_t nW1 = (size_t)Dp * Hp, nW2 = (size_t)Hp * Hp, nW3 = (size_t)Hp * Xp;
+    CHK(ensure(w.wpad, (2 * (nW1 + nW2 + nW3) + 2 * Hp + Xp) * 4, st));
+    float* wp = ptr<float>(w.wpad);
+    AisChainArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    {
+        float* W1 = wp; float* W1T = W1 + nW1; float* W2 = W1T + nW1; float* W2T = W2 + nW2; float* W3 = W2T + nW2; float* W3T = W3 + nW3;
+        float* b1 = W3T + nW3; float* b2 = b1 + Hp; float* b3 = b2 + Hp;
+        const AisPrepArgs jobs[6] = {{m->param + d1[0].offW, D, H, Dp, Hp, W1, W1T}, {m->param + d1[1].offW, H, H, Hp, Hp, W2, W2T},
+                                     {m->param + d1[2].offW, H, X, Hp, Xp, W3, W3T}, {m->param + d1[0].offb, 1, H, 1, Hp, b1, nullptr},
+                                     {m->param + d1[1].offb, 1, H, 1, Hp, b2, nullptr}, {m->param + d1[2].offb, 1, X, 1, Xp, b3, nullptr}};
+        for (const AisPrepArgs& j : jobs) launch_ais_pad(j, st);
+        HIPCHK(hipGetLastError());
+        ca.W1 = W1; ca.W1T = W1T; ca.W2 = W2; ca.W2T = W2T; ca.W3 = W3; ca.W3T = W3T; ca.b1 = b1; ca.b2 = b2; ca.b3 = b3;
+    }
+    // ---- chain state: e_0 = the caller's draws, (z0 - mu) / sigma, or what iwae_debug_eps(N, C, 0) returns at this step and offset
+    CHK(ensure(w.e, (size_t)R * D * 4, st));
+    CHK(ensure(w.logw, (size_t)R * 8, st));
+    CHK(ensure(w.h, (size_t)R * 4, st));
+    CHK(ensure(w.nacc, (size_t)R * 4, st));
+    CHK(ensure(w.lpx, (size_t)N * 8, st));
+    CHK(copy_in(m, w.betas, betas.data(), (size_t)(T + 1) * 4));
+    const float* z0d = o->z0;
+    if (o->z0 && !is_device_ptr(o->z0, m->cfg.device)) { CHK(copy_in(m, w.z0, o->z0, (size_t)R * D * 4)); z0d = ptr<float>(w.z0); }
+    if (!o->z0) {
+        if (user_noise) HIPCHK(hipMemcpyAsync(w.e.p, o->eps0, (size_t)R * D * 4, hipMemcpyDefault, st));
+        else {
+            EpsSrc e;
+            e.user = nullptr; e.B = N; e.seed = m->cfg.seed; e.row_offset = (uint64_t)m->batch_offset * (uint64_t)C; e.step = m->noise_step; e.stream = 0;
+            launch_eps_dump(e, N, C, D, ptr<float>(w.e), st);
+        }
+    }
+    AisInitArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.z0 = z0d; ia.head = head; ia.ldh = ldh; ia.soff = Dh; ia.N = N; ia.D = D; ia.R = R; ia.step = o->step_size;
+    ia.e = ptr<float>(w.e); ia.log_w = ptr<double>(w.logw); ia.h = ptr<float>(w.h); ia.nacc = ptr<int>(w.nacc);
+    launch_ais_init(ia, st);
+    HIPCHK(hipGetLastError());
+    const float *momd = o->mom, *unifd = o->unif;
+    if (user_noise && !is_device_ptr(o->mom, m->cfg.device)) { CHK(copy_in(m, w.mom, o->mom, (size_t)T * R * D * 4)); momd = ptr<float>(w.mom); }
+    if (user_noise && !is_device_ptr(o->unif, m->cfg.device)) { CHK(copy_in(m, w.unif, o->unif, (size_t)T * R * 4)); unifd = ptr<float>(w.unif); }
+    float* dHd = nullptr;
+    uint8_t* accd = nullptr;
+    if (out->dH) {
+        if (is_device_ptr(out->dH, m->cfg.device)) dHd = out->dH;
+        else { CHK(ensure(w.dH, (size_t)T * R * 4, st)); dHd = ptr<float>(w.dH); }
+    }
+    if (out->accepted || out->accept_rate) {
+        if (out->accepted && is_device_ptr(out->accepted, m->cfg.device)) accd = out->accepted;
+        else { CHK(ensure(w.acc, (size_t)T * R, st)); accd = ptr<uint8_t>(w.acc); }
+    }
+    ca.D = D; ca.H = H; ca.X = X; ca.Dp = Dp; ca.Hp = Hp; ca.Xp = Xp;
+    ca.x = xd; ca.head = head; ca.ldh = ldh; ca.soff = Dh; ca.N = N; ca.C = C; ca.R = R;
+    ca.betas = ptr<float>(w.betas); ca.L = o->L; ca.adapt = o->adapt != 0;
+    ca.mom = user_noise ? momd : nullptr; ca.unif = user_noise ? unifd : nullptr;
+    ca.seed = m->cfg.seed; ca.row_offset = (uint64_t)m->batch_offset * (uint64_t)C; ca.step0 = m->noise_step;
+    ca.e = ia.e; ca.log_w = ia.log_w; ca.h = ia.h; ca.nacc = ia.nacc; ca.dH = dHd; ca.accepted = accd;
+    const int chunk = m->opt.ais_t_chunk > 0 ? m->opt.ais_t_chunk : AIS_T_CHUNK_DEFAULT;
+    m->time_this = m->timing > 0;
+    for (int t0 = 0; t0 < T; t0 += chunk) {
+        ca.t0 = t0; ca.t1 = std::min(T, t0 + chunk);
+        ScopedTimer tm(m, T_AIS_CHAIN, st);
+        launch_ais_chain(ca, st);
+        HIPCHK(hipGetLastError());
+    }
+    m->time_this = false;
+    AisFinishArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.head = head; fa.ldh = ldh; fa.soff = Dh; fa.N = N; fa.C = C; fa.D = D; fa.R = R; fa.e = ia.e; fa.log_w = ia.log_w;
+    fa.log_px = ptr<double>(w.lpx);
+    if (out->ess) { CHK(ensure(w.ess, (size_t)N * 4, st)); fa.ess = ptr<float>(w.ess); }
+    if (out->z) {
+        if (is_device_ptr(out->z, m->cfg.device)) fa.z = out->z;
+        else { CHK(ensure(w.z, (size_t)R * D * 4, st)); fa.z = ptr<float>(w.z); }
+    }
+    launch_ais_finish(fa, st);
+    HIPCHK(hipGetLastError());
+    if (out->accept_rate) {
+        CHK(ensure(w.rate, (size_t)T * 4, st));
+        launch_ais_accept_rate(accd, T, R, ptr<float>(w.rate), st);
+        HIPCHK(hipGetLastError());
+        CHK(copy_out(m, out->accept_rate, w.rate.p, (size_t)T * 4));
+    }
+    CHK(copy_out(m, out->log_px, w.lpx.p, (size_t)N * 8));
+    if (out->log_w) CHK(copy_out(m, out->log_w, w.logw.p, (size_t)R * 8));
+    if (out->ess) CHK(copy_out(m, out->ess, w.ess.p, (size_t)N * 4));
+    if (out->step_out) CHK(copy_out(m, out->step_out, w.h.p, (size_t)R * 4));
+    if (out->z && fa.z != out->z) CHK(copy_out(m, out->z, fa.z, (size_t)R * D * 4));
+    if (out->dH && dHd != out->dH) CHK(copy_out(m, out->dH, dHd, (size_t)T * R * 4));
+    if (out->accepted && accd != out->accepted) CHK(copy_out(m, out->accepted, accd, (size_t)T * R));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!user_noise) m->noise_step += (uint32_t)T + 1u;
     m->have_forward = false;
     return IWAE_OK;
 }

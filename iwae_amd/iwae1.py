@@ -4,6 +4,7 @@ import numpy as np
 
 from . import utils
 from ._shim import BaseIWAE, _Sub, as_tensor
+from .native import ais_schedule
 
 
 class IWAE(BaseIWAE):
@@ -74,3 +75,36 @@ class IWAE(BaseIWAE):
             raise NotImplementedError("the aggregate posterior covers the unconditional 1-layer model only (q(z|x, y) and a learned p(z|y) "
                                       "need a label per image)")
         return self._net.aggregate_posterior(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), n_samples=n_samples)
+
+    # ---- annealed importance sampling (Neal 2001; Wu et al. 2017) and its check on simulated data (Grosse et al. 2015)
+    def _ais_scope(self):
+        if self._net.cond_dim:
+            raise NotImplementedError("annealed importance sampling covers the unconditional 1-layer model only")
+
+    def ais_log_likelihood(self, X, n_chains=16, n_temps=1000, **kwargs):
+        """Test-set log p(x) by annealed importance sampling with HMC transitions (iwae_ais): a stochastic lower bound that tightens
+        with n_temps where the k-sample bound of the evaluator is limited by the encoder.  Returns (mean, the binding's dict)."""
+        self._ais_scope()
+        res = self._net.ais(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), n_chains=n_chains, n_temps=n_temps, **kwargs)
+        return float(np.mean(res["log_px"])), res
+
+    def bdmc(self, n, n_chains=16, n_temps=1000, seed=0, schedule="sigmoid", **kwargs):
+        """Bidirectional Monte Carlo on n images simulated from the model: z ~ N(0, I), x ~ Bernoulli(decode(z)) (a seeded host generator),
+        so z is an exact posterior sample of x.  The forward run (ascending betas) gives a stochastic lower bound of log p(x), the reverse
+        run (descending betas, every chain started at the exact sample) a stochastic upper bound, upper = -(LSE_c log_w_rev - log C).
+        kwargs (leapfrog, step_size, adapt, init) go to both runs.  Returns {"x", "z", "lower", "upper" [n] float64, "gap": mean(upper - lower), "forward", "reverse": the two runs' dicts}."""
+        self._ais_scope()
+        rng = np.random.default_rng(seed)
+        D = self._net.n_latent[0]
+        z = rng.standard_normal((int(n), D)).astype(np.float32)
+        probs = self._net.decode(z)
+        x = (rng.random(probs.shape) < probs).astype(np.float32)
+        betas = ais_schedule(n_temps, schedule)
+        fwd = self._net.ais(x, n_chains=n_chains, betas=betas, **kwargs)
+        z0 = np.ascontiguousarray(np.broadcast_to(z[None], (int(n_chains),) + z.shape))
+        rev = self._net.ais(x, n_chains=n_chains, betas=betas[::-1].copy(), z0=z0, **kwargs)
+        lw = rev["log_w"]
+        m = lw.max(axis=0)
+        upper = -(m + np.log(np.mean(np.exp(lw - m[None]), axis=0)))
+        lower = fwd["log_px"]
+        return {"x": x, "z": z, "lower": lower, "upper": upper, "gap": float(np.mean(upper - lower)), "forward": fwd, "reverse": rev}

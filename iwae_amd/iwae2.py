@@ -39,3 +39,10 @@ class IWAE(BaseIWAE):
     def aggregate_posterior(self, X, n_samples=1):
         raise NotImplementedError("the aggregate posterior covers the 1-layer model only: q(z2|x) of the 2-layer model is not Gaussian and "
                                   "its p(z1) is not N(0,1)")
+
+    def ais_log_likelihood(self, X, n_chains=16, n_temps=1000, **kwargs):
+        raise NotImplementedError("annealed importance sampling covers the 1-layer model only: the 2-layer chain would have to move (z1, z2) "
+                                  "jointly under p(z1|z2) p(z2)")
+
+    def bdmc(self, n, n_chains=16, n_temps=1000, seed=0, **kwargs):
+        self.ais_log_likelihood(None)

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import OBJECTIVES, PRECISIONS, Config, Scalars, Tensors, check
+from ._capi import AIS_INITS, OBJECTIVES, PRECISIONS, AisOptions, AisOutputs, Config, Scalars, Tensors, check
 
 _SCALAR_NAMES = ("vae_elbo", "vae_elbo_kl", "iwae_elbo", "iwae_eq14", "inference_loss",
                  "mean_lpxz", "mean_lpz", "mean_lqzx", "mean_kl")
@@ -15,6 +15,26 @@ _SCALAR_NAMES = ("vae_elbo", "vae_elbo_kl", "iwae_elbo", "iwae_eq14", "inference
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def ais_schedule(n_temps, schedule="sigmoid", delta=4.0):
+    """The T + 1 = n_temps + 1 inverse temperatures of an annealing run, float32, from 0 to 1.  "sigmoid": Wu et al. 2017 (section 3.1),
+    beta_t = (s_t - s_0) / (s_T - s_0) with s_t = sigmoid(delta (2 t / T - 1)), delta = 4: more temperatures near both ends; "linear":
+    t / T.  Pure host code (no GPU)."""
+    T = int(n_temps)
+    if T < 1:
+        raise ValueError("ais_schedule: n_temps must be at least 1")
+    t = np.arange(T + 1, dtype=np.float64)
+    if schedule == "linear":
+        b = t / T
+    elif schedule == "sigmoid":
+        s = 1.0 / (1.0 + np.exp(-float(delta) * (2.0 * t / T - 1.0)))
+        b = (s - s[0]) / (s[-1] - s[0])
+    else:
+        raise ValueError("ais_schedule: schedule must be 'sigmoid' or 'linear', got %r" % (schedule,))
+    b = np.clip(b, 0.0, 1.0)
+    b[0], b[-1] = 0.0, 1.0
+    return b.astype(np.float32)
 
 
 class NativeModel:
@@ -346,6 +366,53 @@ class NativeModel:
         if per_sample:
             out["log_qz"], out["log_qzd"] = lqz, lqzd
         return out
+
+    def ais(self, x, n_chains=16, n_temps=1000, leapfrog=10, step_size=0.1, adapt=True, init="encoder", betas=None, z0=None, noise=None,
+            trace=False, schedule="sigmoid"):
+        """iwae_ais: annealed importance sampling log p(x) of the images x [N, x_dim] with n_chains HMC chains each through the
+        temperatures betas [T + 1] (default: ais_schedule(n_temps, schedule)); init "encoder" (q(z|x)) or "prior" (N(0, I)); z0 [C, N, D]
+        starts the chains there (the reverse run of bidirectional Monte Carlo); noise = (eps0 [C, N, D], mom [T, C, N, D], unif [T, C, N])
+        replaces the device generator.  Returns log_px [N] and log_w [C, N] (float64), ess [N], accept_rate [T], z [C, N, D] (final
+        states), step_size [C, N], q_mu, q_sigma [N, D], betas; with trace=True also dH [T, C, N] and accepted [T, C, N] (uint8)."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        N, D, Cn = x.shape[0], self.n_latent[0], int(n_chains)
+        b = ais_schedule(n_temps, schedule) if betas is None else _f32(betas).ravel()
+        T = b.size - 1
+        o = AisOptions()
+        o.C, o.T, o.L = Cn, T, int(leapfrog)
+        o.betas = b.ctypes.data
+        o.step_size, o.adapt = float(step_size), 1 if adapt else 0
+        if init not in AIS_INITS:
+            raise ValueError("ais: init must be 'encoder' or 'prior', got %r" % (init,))
+        o.init = AIS_INITS[init]
+        keep = [b]
+        if z0 is not None:
+            z0 = _f32(z0)
+            if z0.shape != (Cn, N, D):
+                raise ValueError("ais: z0 must be [n_chains, N, %d] = %s, got %s" % (D, (Cn, N, D), z0.shape))
+            o.z0 = z0.ctypes.data
+        if noise is not None:
+            e0, mom, unif = (_f32(v) for v in noise)
+            if e0.shape != (Cn, N, D) or mom.shape != (T, Cn, N, D) or unif.shape != (T, Cn, N):
+                raise ValueError("ais: noise must be (eps0 %s, mom %s, unif %s), got %s, %s, %s"
+                                 % ((Cn, N, D), (T, Cn, N, D), (T, Cn, N), e0.shape, mom.shape, unif.shape))
+            o.eps0, o.mom, o.unif = e0.ctypes.data, mom.ctypes.data, unif.ctypes.data
+            keep += [e0, mom, unif]
+        n0, c0, t0 = max(N, 0), max(Cn, 0), max(T, 0)      # (bad counts: the library rejects them; nothing is written)
+        res = {"log_px": np.empty(n0, dtype=np.float64), "log_w": np.empty((c0, n0), dtype=np.float64), "ess": np.empty(n0, dtype=np.float32),
+               "accept_rate": np.empty(t0, dtype=np.float32), "z": np.empty((c0, n0, D), dtype=np.float32),
+               "step_out": np.empty((c0, n0), dtype=np.float32), "q_mu": np.empty((n0, D), dtype=np.float32),
+               "q_sigma": np.empty((n0, D), dtype=np.float32)}
+        if trace:
+            res["dH"] = np.empty((t0, c0, n0), dtype=np.float32)
+            res["accepted"] = np.empty((t0, c0, n0), dtype=np.uint8)
+        outs = AisOutputs()
+        for name, arr in res.items():
+            setattr(outs, name, arr.ctypes.data)
+        check(self.lib.iwae_ais(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
+        res["step_size"] = res.pop("step_out")
+        res["betas"] = b
+        return res
 
     def grad_moments(self, x, k, draws, beta=1.0, objective="iwae_elbo"):
         """iwae_grad_moments: the per-parameter mean and unbiased variance (float64 [P] each) of `draws` gradient draws of the training
