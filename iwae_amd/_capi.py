@@ -109,7 +109,7 @@ SYMBOLS = {
 
 _lib = None
 
-_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "model.hip", "moments_kernels.hip",
+_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "model.h", "model.hip", "moments_kernels.hip",
                os.path.join("..", "..", "include", "iwae_amd.h"))
 
 

@@ -1,21 +1,16 @@
 // Host side of libiwae_amd.so: device memory, launch sequencing and the C ABI of include/iwae_amd.h.
 // Step structure follows the reference's train_step (src/iwae1.py:153-162): forward (IWAE.call,
 // :98-151), backward (closed form of tape.gradient), Adam (main.py:93).
-#include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include <stddef.h>
 #include <stdlib.h>
-#include <string>
-#include <vector>
 #include <algorithm>
 #include <random>
 #include <memory>
 #include <dlfcn.h>
-#include <rccl/rccl.h>       // types only: RCCL is loaded with dlopen at iwae_comm_init, the library does not link against it
-#include "../../include/iwae_amd.h"
-#include "kernels.h"
+#include "model.h"       // (the HIP runtime, RCCL's types, include/iwae_amd.h and kernels.h come with it)
 #include "layout.h"
 
 using namespace iwae;
@@ -27,53 +22,7 @@ static_assert(sizeof(iwae_ais_options) == 72 && offsetof(iwae_ais_options, betas
               offsetof(iwae_ais_options, unif) == 64 && sizeof(iwae_ais_outputs) == 10 * sizeof(void*), "iwae_ais_options / iwae_ais_outputs layout is part of the ABI (iwae_amd/_capi.py)");
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(e_ == hipErrorOutOfMemory ? IWAE_ERR_NOMEM : IWAE_ERR_HIP,                     \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                            \
-    } while (0)
-#define CHK(expr)            \
-    do {                     \
-        int rc_ = (expr);    \
-        if (rc_ != IWAE_OK) return rc_; \
-    } while (0)
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-struct KerasLayer {
-    std::string name;
-    int Kin, Nout;
-    size_t offW, offb;
-};
-
-// one GEMM-able linear map; the mu|sigma head merges two Keras layers into one (joff = 0 / Dp)
-struct Linear {
-    int Kin = 0, Nspace = 0;          // in-features, out-feature space (heads: 2*Dp)
-    int Kp32 = 0, Np32 = 0, KT = 0, MG = 0;
-    int nsub = 0, sub[2] = {0, 0}, joff[2] = {0, 0};
-    char* imgF = nullptr; size_t imgF_bytes = 0;
-    char* imgB = nullptr; size_t imgB_bytes = 0; int KT_B = 0, MG_B = 0, MT_B = 0, kmajor = 0;
-    DevBuf slabW, slabB;
-    int IT = 0, JT = 0, nsplit = 1;
-};
-
-struct BlockWs {   // activations / gradients of one BasicBlock applied to R rows
-    DevBuf h1P, h2P, head, dheadP, d2P, d1P, dx;
-};
-struct MlpWs {     // decode_z_to_x applied to M rows
-    DevBuf g1P, g2P, dlP, d2P, d1P, dz;
-    DevBuf g2wP;      // g2 times the row weight (bf16, P-layout; pad feature H = the row weight): the pre-weighted operand of the output layer's weight gradient
-};
-
-}  // namespace
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 // RCCL entry points, resolved at run time (the process may already hold torch's copy of librccl: that one is reused)
 struct RcclApi {
@@ -113,302 +62,12 @@ static int load_rccl() {
         if (r_ != ncclSuccess) return fail(IWAE_ERR_HIP, std::string(#expr) + ": " + g_rccl.GetErrorString(r_));    \
     } while (0)
 
-// kernels iwae_enable_timing brackets with HIP events (on the stream each is launched on); names: iwae_kernel_time
-enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_COUNT };
 static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgrad_out", "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent",
                                                  "latent_bwd", "encoder_fwd", "reduce_adam", "decoder_bwd",
                                                  "allreduce_enc", "allreduce_dec",       // (the data-parallel step's two ncclAllReduce calls, each on its own stream)
                                                  "ais_chain"};                           // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
 
-// What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
-// images and samples in chunks and needs log_w only.
-struct FwdCall {
-    uint32_t batch_offset = 0;        // Philox row offset of the call's first image (iwae_set_step, plus the chunk's first image)
-    int cond_row0 = 0;                // first row of iwae_model::cond the call's images use
-    int k_total = 0, s_off = 0;       // k_total > 0: the call holds samples [s_off, s_off + k) of k_total per image and draws the unchunked call's Philox rows
-    bool log_w_only = false;          // forward-only call: no second (DReG) density per sample (round 5: ~14 % of the sampling pass); the log-mean-exp alone when no tensor is wanted
-    bool no_ksplit = false;           // float32: no K split of few-row products (an image's result must not depend on how many images share the launch)
-};
-
-// Every switch and tuning value iwae_set_option writes (defaults: the measured best).  plan_step reads the switches that choose kernels and streams; the
-// launch code reads only the values that size a launch already chosen (wg_target*, wout_wg*, eps_blocks, dense_g1_mask, dec_bwd_nw).
-struct StepOptions {
-    bool allow_s_mode = true;   // option out_recompute switches back to recomputing the logits in out_bwd (A/B measurements)
-    bool allow_zin = true;      // option no_zin: always the separate sampling kernel (A/B measurements)
-    bool allow_zin_eval = false; // option zin_eval (round 4, measured and NOT the default): forward-only calls on many rows take their draws from eps_gen_kernel and let the decoder
-                                 // kernel make z in its prologue instead of sample_kernel (inline Philox) in front of it -- bf16 evaluator 146 k vs 158 k images/s: the prologue's 20 MB of
-                                 // float32 draws cost the vector-issue-bound kernel more than the separate pass
-    bool allow_eps_multi = true;   // option no_eps_multi: one draw launch per step there too
-    int eps_blocks = 512;      // blocks of the ahead-of-time noise draw (option eps_blocks; 0 = one block per 256 threads of work)
-    bool allow_block_fused = true;   // option no_block_fused: a BasicBlock on few rows stays three dense_kernel launches (A/B measurements)
-    bool allow_out_in_block = true;  // option no_out_in_block: the output layer of a few-row decoder stays a dense_kernel<EPI_BERN> launch (A/B measurements)
-    bool allow_dec_fused = true;     // option no_dec_fused: the two tanh layers of the decoder stay dense_kernel launches (A/B measurements)
-    bool allow_bern_pipe = true;   // option no_bern_pipe: the Bernoulli forward stays on dense_kernel<EPI_BERN> (A/B measurements)
-    bool bern_qw = true;             // option no_bern_qw: the decoder kernel's 8-wave / 128-row shape instead of 16 waves / 200 rows (A/B measurements)
-    bool bern_qw_force = false;      // option bern_qw_force: that shape at every row count it exists for (tests)
-    bool allow_lse_fused = true;  // the decoder kernel does lse_kernel's work for its rows (option no_lse_fused)
-    bool allow_lse_dup = true;      // option no_lse_dup: one lse_kernel, the side stream forks behind it (A/B measurements)
-    bool allow_lse_in_bwd = true;      // few rows: this step's lse_kernel work is left to dec_bwd_rows_kernel (option no_lse_in_bwd)
-    bool allow_early_wout = true;    // option no_early_wout: the output layer's weight gradient forks behind out_bwd with the others (A/B measurements)
-    // Option g2w (round 4, measured and NOT the default): the decoder kernel leaves g2w = bf16(g_r g2) and the output layer's weight gradient runs
-    // unweighted on it (no 870 cycles of row weighting per loader stage).  That kernel got faster (107 -> 97 us in the step) and the step SLOWER
-    // (0.2044 -> 0.2154 ms, interleaved A/B): the decoder kernel pays 4 us for 23 MB more writes and the backward phase is bound by its bytes, not
-    // by that kernel's instruction stream.
-    bool allow_g2w = false;
-    bool allow_chain2 = true;   // option no_chain2: the 2-layer model's per-sample blocks as dense_kernel launches + sample_kernel + gauss_lp_kernel (A/B measurements, variant tests)
-    bool allow_chain2_bwd = true;      // option no_chain2_bwd: the per-sample blocks' backward as gauss_bwd_kernel + dense_kernel launches
-    unsigned dense_g1_mask = IWAE_DENSE_G1_DEFAULT;   // option dense_g1 = <mask> (tuning aid, kernels.h)
-    bool allow_dec_bwd = true;  // option no_dec_bwd: out_bwd_s + the two dX kernels stay three launches (A/B measurements)
-    bool small_dec_bwd = true; int small_rows = 8191;   // the one-launch dX chain also below 8 192 rows (option no_small_dec_bwd: the per-pixel-group out_bwd + finish + two dX launches
-                                                        // there).  Measured: B=20,k=1 0.1417 -> 0.1383 ms/step, B=100,k=5 150.7 -> 144.6 us, B=160,k=50 189.1 -> 165.7 us
-    int dec_rows_max = 1024;    // dec_bwd_rows_kernel up to this many rows (option dec_rows), dec_bwd_kernel beyond
-    int dec_bwd_nw = 8;         // option dec_bwd_nw: dec_bwd_kernel's shape (8 waves x 16 rows, round 4 | 4 waves x 32 rows)
-    bool allow_dz_half = true;  // option dz_f32: dec_bwd_kernel leaves dz as float32 (A/B measurements)
-    bool allow_wg3 = true;                           // few rows: the decoder's three weight gradients as one grouped launch (option no_wg3)
-    bool allow_dec_rows = true;                      // ... and, with <= 2 048 DATA rows, the decoder's in the same launch (dec_rows_step; option no_dec_rows)
-    bool allow_wgrad_rows = true;                    // few rows (<= 2 048): the image encoder's weight gradients + Adam in ONE launch, whole row reduction per workgroup (wgrad_rows_kernel; option no_wgrad_rows)
-    bool allow_lat_rows4 = false;                    // option lat_rows4 (round 5, measured and NOT the default): beyond 16 samples per image the sums inside block_bwd_kernel<4> (4 images per
-                                                     // workgroup, an image's samples over four waves, 256 workgroups).  In the step it takes 32.6 us where latent_bwd_kernel + block_bwd_kernel
-                                                     // take 18.7 + 10.1: its 1024-thread / 101-register workgroups need a whole CU each and only ~96 CUs are free beside the weight
-                                                     // gradients (three rounds), where latent_bwd_kernel's small workgroups fit anywhere: c1 0.1965 vs 0.1962 ms, c2 0.3856 vs 0.3802
-    bool allow_lat_in_block = true;                  // few images: latent_bwd_kernel's sums inside the encoder's block_bwd_kernel (option no_lat_in_block)
-    bool use_side2 = true;             // option no_side2: the hidden layers' weight gradients behind the output layer's on `side`, not beside it on `side2`
-    bool allow_wg_group = false;       // option wg_group: the hidden layers' gradients as ONE grouped launch (measured: 0.2450 vs 0.2384 ms/step as two launches --
-                                       // both at once take more of the machine from the output layer's gradient, which is what the step waits for)
-    int wout_split = 0, wout_wg1 = 56, wout_wg2 = 128;      // option wout_split (percent of the rows, 0 = off; round 5): the output layer's weight gradient as an EARLY launch on few
-                                // workgroups beside dec_bwd_kernel (rows [0, R1)) and a LATE one behind it (the rest, beside the hidden layers' gradients)
-    bool defer_split = false;   // option defer_split (round 5): 1-layer step, each side stream sums + updates the decoder layers whose gradients IT carried
-    bool allow_defer = true;    // option no_defer: always join at the end of the step (A/B measurements)
-    bool allow_defer2 = true;   // option no_defer2
-    bool allow_defer2_split = true;      // ... one deferred update per side stream (option no_defer2_split: one, on `tail`)
-    int wg_target16 = 0;       // workgroups aimed at per 16-wave weight-gradient launch (option wg16; 0 = the model's default: 96 for the 1-layer model, 64 (round 5; 128 before) for
-                               // the 2-layer one -- round 3, with the output layer's gradient starting right behind the decoder kernel: 80 / 88 / 96 / 104 / 112 / 128
-                               // -> 0.2192 / 0.2168 / 0.2132 / 0.2164 / 0.2206 / 0.2175 ms, 24 row splits write 17 MB of slabs instead of 22.5; the 2-layer
-                               // step: 0.3932 vs 0.3916): these are one-per-CU
-                               // workgroups (128 KB of LDS); 256 of them lock every CU against the kernels running beside them on the main
-                               // stream (256 -> 0.294, 192 -> 0.280, 160 -> 0.279 ms/step while the gradient forked behind out_bwd; forked
-                               // behind lse_kernel, beside out_bwd: 96 -> 0.268, 112 -> 0.262, 128 -> 0.258, 144 -> 0.261, 160 -> 0.265)
-    int wg_target16_1 = 64;    // same, for layers that are a single block wide (option wg16_1): the hidden layers' gradients -- with the specialised-wave kernel 64 row splits (12.8 MB of slabs each) beat 128 (0.259 -> 0.249-0.254 ms/step); 48 and 32 are slower again
-    int wg_target8 = 128;      // same for the 8-wave launches on many rows (narrow layers of the 2-layer model; option wg8): 128 row splits halve the 109 MB of fp32 slabs 256 wrote per step (c2: 0.4193 -> 0.4176 ms; 64: 0.462)
-    int wg_target8_few = 32;   // 8-wave launches on < 8 192 rows (the encoder's layers on the batch's images; option wg8_few): the 784-wide first layer in 4 row
-                               // splits instead of 16 (10.6 -> 2.7 MB of slabs each way): 0.2439 -> 0.2351 ms/step at B = 1 024; 8 / 16 / 48: 0.2374 / 0.2374 / 0.2360
-    int wg_shape9 = 0;          // option wg9 (bit mask, see wgradp_plan): layers that take the 8 + 8-wave / 128-feature shape of wgradws_kernel
-    bool allow_wg7 = true;      // option no_wg7: the 16-wave weight-gradient shapes also where the 8-wave 7 x 4 shape exists (A/B measurements)
-    bool dp_concurrent = false;        // option dp_concurrent: the two all-reduces of a step may run at the same time (see dp_finish)
-    GemmF32Opts gemm_f32;                     // kernel choice of the float32 GEMM launchers (options f32_gemm_*, f32_no_ksplit, f32_ksplit_min_tiles)
-    bool allow_f32_multi_reduce = true;      // option no_f32_multi_reduce: a slab reduction launch per gradient tensor instead of one per step
-    bool allow_f32_side = true, f32_wout_first = true;      // float32 step: the decoder's weight gradients + update on the side stream (options no_f32_side, f32_wout_first)
-    int f32_dw_last = 0;        // option f32_dw_last: all decoder weight gradients behind the dX chain (1: tiles as picked, 2: 4-wave tiles, 3: ... at 3 waves per SIMD)
-    int f32_dw_min_rows = 32;   // float32 weight gradients: a row split covers at least this many rows (option f32_dw_min_rows; 64 until round 5)
-    int f32_dw_tiles = 1024;    // float32 weight gradients: workgroups aimed at per launch (row splits = this / output tiles; option f32_dw_tiles)
-    bool f32_dec_fused_train = false;
-    bool allow_f32_dec_fused = true;                           // float32 mode: the decoder forward as one launch (dec_fwd_f32_kernel; option no_f32_dec_fused)
-    bool allow_f32_bern_fused = true;      // float32 mode: log p(x|z) (and, in a training step, s) in the output layer's GEMM epilogue (option no_f32_bern_fused)
-    int eval_rows = 0;                        // data rows per evaluator launch (option eval_rows): images x samples, k chunked beyond it; 0 = eval_rows_auto()
-    int grid_chunk = 0;                       // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT)
-    int ais_t_chunk = 0;                      // iwae_ais: transitions per launch of ais_chain_kernel (option ais_t_chunk; 0 = AIS_T_CHUNK_DEFAULT)
-};
-
-// The kernels and streams of one bf16 step.  plan_step decides all of it from shapes and options before forward_impl launches or allocates
-// anything; forward_impl, backward_impl and the entry points behind them read it and decide nothing themselves, so the forward pass never
-// predicts what the backward pass will do -- both follow the same plan.  Every bf16 forward, a forward-only one too, writes m->plan anew: the
-// backward half is valid only from a training forward to the entry points of that same step (backward_impl, dp_finish, the split step's halves).
-enum ZFrom { Z_SAMPLE = 0, Z_DENSE_ZIN, Z_DEC_PROLOGUE, Z_BLOCK, Z_CHAIN2 };      // who makes z (z1): sample_kernel | dense_kernel's sampled-input mode | the decoder kernel's prologue | block_fwd_kernel | chain2_fwd_kernel
-enum DecFwd { DEC_DENSE = 0, DEC_BLOCK2, DEC_BLOCK_OUT, DEC_PIPE };              // the decoder's tanh layers: dense_kernel launches | block_fwd_kernel | block_fwd_kernel with the output layer | inside the one-launch bern_pipe_kernel
-enum LseAt { LSE_FWD = 0, LSE_DECODER, LSE_BWD_ROWS };                           // the log-mean-exp: lse_kernel in the forward pass | the decoder kernel | dec_bwd_rows_kernel
-enum DxPath { DX_THREE = 0, DX_DEC_BWD, DX_ROWS };                               // the decoder's dX chain: out_bwd + two dense launches | dec_bwd_kernel | dec_bwd_rows_kernel
-enum OnStream { ON_MAIN = 0, ON_SIDE, ON_SIDE2 };
-struct StepPlan {
-    // ---- forward
-    bool zin_eval = false;      // forward-only call whose decoder kernel makes z from eps_gen_kernel's draws (option zin_eval)
-    bool keep_eps = false;      // the draws come from eps_gen_kernel's buffers (later kernels of the call read them again)
-    bool eps_multi = false;     // ... from the multi-step buffers (few data rows, single-stream backward)
-    bool enc_takes_f32 = false; // the encoder's block_fwd_kernel converts float32 input rows itself (else prep_rows runs first)
-    ZFrom z_from = Z_SAMPLE;
-    bool chain = false;         // 2-layer model: both per-sample blocks in chain2_fwd_kernel
-    bool chain2_bwd = false;    // ... and their backward as gblock_bwd_kernel
-    DecFwd dec_fwd = DEC_DENSE;
-    DenseArgs bern;             // shape half of the output layer's / decoder kernel's argument block (pipe: bern_pipe's shape 1 or 2); forward_impl adds the buffers
-    BlockFwdArgs dec_blk;       // ... of block_fwd_kernel on the decoder (DEC_BLOCK2, DEC_BLOCK_OUT)
-    int px_parts = 1;           // > 1: log p(x|z) of this forward arrives in px_part as that many partial sums per row
-    bool s_mode = false;        // the forward keeps s = x - sigmoid(l) in wdec1.dlP
-    bool early_wout = false;    // the output layer's weight gradient forks behind the decoder forward / lse_kernel, not behind out_bwd
-    bool lse_fused = false;     // the decoder kernel does lse_kernel's work for its rows
-    bool lse_dup = false;       // a second lse_kernel on the side stream makes the output layer's row weights
-    bool g2w = false;           // the decoder kernel leaves g2w = bf16(g_r g2) (option g2w)
-    LseAt lse_at = LSE_FWD;
-    bool want_dreg = false;     // the call wants the second (DReG) log q per sample
-    OnStream draw_on = ON_SIDE; // the stream of the speculative draw of the next step's noise
-    // ---- backward (filled when the forward is a training step's)
-    bool dec_rows = false;      // the decoder's weight gradients ride in the encoder's wgrad_rows_kernel launch: no side-stream work at all
-    DxPath dx = DX_THREE;
-    DecBwdRowsArgs rows;        // shape half of dec_bwd_rows_kernel's argument block (DX_ROWS)
-    bool out_parts = false;     // DX_THREE: out_bwd_s_kernel per pixel group, partial sums + finish kernel
-    bool dz_half = false;       // the dX kernel leaves dz as bf16
-    bool lat_fuse = false;      // latent_bwd_kernel's sums inside the encoder's block_bwd_kernel
-    bool rows_enc = false;      // the encoder's weight gradients + update as wgrad_rows_kernel
-    bool group3 = false;        // the decoder's three weight gradients as one grouped launch on `side2`
-    bool wout_two_part = false; // the output layer's weight gradient as an early and a late launch (option wout_split)
-    bool hid_group = false;     // the hidden layers' weight gradients as one grouped launch (option wg_group)
-    OnStream hid_on = ON_SIDE;  // the stream of the hidden layers' weight gradients (the output layer's: `side`, or `side2` in group3)
-    OnStream tail = ON_SIDE;    // the side stream that finishes last (carries the decoder's reduction / exchange / update)
-};
-
-struct iwae_model {
-    iwae_config cfg;
-    int X, Xp32;
-    int C = 0, Xinp = 0;       // conditional model: condition width; row width of the encoder input concat(x, y) (= Xp32 without)
-    DevBuf cond; int cond_n = 0;   // y [cond_n][C] fp32 for the next call (iwae_set_condition)
-    int H[2], D[2], Hp[2], Dp[2];
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::vector<KerasLayer> klayers;
-    size_t nparam = 0;
-    // Linear maps.  1-layer: enc{l1,l2,head}, dec{d1,d2,out}.  2-layer adds enc2, dec2 blocks.
-    Linear enc1[3], enc2[3], dec2[3], dec1[3];
-    Linear prior[3];           // conditional prior network p(z|y) (cfg.cond_prior, tasks/task04.py:108): BasicBlock on y
-    bool has_prior = false;
-    DevBuf condP;              // y as bf16 P-layout [Bp][32*ceil(C/32)] (the prior block's input)
-    float *param = nullptr, *grad = nullptr, *mom = nullptr, *vel = nullptr;
-    int64_t adam_t = 0;
-    // float32 mode (iwae_config.precision / iwae_set_eval_precision): row-major float32 activations, GEMMs on v_mfma_f32_16x16x4_f32
-    struct F32Block { DevBuf h1, h2, dhead, d2, d1, dx; };
-    struct F32State { F32Block enc1, enc2, dec2, prior; DevBuf z[2], g1, g2, logits, d2, d1, slab, bpart, xcat, kslab; } f32;
-    // float32 weight gradients of a step keep their row-split slabs (each in its own region of f32.slab) and are summed by ONE launch at the end of
-    // backward_f32 (reduce_slabs_multi_f32_kernel): jobs queued by f32_dw, slab offsets in floats (the buffer may still grow while they queue)
-    struct F32Pending { size_t off; size_t stride; size_t n; float* out; int nsplit; int seg; };
-    std::vector<F32Pending> f32_pending; size_t f32_slab_used = 0;
-    bool f32_side_active = false;      // float32 step: the decoder's weight gradients + update run on the side stream
-    bool f32_z_pending = false;
-    bool bf16_side_used = false;      // a bf16 call may have left a speculative draw on a side stream (forward_f32 waits for it on the host)
-    size_t f32_slab_want = 0, f32_slab_want_step = 0;      // floats of slabs the last whole step asked for (the buffer's target size) / this step so far
-    DevBuf eval_x, eval_lme;                  // iwae_eval_llh: the images (uploaded once) and the per-image log-mean-exps of every launch
-    int eval_precision = IWAE_PREC_FP32;      // arithmetic of iwae_eval_llh and iwae_grid_posterior (iwae_set_eval_precision)
-    // iwae_grid_posterior's buffers
-    struct GridWs { DevBuf x, xb, xP, flag, head, z, lw, zP, h1, h2, logits, lhi, llo, c, zc, w, part, run, lpx, mean, cov, qmass, kl, lj; } grid;
-    // iwae_latent_activity's buffers: the images, the chunk's draws, z1 rows and q(z2|z1) activations of the composed paths, the block partials
-    // of mu2 [N][blocks][D2] and the outputs
-    struct ActWs { DevBuf x, xP, head, eps, z, rows, part, pm, act, dm; BlockWs blk; F32Block f32; } act;
-    // iwae_grad_moments' buffers: the images (uploaded once per call), the Welford mean and M2 [nparam] in double
-    struct MomWs { DevBuf x, mean, m2; } mom_ws;
-    // iwae_aggregate_posterior's buffers: the images, heads and draws, the component tables, a sample tile's z / own terms and range partials,
-    // the per-sample densities (log_qzd transposed [Dpad][S N]) and the double sums
-    struct AggWs { DevBuf x, xP, head, eps, mu, inv, invd, nls, nls_sum, zT, shT, dim_part, jmax, jsum, lqz, lqzdT, lqzd, part, out; } agg;
-    // iwae_ais's buffers: the images, heads, the decoder's padded weights, the schedule, the chain state (e, log_w, h, accept counts), the
-    // caller's noise and initial states when they arrive on the host, and the outputs
-    struct AisWs { DevBuf x, xP, head, wpad, betas, e, logw, h, nacc, z0, mom, unif, dH, acc, rate, z, lpx, ess; } ais;
-    bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
-    const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
-    // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
-    ncclComm_t comm_main = nullptr, comm_side = nullptr;
-    int comm_world = 1, comm_rank = 0;
-    float adam_b1 = 0.9f, adam_b2 = 0.999f, adam_eps = 1e-4f;   // keras Adam(lr, epsilon=1e-4) of main.py:93 unless iwae_set_adam says otherwise
-    uint32_t noise_step = 0, batch_offset = 0;
-    // layer descriptor table
-    std::vector<LayerDesc> descs;
-    LayerDesc* d_descs = nullptr;
-    int elem_blocks = 0, reduce_blocks = 0;
-    bool descs_dirty = true;
-    StepOptions opt;
-    StepPlan plan;             // the kernels and streams of the step in flight: written by plan_step (forward_impl), read by the backward pass and the entry points behind it
-    // per-call state: written by begin_forward only (the backward pass and eps_src read the forward's copy)
-    FwdCall call;
-    int B = 0, k = 0, M = 0, Mp = 0, Bp = 0;
-    float beta = 1.0f;
-    bool have_forward = false, user_eps = false;
-    DevBuf dg2_part;            // small row counts: out_bwd_s_kernel's per-pixel-group partial sums
-    DevBuf px_part;
-    DevBuf xin, xP, epsbuf, zP[2];
-    DevBuf rows[6];            // lpxz, t1, t2, t3, t4, lq_dreg   (per data row)
-    DevBuf logw, wn, gx, cf, per_b, dzdir;
-    // lse_kernel's outputs once more, written by the copy of it that runs on the side stream (see forward_impl): the output layer's
-    // weight gradient takes its row weights from there
-    DevBuf logw2, wn2, gx2, cf2, per_b2;
-    bool f32_keeps_s = false;      // float32 step: the output layer's GEMM epilogue left s where the logits would have gone
-    bool g2w_descs = false;     // the layer table was built for a step with plan.g2w
-    BlockWs wenc1, wenc2, wdec2, wprior;
-    MlpWs wdec1;
-    DevBuf scratch;            // exports
-    // resident dataset (iwae_dataset_*): uint8 grey levels [N][X] + the epoch's visiting order
-    DevBuf ds_data, ds_order;
-    DevBuf ds_labels; bool ds_has_labels = false;   // class id per image of the resident set (iwae_dataset_set_labels; conditional models)
-    int ds_N = 0;
-    // N(0,1) draws of a step, fp32 [Mp][Dp] per latent layer, made by eps_gen_kernel and read by the sampling / decoder and
-    // backward kernels.  A training step draws the NEXT step's noise during its forward pass on the side stream, idle then
-    // (speculating step+1, same batch shape); it is ordered by the join the main stream performs anyway, and a forward
-    // whose counters do not match the speculation draws on its own stream first.  Three ring slots: this step's draws, the
-    // previous step's (its backward pass may still read them) and the next step's.
-    DevBuf epsc[3][2];          // [ring slot][layer]: the step's draws, the previous step's (its backward may still read them
-                                // when the next step's are requested) and the next step's (drawn during this step's forward)
-    struct EpsTag { bool valid = false; uint32_t step = 0; uint64_t row_offset = 0; int M = 0; } eps_tag[3];
-    int epsc_par = 0;
-    // Few data rows (the single-stream regime of dec_rows_step, round 5): the draws of EPSM_STEPS consecutive steps in ONE launch, two buffers taking turns
-    // (the next group is drawn during the forward pass of the current group's last step: the buffer it overwrites was last read a whole group ago, in stream order)
-    DevBuf epsm[2][2];          // [buffer][layer]: [EPSM_STEPS][Mp][eps_ld]
-    struct EpsMTag { bool valid = false; uint32_t step0 = 0; uint64_t row_offset = 0; int M = 0; } epsm_tag[2];
-    const float* epsc_ptr[2] = {nullptr, nullptr};
-    char* d_zero = nullptr;    // 1 KiB of zeros (wgradp_kernel's source for rows >= M)
-    uint32_t ds_epoch = 0;
-    int ds_start = -1;         // >= 0: the next forward gathers + binarises rows ds_start.. from the dataset instead of reading x
-    DevBuf stamps;             // diagnostic (option stamps, DIAG builds)
-    DevBuf dstamps; int dstamp_epi = -1, dstamp_kt = -1, dstamp_waves = 0;   // diagnostic (options dense_stamps_epi / dense_stamps_kt, STAMPS builds)
-    // optional HIP-event timing of the dominant kernels (iwae_enable_timing): pairs recorded on m->stream
-    // fork/join of the decoder weight-gradient GEMMs (independent of the dz -> encoder chain) onto a side stream
-    hipStream_t side = nullptr;
-    hipStream_t side2 = nullptr;       // the hidden layers' weight gradients beside the output layer's (option no_side2: behind it on `side`)
-    hipEvent_t ev_s2 = nullptr;
-    hipEvent_t ev_ar = nullptr;        // data-parallel step: recorded behind the encoder segment's all-reduce (dp_finish)
-    bool early_held = false;           // in-library data-parallel step: backward_impl left the decoder's slab reduction to dp_finish
-    hipEvent_t ev_lse = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_blk = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_dec = nullptr;
-    // Single-GPU train step: the decoder's slab reduction + Adam (90 % of the slab bytes) stays on the side stream and is
-    // NOT joined at the end of the step -- nothing needs the decoder's new weights before the next step's d1 layer, so it
-    // runs beside the next encoder forward.  dec_pending: ev_dec (recorded behind it) has not been waited for yet;
-    // join_side() does that, and every entry point that touches parameters, gradients or the decoder calls it.
-    bool dec_pending = false;
-    size_t split_offset = 0;    // iwae_forward_backward_split: first float of the flat gradient that was left on the side stream
-    int fake_s = 0;             // DIAG builds: byte ablations of s (option fake_s)
-    int abl_skip = 0;           // DIAG builds: launch ablations of the full-size step (option abl_skip; timing only, results wrong): 1 no output-layer weight gradient,
-                                // 2 no hidden-layer weight gradients, 4 no deferred decoder reduction + update, 8 no latent_bwd_kernel, 16 no noise draw ahead
-    int wg_debug = 0;           // option wg_debug (DIAG builds): diagnostic ablations of wgradp_kernel (kernels.h)
-    int num_cus = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    int early_first2 = -1;      // 2-layer model: first reduce block behind the image encoder's layers (everything whose weight gradients run on the side streams)
-    bool dec2_pending = false;
-    hipEvent_t ev_dec2 = nullptr;
-    int early_first = -1;       // first reduce block of the decoder's layers when they are the tail of the table, else -1
-    int timing = 0;            // 0 off, n > 0: time every n-th forward (event records cost a few us of stream bubble each)
-    int64_t timing_calls = 0;
-    bool time_this = false;
-    std::vector<hipEvent_t> ev_start[T_COUNT], ev_stop[T_COUNT];   // per timed kernel (enum TimedKernel)
-    size_t ev_used[T_COUNT] = {};
-    bool want_stamps = false;
-    float* d_scalars = nullptr;
-    float* h_scalars = nullptr;   // pinned
-};
-
 namespace {
-
-int ensure(DevBuf& b, size_t bytes, hipStream_t st) {
-    if (bytes <= b.cap) return IWAE_OK;
-    if (b.p) {
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    const size_t want = bytes + bytes / 8 + 256;
-    HIPCHK(hipMalloc(&b.p, want));
-    b.cap = want;
-    return IWAE_OK;
-}
-template <class T>
-T* ptr(const DevBuf& b) { return (T*)b.p; }
-
-void free_buf(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
 
 void init_linear(Linear& L, int Kin, int Nspace, bool need_B, bool kmajor) {
     L.Kin = Kin;
@@ -566,25 +225,6 @@ int refresh_images(iwae_model* m) {   // rebuild bf16 A-images from the fp32 mas
     return IWAE_OK;
 }
 
-struct ScopedTimer {     // records a start/stop event pair around a launch when timing is enabled
-    iwae_model* m; int id; bool on;
-    hipStream_t ts;
-    ScopedTimer(iwae_model* m_, int id_, hipStream_t s_ = nullptr) : m(m_), id(id_), on(m_->time_this), ts(s_ ? s_ : m_->stream) {
-        if (!on) return;
-        if (m->ev_used[id] == m->ev_start[id].size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
-            m->ev_start[id].push_back(a); m->ev_stop[id].push_back(b);
-        }
-        (void)hipEventRecord(m->ev_start[id][m->ev_used[id]], ts);
-    }
-    ~ScopedTimer() {
-        if (!on) return;
-        (void)hipEventRecord(m->ev_stop[id][m->ev_used[id]], ts);
-        m->ev_used[id] += 1;
-    }
-};
-
 // row stride of the cached draws: the latent width rounded to 4, NOT the 32-padded operand width -- D = 100: 400 B instead of 512 B per row,
 // 5.7 MB less per pass over the k = 50, B = 1 024 step's draws (written once, read by the decoder kernel and by latent_bwd_kernel)
 static inline int eps_ld(const iwae_model* m, int layer) { return 4 * ((m->D[layer] + 3) / 4); }
@@ -615,53 +255,7 @@ int attach_dense_stamps(iwae_model* m, int epi, DenseArgs& a) {
     return IWAE_OK;
 }
 
-// orders the main stream behind a deferred decoder update (and the noise prefetch in front of it) still on the side stream
-int join_side(iwae_model* m) {
-    if (m->dec2_pending) {      // (2-layer step: the first side stream's own deferred update)
-        HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec2, 0));
-        m->dec2_pending = false;
-    }
-    if (!m->dec_pending) return IWAE_OK;
-    HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec, 0));
-    m->dec_pending = false;
-    return IWAE_OK;
-}
-
 // ---------------------------------------------------------------- forward pieces
-int dense_fwd(iwae_model* m, Linear& L, int epi, const uint16_t* XP, int rows, uint16_t* YP, float* YF, int ldYF, const SampleArgs* zin = nullptr) {
-    DenseArgs a;
-    memset(&a, 0, sizeof(a));
-    a.X = XP; a.ldX = L.Kp32; a.img = L.imgF;
-    a.split = (L.nsub == 2) ? L.joff[1] : (1 << 30);
-    a.M = rows; a.KT = L.KT; a.MG = L.MG; a.mg_per_block = (rows <= 8192) ? 1 : L.MG; a.Np32 = L.Np32; a.g1_mask = m->opt.dense_g1_mask;
-    a.stage_all = (a.mg_per_block == 1 && L.KT > 8 && (L.KT + 7) / 8 <= 4) ? 1 : 0;
-    if (zin) {      // sampled-input mode: the layer makes its own input rows z = mu + sigma*eps (and keeps them in zin->ZP)
-        a.zhead = zin->head; a.ldZH = zin->ldH; a.zeps = zin->eps.cache; a.zldE = zin->eps.ldC; a.zD = zin->D; a.zDp = zin->Dp;
-        a.ZPout = zin->ZP; a.zlp = zin->lp_prior; a.zlq = zin->lq; a.k = zin->k;
-        a.mg_per_block = L.MG;          // one block owns all out-feature groups of its rows (the z rows are made once)
-    }
-    a.YP = YP; a.ldYP = L.Np32; a.YF = YF; a.ldYF = ldYF;
-    CHK(attach_dense_stamps(m, epi, a));
-    launch_dense(epi, a, m->stream);
-    HIPCHK(hipGetLastError());
-    return IWAE_OK;
-}
-
-int block_alloc(iwae_model* m, Linear* blk, BlockWs& w, int R, int Rp, bool bwd, bool need_dx) {
-    const int Hp = blk[0].Np32, N2 = blk[2].Np32;
-    CHK(ensure(w.h1P, (size_t)Rp * Hp * 2, m->stream));
-    CHK(ensure(w.h2P, (size_t)Rp * Hp * 2, m->stream));
-    CHK(ensure(w.head, (size_t)Rp * N2 * 4, m->stream));
-    if (bwd) {
-        CHK(ensure(w.dheadP, (size_t)Rp * N2 * 2, m->stream));
-        CHK(ensure(w.d2P, (size_t)Rp * Hp * 2, m->stream));
-        CHK(ensure(w.d1P, (size_t)Rp * Hp * 2, m->stream));
-        if (need_dx) CHK(ensure(w.dx, (size_t)Rp * blk[0].Kp32 * 4, m->stream));
-    }
-    (void)R;
-    return IWAE_OK;
-}
-
 // Does block_fwd_kernel take the whole block on R rows (few rows: the encoder on the batch's images)?  Fills the shape half of its argument block.
 bool block_fwd_shape(const iwae_model* m, const Linear* blk, int R, BlockFwdArgs& a) {
     memset(&a, 0, sizeof(a));
@@ -669,24 +263,6 @@ bool block_fwd_shape(const iwae_model* m, const Linear* blk, int R, BlockFwdArgs
     a.KT0 = blk[0].KT; a.KT1 = blk[1].KT; a.NT1 = blk[0].Np32 / 16; a.NT2 = blk[2].Np32 / 16; a.R = R;
     a.ldH = blk[0].Np32; a.ldYF = blk[2].Np32; a.split = (blk[2].nsub == 2) ? blk[2].joff[1] : (1 << 30);
     return m->opt.allow_block_fused && blk[1].Np32 == blk[0].Np32 && blk[2].KT == blk[1].KT && blk[1].Kp32 == blk[0].Np32 && block_fwd_ok(a);
-}
-
-// xf != null: the input rows are still fp32 [R][xdim] and the fused kernel converts them into XP itself -- only where block_fwd_shape says
-// that kernel runs (StepPlan::enc_takes_f32); elsewhere the caller runs prep_rows first
-int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R, const float* xf = nullptr, int xdim = 0) {
-    BlockFwdArgs a;
-    if (block_fwd_shape(m, blk, R, a)) {       // few rows: the whole block in one launch
-        a.X = XP; a.H1 = ptr<uint16_t>(w.h1P); a.H2 = ptr<uint16_t>(w.h2P); a.YF = ptr<float>(w.head);
-        if (xf) { a.Xf = xf; a.Xdim = xdim; a.XPout = const_cast<uint16_t*>(XP); }
-        launch_block_fwd(a, m->stream);
-        HIPCHK(hipGetLastError());
-        return IWAE_OK;
-    }
-    if (xf) return fail(IWAE_ERR_STATE, "block_fwd: float32 input rows on a shape block_fwd_kernel does not cover");
-    CHK(dense_fwd(m, blk[0], EPI_TANH, XP, R, ptr<uint16_t>(w.h1P), nullptr, 0));
-    CHK(dense_fwd(m, blk[1], EPI_TANH, ptr<uint16_t>(w.h1P), R, ptr<uint16_t>(w.h2P), nullptr, 0));
-    CHK(dense_fwd(m, blk[2], EPI_HEAD, ptr<uint16_t>(w.h2P), R, nullptr, ptr<float>(w.head), blk[2].Np32));
-    return IWAE_OK;
 }
 
 // ---------------------------------------------------------------- backward pieces
@@ -888,23 +464,6 @@ int block_wgrad_rows(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* inP
     launch_wgrad_rows(jobs, njobs, m->d_descs, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, fuse ? 1 : 0,
                       with_means ? ptr<float>(m->per_b) : nullptr, m->B, two ? 1.f : m->beta, m->d_scalars, m->d_zero, m->stream);
     HIPCHK(hipGetLastError());
-    return IWAE_OK;
-}
-
-bool is_device_ptr(const void* p, int device) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // plain host memory
-    return at.type == hipMemoryTypeDevice && at.device == device;
-}
-
-int copy_in(iwae_model* m, DevBuf& dst, const void* src, size_t bytes) {
-    CHK(ensure(dst, bytes, m->stream));
-    HIPCHK(hipMemcpyAsync(dst.p, src, bytes, hipMemcpyDefault, m->stream));
-    return IWAE_OK;
-}
-
-int copy_out(iwae_model* m, void* dst, const void* src, size_t bytes) {
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, m->stream));
     return IWAE_OK;
 }
 
@@ -1202,10 +761,7 @@ int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float
                                ptr<uint16_t>(m->xP), xf, m->stream, m->C > 0 ? ptr<uint8_t>(m->ds_labels) : nullptr, m->C, m->C > 0 ? ptr<float>(m->cond) : nullptr);
         m->ds_start = -1;
         *xd = xf;
-    } else if (!is_device_ptr(x, m->cfg.device)) {
-        CHK(copy_in(m, m->xin, x, (size_t)B * m->X * 4));
-        *xd = ptr<float>(m->xin);
-    }
+    } else CHK(staged_in(m, x, m->xin, (size_t)B * m->X * 4, xd));
     return IWAE_OK;
 }
 
@@ -1919,10 +1475,6 @@ int f32_gemm(iwae_model* m, const float* A, long sam, long sak, const float* B, 
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
-// Y = epi(X W + b), W = the Keras kernel [in, out] of layer kl inside the flat float32 parameters
-int f32_fwd(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, int rows, float* Y, long ldy, int epi, bool no_ksplit) {
-    return f32_gemm(m, X, ldx, 1, m->param + kl.offW, kl.Nout, 1, Y, ldy, rows, kl.Nout, kl.Kin, m->param + kl.offb, epi, nullptr, 0, false, nullptr, nullptr, nullptr, no_ksplit);
-}
 // DX (+)= (G W^T) * (1 - ACT^2)   (ACT = the stored tanh output of the layer below, or null)
 // (rowscale: row r of G counts with weight rowscale[r] -- applied to the product's rows, in front of the tanh' factor)
 int f32_dx(iwae_model* m, const KerasLayer& kl, const float* G, long ldg, int rows, float* DX, long lddx, const float* ACT, long ldact, bool accumulate,
@@ -2005,18 +1557,6 @@ int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const 
         }
     }
     HIPCHK(hipGetLastError());
-    return IWAE_OK;
-}
-// BasicBlock (iwae1.py:36-44) on R rows: X [R][ldx] -> h1, h2 [R][H], head [R][2Dp] (mu at 0.., sigma = exp(.)+1e-6 at Dp..)
-int f32_block_fwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, float* head, int Dp, bool no_ksplit) {
-    const KerasLayer *l1 = &m->klayers[base], *l2 = l1 + 1, *lmu = l1 + 2, *lsd = l1 + 3;
-    const int H = l1->Nout;
-    CHK(ensure(w.h1, (size_t)R * H * 4, m->stream));
-    CHK(ensure(w.h2, (size_t)R * H * 4, m->stream));
-    CHK(f32_fwd(m, *l1, X, ldx, R, ptr<float>(w.h1), H, GEMM_EPI_TANH, no_ksplit));
-    CHK(f32_fwd(m, *l2, ptr<float>(w.h1), H, R, ptr<float>(w.h2), H, GEMM_EPI_TANH, no_ksplit));
-    CHK(f32_fwd(m, *lmu, ptr<float>(w.h2), H, R, head, 2 * Dp, GEMM_EPI_NONE, no_ksplit));
-    CHK(f32_fwd(m, *lsd, ptr<float>(w.h2), H, R, head + Dp, 2 * Dp, GEMM_EPI_EXP, no_ksplit));
     return IWAE_OK;
 }
 // backward of a BasicBlock from dhead [R][2Dp] (d mu | d pre-exp): all four weight gradients, optionally dX [R][lddx]
@@ -2422,6 +1962,124 @@ int dp_finish(iwae_model* m, float lr) {
 
 }  // namespace
 
+// ---------------------------------------------------------------- helpers analysis.hip calls too (declared in model.h)
+int ensure(DevBuf& b, size_t bytes, hipStream_t st) {
+    if (bytes <= b.cap) return IWAE_OK;
+    if (b.p) {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipFree(b.p));
+        b.p = nullptr;
+        b.cap = 0;
+    }
+    const size_t want = bytes + bytes / 8 + 256;
+    HIPCHK(hipMalloc(&b.p, want));
+    b.cap = want;
+    return IWAE_OK;
+}
+void free_buf(DevBuf& b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
+// orders the main stream behind a deferred decoder update (and the noise prefetch in front of it) still on the side stream
+int join_side(iwae_model* m) {
+    if (m->dec2_pending) {      // (2-layer step: the first side stream's own deferred update)
+        HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec2, 0));
+        m->dec2_pending = false;
+    }
+    if (!m->dec_pending) return IWAE_OK;
+    HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec, 0));
+    m->dec_pending = false;
+    return IWAE_OK;
+}
+
+int dense_fwd(iwae_model* m, Linear& L, int epi, const uint16_t* XP, int rows, uint16_t* YP, float* YF, int ldYF, const SampleArgs* zin) {
+    DenseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.X = XP; a.ldX = L.Kp32; a.img = L.imgF;
+    a.split = (L.nsub == 2) ? L.joff[1] : (1 << 30);
+    a.M = rows; a.KT = L.KT; a.MG = L.MG; a.mg_per_block = (rows <= 8192) ? 1 : L.MG; a.Np32 = L.Np32; a.g1_mask = m->opt.dense_g1_mask;
+    a.stage_all = (a.mg_per_block == 1 && L.KT > 8 && (L.KT + 7) / 8 <= 4) ? 1 : 0;
+    if (zin) {      // sampled-input mode: the layer makes its own input rows z = mu + sigma*eps (and keeps them in zin->ZP)
+        a.zhead = zin->head; a.ldZH = zin->ldH; a.zeps = zin->eps.cache; a.zldE = zin->eps.ldC; a.zD = zin->D; a.zDp = zin->Dp;
+        a.ZPout = zin->ZP; a.zlp = zin->lp_prior; a.zlq = zin->lq; a.k = zin->k;
+        a.mg_per_block = L.MG;          // one block owns all out-feature groups of its rows (the z rows are made once)
+    }
+    a.YP = YP; a.ldYP = L.Np32; a.YF = YF; a.ldYF = ldYF;
+    CHK(attach_dense_stamps(m, epi, a));
+    launch_dense(epi, a, m->stream);
+    HIPCHK(hipGetLastError());
+    return IWAE_OK;
+}
+
+int block_alloc(iwae_model* m, Linear* blk, BlockWs& w, int R, int Rp, bool bwd, bool need_dx) {
+    const int Hp = blk[0].Np32, N2 = blk[2].Np32;
+    CHK(ensure(w.h1P, (size_t)Rp * Hp * 2, m->stream));
+    CHK(ensure(w.h2P, (size_t)Rp * Hp * 2, m->stream));
+    CHK(ensure(w.head, (size_t)Rp * N2 * 4, m->stream));
+    if (bwd) {
+        CHK(ensure(w.dheadP, (size_t)Rp * N2 * 2, m->stream));
+        CHK(ensure(w.d2P, (size_t)Rp * Hp * 2, m->stream));
+        CHK(ensure(w.d1P, (size_t)Rp * Hp * 2, m->stream));
+        if (need_dx) CHK(ensure(w.dx, (size_t)Rp * blk[0].Kp32 * 4, m->stream));
+    }
+    (void)R;
+    return IWAE_OK;
+}
+
+// xf != null: the input rows are still fp32 [R][xdim] and the fused kernel converts them into XP itself -- only where block_fwd_shape says
+// that kernel runs (StepPlan::enc_takes_f32); elsewhere the caller runs prep_rows first
+int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R, const float* xf, int xdim) {
+    BlockFwdArgs a;
+    if (block_fwd_shape(m, blk, R, a)) {       // few rows: the whole block in one launch
+        a.X = XP; a.H1 = ptr<uint16_t>(w.h1P); a.H2 = ptr<uint16_t>(w.h2P); a.YF = ptr<float>(w.head);
+        if (xf) { a.Xf = xf; a.Xdim = xdim; a.XPout = const_cast<uint16_t*>(XP); }
+        launch_block_fwd(a, m->stream);
+        HIPCHK(hipGetLastError());
+        return IWAE_OK;
+    }
+    if (xf) return fail(IWAE_ERR_STATE, "block_fwd: float32 input rows on a shape block_fwd_kernel does not cover");
+    CHK(dense_fwd(m, blk[0], EPI_TANH, XP, R, ptr<uint16_t>(w.h1P), nullptr, 0));
+    CHK(dense_fwd(m, blk[1], EPI_TANH, ptr<uint16_t>(w.h1P), R, ptr<uint16_t>(w.h2P), nullptr, 0));
+    CHK(dense_fwd(m, blk[2], EPI_HEAD, ptr<uint16_t>(w.h2P), R, nullptr, ptr<float>(w.head), blk[2].Np32));
+    return IWAE_OK;
+}
+
+bool is_device_ptr(const void* p, int device) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // plain host memory
+    return at.type == hipMemoryTypeDevice && at.device == device;
+}
+
+int copy_in(iwae_model* m, DevBuf& dst, const void* src, size_t bytes) {
+    CHK(ensure(dst, bytes, m->stream));
+    HIPCHK(hipMemcpyAsync(dst.p, src, bytes, hipMemcpyDefault, m->stream));
+    return IWAE_OK;
+}
+
+int copy_out(iwae_model* m, void* dst, const void* src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, m->stream));
+    return IWAE_OK;
+}
+
+// Y = epi(X W + b), W = the Keras kernel [in, out] of layer kl inside the flat float32 parameters
+int f32_fwd(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, int rows, float* Y, long ldy, int epi, bool no_ksplit) {
+    return f32_gemm(m, X, ldx, 1, m->param + kl.offW, kl.Nout, 1, Y, ldy, rows, kl.Nout, kl.Kin, m->param + kl.offb, epi, nullptr, 0, false, nullptr, nullptr, nullptr, no_ksplit);
+}
+// BasicBlock (iwae1.py:36-44) on R rows: X [R][ldx] -> h1, h2 [R][H], head [R][2Dp] (mu at 0.., sigma = exp(.)+1e-6 at Dp..)
+int f32_block_fwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, float* head, int Dp, bool no_ksplit) {
+    const KerasLayer *l1 = &m->klayers[base], *l2 = l1 + 1, *lmu = l1 + 2, *lsd = l1 + 3;
+    const int H = l1->Nout;
+    CHK(ensure(w.h1, (size_t)R * H * 4, m->stream));
+    CHK(ensure(w.h2, (size_t)R * H * 4, m->stream));
+    CHK(f32_fwd(m, *l1, X, ldx, R, ptr<float>(w.h1), H, GEMM_EPI_TANH, no_ksplit));
+    CHK(f32_fwd(m, *l2, ptr<float>(w.h1), H, R, ptr<float>(w.h2), H, GEMM_EPI_TANH, no_ksplit));
+    CHK(f32_fwd(m, *lmu, ptr<float>(w.h2), H, R, head, 2 * Dp, GEMM_EPI_NONE, no_ksplit));
+    CHK(f32_fwd(m, *lsd, ptr<float>(w.h2), H, R, head + Dp, 2 * Dp, GEMM_EPI_EXP, no_ksplit));
+    return IWAE_OK;
+}
+
 // =================================================================== C ABI
 extern "C" {
 
@@ -2548,52 +2206,18 @@ void iwae_destroy(iwae_handle m) {
     for (Linear* L : all_linears(m)) free_linear(*L);
     DevBuf* bufs[] = {&m->xin, &m->xP, &m->epsbuf, &m->zP[0], &m->zP[1], &m->rows[0], &m->rows[1],
                       &m->rows[2], &m->rows[3], &m->rows[4], &m->rows[5], &m->logw, &m->wn, &m->gx, &m->cf, &m->per_b, &m->logw2, &m->wn2, &m->gx2, &m->cf2, &m->per_b2,
-                      &m->dzdir, &m->scratch, &m->ds_data, &m->ds_order, &m->dstamps, &m->px_part, &m->dg2_part, &m->cond, &m->condP, &m->epsc[0][0], &m->epsc[0][1], &m->epsc[1][0], &m->epsc[1][1], &m->epsc[2][0], &m->epsc[2][1], &m->eval_x, &m->eval_lme,
-                      &m->ds_labels, &m->epsm[0][0], &m->epsm[0][1], &m->epsm[1][0], &m->epsm[1][1]};
+                      &m->dzdir, &m->scratch, &m->ds_data, &m->ds_order, &m->dstamps, &m->px_part, &m->dg2_part, &m->cond, &m->condP, &m->epsc[0][0], &m->epsc[0][1], &m->epsc[1][0], &m->epsc[1][1], &m->epsc[2][0], &m->epsc[2][1], &m->eval_lme,
+                      &m->ds_labels, &m->epsm[0][0], &m->epsm[0][1], &m->epsm[1][0], &m->epsm[1][1], &m->stamps};
     for (DevBuf* b : bufs) free_buf(*b);
-    {
-        iwae_model::GridWs& g = m->grid;
-        DevBuf* bb[] = {&g.x, &g.xb, &g.xP, &g.flag, &g.head, &g.z, &g.lw, &g.zP, &g.h1, &g.h2, &g.logits, &g.lhi, &g.llo, &g.c, &g.zc, &g.w,
-                        &g.part, &g.run, &g.lpx, &g.mean, &g.cov, &g.qmass, &g.kl, &g.lj};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
-    {
-        iwae_model::ActWs& a = m->act;
-        DevBuf* bb[] = {&a.x, &a.xP, &a.head, &a.eps, &a.z, &a.rows, &a.part, &a.pm, &a.act, &a.dm, &a.blk.h1P, &a.blk.h2P, &a.blk.head,
-                        &a.blk.dheadP, &a.blk.d2P, &a.blk.d1P, &a.blk.dx, &a.f32.h1, &a.f32.h2, &a.f32.dhead, &a.f32.d2, &a.f32.d1, &a.f32.dx};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
-    {
-        DevBuf* bb[] = {&m->mom_ws.x, &m->mom_ws.mean, &m->mom_ws.m2};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
-    {
-        iwae_model::AggWs& g = m->agg;
-        DevBuf* bb[] = {&g.x, &g.xP, &g.head, &g.eps, &g.mu, &g.inv, &g.invd, &g.nls, &g.nls_sum, &g.zT, &g.shT, &g.dim_part, &g.jmax, &g.jsum, &g.lqz, &g.lqzdT,
-                        &g.lqzd, &g.part, &g.out};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
-    {
-        iwae_model::AisWs& g = m->ais;
-        DevBuf* bb[] = {&g.x, &g.xP, &g.head, &g.wpad, &g.betas, &g.e, &g.logw, &g.h, &g.nacc, &g.z0, &g.mom, &g.unif, &g.dH, &g.acc, &g.rate, &g.z, &g.lpx, &g.ess};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
-    BlockWs* bw[] = {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior};
-    for (BlockWs* w : bw) {
-        DevBuf* bb[] = {&w->h1P, &w->h2P, &w->head, &w->dheadP, &w->d2P, &w->d1P, &w->dx};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
-    {
-        MlpWs* w = &m->wdec1;
-        DevBuf* bb[] = {&w->g1P, &w->g2P, &w->dlP, &w->d2P, &w->d1P, &w->dz};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
-    {
-        iwae_model::F32Block* fb[] = {&m->f32.enc1, &m->f32.enc2, &m->f32.dec2, &m->f32.prior};
-        for (auto* w : fb) { DevBuf* bb[] = {&w->h1, &w->h2, &w->dhead, &w->d2, &w->d1, &w->dx}; for (DevBuf* b : bb) free_buf(*b); }
-        DevBuf* bb[] = {&m->f32.z[0], &m->f32.z[1], &m->f32.g1, &m->f32.g2, &m->f32.logits, &m->f32.d2, &m->f32.d1, &m->f32.slab, &m->f32.bpart, &m->f32.xcat, &m->f32.kslab};
-        for (DevBuf* b : bb) free_buf(*b);
-    }
+    free_all(m->ev);
+    free_all(m->grid);
+    free_all(m->act);
+    free_all(m->mom_ws);
+    free_all(m->agg);
+    free_all(m->ais);
+    for (BlockWs* w : {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior}) free_all(*w);
+    free_all(m->wdec1);
+    free_all(m->f32);
     if (m->param) (void)hipFree(m->param);
     if (m->grad) (void)hipFree(m->grad);
     if (m->mom) (void)hipFree(m->mom);
@@ -3029,7 +2653,7 @@ int iwae_eval_llh(iwae_handle m, const float* x, int32_t N, int32_t k, int32_t c
     const int ns = (k + kc - 1) / kc;
     const float* xd = x;
     const size_t xbytes = (size_t)N * m->X * 4;
-    if (!is_device_ptr(x, m->cfg.device) && xbytes <= ((size_t)1 << 31)) { CHK(copy_in(m, m->eval_x, x, xbytes)); xd = ptr<float>(m->eval_x); }
+    if (xbytes <= ((size_t)1 << 31)) CHK(staged_in(m, x, m->ev.x, xbytes, &xd));      // (a larger host array is passed on as it is)
     CHK(ensure(m->eval_lme, (size_t)ns * N * 4, m->stream));
     int rc = IWAE_OK;
     for (int i0 = 0; i0 < N && rc == IWAE_OK; i0 += chunk) {
@@ -3130,524 +2754,6 @@ int iwae_decode(iwae_handle m, const float* z, int32_t n, float* probs) {
     return IWAE_OK;
 }
 
-// Grid points per chunk of iwae_grid_posterior: ~8 KB of chunk-sized buffers per point at 784 pixels (logits, L_hi + L_lo, two hidden layers
-// in float32), so 32 768 points keep them near 256 MB whatever G is.
-#define GRID_CHUNK_DEFAULT 32768
-
-// Encoder heads mu | sigma (src/iwae1.py:39-42) of N images xd [N][x_dim] (device) in the eval precision, for iwae_grid_posterior and
-// iwae_latent_activity: mu_i at (*head)[i * ldh], sigma_i at Dp[0] further.  float32: f32_block_fwd into headbuf; bf16: block_fwd on the
-// bf16 rows xPbuf into the handle's encoder workspace.
-static int eval_enc_heads(iwae_model* m, const float* xd, int N, DevBuf& headbuf, DevBuf& xPbuf, const float** head, int* ldh) {
-    hipStream_t st = m->stream;
-    const int X = m->X, Xp = m->Xp32, Dp = m->Dp[0];
-    if (m->eval_precision == IWAE_PREC_FP32) {
-        CHK(ensure(headbuf, (size_t)N * 2 * Dp * 4, st));
-        CHK(f32_block_fwd(m, m->enc1[0].sub[0], m->f32.enc1, xd, X, N, ptr<float>(headbuf), Dp, true));      // (no K split of the few-row products: an image's heads must not depend on N)
-        *head = ptr<float>(headbuf); *ldh = 2 * Dp;
-    } else {
-        const int Nbp = round_up(N, 128);
-        CHK(ensure(xPbuf, (size_t)Nbp * Xp * 2, st));
-        launch_prep_rows(xd, nullptr, N, X, 0, Xp, Nbp, ptr<uint16_t>(xPbuf), st);
-        CHK(block_alloc(m, m->enc1, m->wenc1, N, Nbp, false, false));
-        CHK(block_fwd(m, m->enc1, m->wenc1, ptr<uint16_t>(xPbuf), N));
-        *head = ptr<float>(m->wenc1.head); *ldh = m->enc1[2].Np32;
-    }
-    return IWAE_OK;
-}
-
-int iwae_grid_posterior(iwae_handle m, const float* x, int32_t N, const float* z, const float* log_wq, int32_t G, double* log_px,
-                        float* post_mean, float* post_cov, float* q_mu, float* q_sigma, float* q_mass, float* kl_q_post, float* log_joint) {
-    if (!m || !x || !z || !log_px) return fail(IWAE_ERR_ARG, "grid_posterior: need x, z and log_px");
-    if (N <= 0 || G <= 0) return fail(IWAE_ERR_ARG, "grid_posterior: N and G must be positive");
-    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "grid_posterior: only the 1-layer model (the 2-layer model needs a nested integral over z1)");
-    if (m->C != 0) return fail(IWAE_ERR_ARG, "grid_posterior: only the unconditional model (cond_dim = 0)");
-    if (m->D[0] > GRID_D_MAX) return fail(IWAE_ERR_ARG, "grid_posterior: needs n_latent <= 4 (got " + std::to_string(m->D[0]) + ")");
-    if (m->Xp32 > GRID_XP_MAX) return fail(IWAE_ERR_ARG, "grid_posterior: needs x_dim <= " + std::to_string(GRID_XP_MAX));
-    HIPCHK(hipSetDevice(m->cfg.device));
-    CHK(join_side(m));      // the parameters a deferred update may still be writing
-    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
-    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
-    hipStream_t st = m->stream;
-    iwae_model::GridWs& w = m->grid;
-    const int D = m->D[0], Dp = m->Dp[0], X = m->X, Xp = m->Xp32, Np = round_up(N, 64);
-    const bool f32 = m->eval_precision == IWAE_PREC_FP32;
-    // ---- images: bf16 copy for the score kernel + the binary check (the scores rely on x being exact in bf16)
-    const float* xd = x;
-    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * X * 4)); xd = ptr<float>(w.x); }
-    CHK(ensure(w.xb, (size_t)Np * Xp * 2, st));
-    CHK(ensure(w.flag, 4, st));
-    HIPCHK(hipMemsetAsync(w.flag.p, 0, 4, st));
-    launch_grid_prep_x(xd, N, X, Np, Xp, ptr<uint16_t>(w.xb), ptr<int>(w.flag), st);
-    HIPCHK(hipGetLastError());
-    int nonbinary = 0;
-    HIPCHK(hipMemcpyAsync(&nonbinary, w.flag.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (nonbinary) return fail(IWAE_ERR_ARG, "grid_posterior: x must be binary (every value 0 or 1)");
-    // ---- encoder heads mu, sigma of the N images (src/iwae1.py:39-42), in the eval precision
-    const float* head;
-    int ldh;
-    CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
-    if (q_mu) HIPCHK(hipMemcpy2DAsync(q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
-    if (q_sigma) HIPCHK(hipMemcpy2DAsync(q_sigma, (size_t)D * 4, head + Dp, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
-    // ---- G in chunks: decoder logits -> prep -> score -> merge into the running per-image state
-    const int chunk = m->opt.grid_chunk > 0 ? m->opt.grid_chunk : GRID_CHUNK_DEFAULT;
-    const int gmax = std::min(chunk, (int)G), gmaxp = round_up(gmax, 128), H = m->H[0], Hp = m->dec1[0].Np32;
-    CHK(ensure(w.run, (size_t)N * GRID_ST * 8, st));
-    CHK(ensure(w.lpx, (size_t)N * 8, st));
-    CHK(ensure(w.mean, (size_t)N * D * 4, st));
-    CHK(ensure(w.cov, (size_t)N * D * D * 4, st));
-    CHK(ensure(w.qmass, (size_t)N * 4, st));
-    CHK(ensure(w.kl, (size_t)N * 4, st));
-    CHK(ensure(w.z, (size_t)gmax * D * 4, st));
-    if (log_wq) CHK(ensure(w.lw, (size_t)gmax * 4, st));
-    CHK(ensure(w.logits, (size_t)gmaxp * Xp * 4, st));
-    CHK(ensure(w.lhi, (size_t)gmaxp * Xp * 2, st));
-    CHK(ensure(w.llo, (size_t)gmaxp * Xp * 2, st));
-    CHK(ensure(w.c, (size_t)gmaxp * 4, st));
-    CHK(ensure(w.zc, (size_t)gmaxp * 16, st));
-    CHK(ensure(w.w, (size_t)gmaxp * 4, st));
-    if (f32) {
-        CHK(ensure(w.h1, (size_t)gmax * H * 4, st));
-        CHK(ensure(w.h2, (size_t)gmax * H * 4, st));
-    } else {
-        CHK(ensure(w.zP, (size_t)gmaxp * Dp * 2, st));
-        CHK(ensure(w.h1, (size_t)gmaxp * Hp * 2, st));
-        CHK(ensure(w.h2, (size_t)gmaxp * Hp * 2, st));
-    }
-    const int nsplit_max = (gmax + GRID_RANGE - 1) / GRID_RANGE;
-    CHK(ensure(w.part, (size_t)nsplit_max * N * GRID_ST * 4, st));
-    float* lj = nullptr;
-    if (log_joint) {
-        if (is_device_ptr(log_joint, m->cfg.device)) lj = log_joint;
-        else { CHK(ensure(w.lj, (size_t)N * G * 4, st)); lj = ptr<float>(w.lj); }
-    }
-    const KerasLayer* d1 = &m->klayers[m->dec1[0].sub[0]];
-    for (int c0 = 0; c0 < G; c0 += chunk) {
-        const int Gc = std::min(chunk, (int)G - c0), Gcp = round_up(Gc, 128);
-        HIPCHK(hipMemcpyAsync(w.z.p, z + (size_t)c0 * D, (size_t)Gc * D * 4, hipMemcpyDefault, st));
-        if (log_wq) HIPCHK(hipMemcpyAsync(w.lw.p, log_wq + c0, (size_t)Gc * 4, hipMemcpyDefault, st));
-        // decoder logits l_g (src/iwae1.py:72-75), as iwae_decode / forward_f32 compute them
-        if (f32) {
-            CHK(f32_fwd(m, d1[0], ptr<float>(w.z), D, Gc, ptr<float>(w.h1), H, GEMM_EPI_TANH, false));
-            CHK(f32_fwd(m, d1[1], ptr<float>(w.h1), H, Gc, ptr<float>(w.h2), H, GEMM_EPI_TANH, false));
-            CHK(f32_fwd(m, d1[2], ptr<float>(w.h2), H, Gc, ptr<float>(w.logits), Xp, GEMM_EPI_NONE, false));
-        } else {
-            launch_prep_rows(ptr<float>(w.z), nullptr, Gc, D, 0, Dp, Gcp, ptr<uint16_t>(w.zP), st);
-            CHK(dense_fwd(m, m->dec1[0], EPI_TANH, ptr<uint16_t>(w.zP), Gc, ptr<uint16_t>(w.h1), nullptr, 0));
-            CHK(dense_fwd(m, m->dec1[1], EPI_TANH, ptr<uint16_t>(w.h1), Gc, ptr<uint16_t>(w.h2), nullptr, 0));
-            // (EPI_HEAD on the output layer: fp32 logits with the bias -- its exp split lies beyond the one-sub-layer map; EPI_F32 adds no bias)
-            CHK(dense_fwd(m, m->dec1[2], EPI_HEAD, ptr<uint16_t>(w.h2), Gc, nullptr, ptr<float>(w.logits), Xp));
-        }
-        GridPrepArgs pa;
-        memset(&pa, 0, sizeof(pa));
-        pa.logits = ptr<float>(w.logits); pa.ldl = Xp; pa.z = ptr<float>(w.z); pa.lw = log_wq ? ptr<float>(w.lw) : nullptr;
-        pa.Gc = Gc; pa.Gcp = round_up(Gc, 16); pa.X = X; pa.Xp = Xp; pa.D = D;
-        pa.Lhi = ptr<uint16_t>(w.lhi); pa.Llo = ptr<uint16_t>(w.llo); pa.c = ptr<float>(w.c); pa.zc = ptr<float4>(w.zc); pa.w = ptr<float>(w.w);
-        launch_grid_prep(pa, st);
-        HIPCHK(hipGetLastError());
-        GridScoreArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.XB = ptr<uint16_t>(w.xb); sa.Xp = Xp; sa.Lhi = pa.Lhi; sa.Llo = pa.Llo; sa.c = pa.c; sa.zc = pa.zc; sa.w = pa.w;
-        sa.head = head; sa.ldh = ldh; sa.soff = Dp; sa.N = N; sa.Gc = Gc; sa.nsplit = (Gc + GRID_RANGE - 1) / GRID_RANGE;
-        sa.part = ptr<float>(w.part); sa.log_joint = lj; sa.ldlj = G; sa.lj_col = c0;
-        launch_grid_score(sa, D, st);
-        HIPCHK(hipGetLastError());
-        GridMergeArgs ma;
-        memset(&ma, 0, sizeof(ma));
-        ma.part = sa.part; ma.nsplit = sa.nsplit; ma.N = N; ma.D = D; ma.run = ptr<double>(w.run);
-        ma.first = c0 == 0; ma.last = c0 + Gc >= G; ma.head = head; ma.ldh = ldh;
-        ma.log_px = ptr<double>(w.lpx); ma.mean = ptr<float>(w.mean); ma.cov = ptr<float>(w.cov); ma.qmass = ptr<float>(w.qmass); ma.kl = ptr<float>(w.kl);
-        launch_grid_merge(ma, st);
-        HIPCHK(hipGetLastError());
-    }
-    CHK(copy_out(m, log_px, w.lpx.p, (size_t)N * 8));
-    if (post_mean) CHK(copy_out(m, post_mean, w.mean.p, (size_t)N * D * 4));
-    if (post_cov) CHK(copy_out(m, post_cov, w.cov.p, (size_t)N * D * D * 4));
-    if (q_mass) CHK(copy_out(m, q_mass, w.qmass.p, (size_t)N * 4));
-    if (kl_q_post) CHK(copy_out(m, kl_q_post, w.kl.p, (size_t)N * 4));
-    if (log_joint && lj != log_joint) CHK(copy_out(m, log_joint, lj, (size_t)N * G * 4));
-    HIPCHK(hipStreamSynchronize(st));
-    m->have_forward = false;
-    return IWAE_OK;
-}
-
-int iwae_latent_activity(iwae_handle m, const float* x, int32_t N, int32_t k, const float* eps, double* activity, double* data_mean, float* post_mean) {
-    if (!m || !x) return fail(IWAE_ERR_ARG, "latent_activity: need x");
-    if (!activity) return fail(IWAE_ERR_ARG, "latent_activity: activity is required");
-    if (N <= 0) return fail(IWAE_ERR_ARG, "latent_activity: N must be positive");
-    if (m->C != 0) return fail(IWAE_ERR_ARG, "latent_activity: only the unconditional models (cond_dim = 0)");
-    const bool two = m->cfg.n_layers == 2;
-    if (two && k <= 0) return fail(IWAE_ERR_ARG, "latent_activity: k must be positive for the 2-layer model");
-    HIPCHK(hipSetDevice(m->cfg.device));
-    CHK(join_side(m));      // the parameters a deferred update may still be writing
-    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
-    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
-    hipStream_t st = m->stream;
-    iwae_model::ActWs& w = m->act;
-    const bool f32 = m->eval_precision == IWAE_PREC_FP32;
-    const int D0 = m->D[0], Dp0 = m->Dp[0], D1 = two ? m->D[1] : 0, Dt = D0 + D1;
-    const float* xd = x;
-    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * m->X * 4)); xd = ptr<float>(w.x); }
-    // ---- layer 1: E_q[z1|x] = mu1(x), the encoder head
-    const float* head;
-    int ldh;
-    CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
-    CHK(ensure(w.pm, (size_t)N * Dt * 4, st));
-    CHK(ensure(w.act, (size_t)Dt * 8, st));
-    CHK(ensure(w.dm, (size_t)Dt * 8, st));
-    ActStatsArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.src = head; sa.ld_img = ldh; sa.ld_blk = 0; sa.nblk = 1; sa.kdiv = 1.0; sa.N = N; sa.D = D0;
-    sa.post_mean = ptr<float>(w.pm); sa.ldpm = Dt; sa.col = 0; sa.activity = ptr<double>(w.act); sa.data_mean = ptr<double>(w.dm);
-    launch_act_stats(sa, st);
-    HIPCHK(hipGetLastError());
-    if (two) {
-        // ---- layer 2: E_q[z2|x] = E_{z1 ~ q(z1|x)}[mu2(z1)], summed per (image, ACT_BLOCK-sample block), launches of at most eval_rows rows:
-        // whole images while k fits (kc = k), else one image at a time in sample chunks of a multiple of ACT_BLOCK -- so a block never
-        // straddles two launches and an image's partials do not depend on the chunking.
-        const Linear* e2 = m->enc2;
-        const bool fused = !f32 && act_chain_ok(e2[0].KT, e2[1].KT, m->Dp[1] / 32) && e2[0].Kp32 == Dp0 && e2[0].Np32 == 32 * e2[1].KT &&
-                           e2[1].Np32 == e2[0].Np32 && e2[2].KT == e2[1].KT && e2[2].Np32 == 2 * m->Dp[1] && ldh == 2 * Dp0;
-        const int eval_rows = m->opt.eval_rows > 0 ? m->opt.eval_rows : 1 << 19;
-        // (bf16 composed path: at most 4096 rows, where block_fwd is one block_fwd_kernel launch on any row count -- a row's mu2 does not
-        // depend on how many rows share its launch)
-        const int cap = (!f32 && !fused) ? std::min(eval_rows, 4096) : eval_rows;
-        const int kc = k <= cap ? k : std::max(ACT_BLOCK, cap / ACT_BLOCK * ACT_BLOCK);
-        const int nbmax = kc == k ? std::max(1, std::min(32768, cap / k)) : 1;
-        const int nblk = (k + ACT_BLOCK - 1) / ACT_BLOCK;
-        CHK(ensure(w.part, (size_t)N * nblk * D1 * 4, st));
-        const size_t rows_max = (size_t)std::min(nbmax, (int)N) * kc, rows_maxp = round_up((int)rows_max, 128);
-        CHK(ensure(w.eps, rows_max * D0 * 4, st));
-        if (!fused) {
-            CHK(ensure(w.rows, rows_maxp * 4, st));
-            if (f32) {
-                const int H = m->klayers[e2[0].sub[0]].Nout;
-                CHK(ensure(w.z, rows_maxp * D0 * 4, st));
-                CHK(ensure(w.f32.h1, rows_maxp * H * 4, st));
-                CHK(ensure(w.f32.h2, rows_maxp * H * 4, st));
-                CHK(ensure(w.blk.head, rows_maxp * D1 * 4, st));
-            } else {
-                CHK(ensure(w.z, rows_maxp * Dp0 * 2, st));
-                CHK(block_alloc(m, m->enc2, w.blk, (int)rows_max, (int)rows_maxp, false, false));
-            }
-        }
-        const uint32_t step = m->noise_step;
-        for (int i0 = 0; i0 < N; i0 += nbmax) {
-            const int nb = std::min(nbmax, (int)N - i0);
-            for (int s0 = 0; s0 < k; s0 += kc) {
-                const int kn = std::min(kc, (int)k - s0), M = nb * kn, Mp = round_up(M, 128);
-                EpsSrc e;
-                e.seed = m->cfg.seed; e.step = step; e.stream = 0;
-                e.row_offset = (uint64_t)(m->batch_offset + (uint32_t)i0) * (uint64_t)k;     // iwae_eval_llh's Philox rows: (offset + i) k + s
-                e.k_total = k; e.s_off = s0; e.kc = kn;
-                if (eps) {      // the caller's [k][N][D0] draws of this chunk -> [kn][nb][D0]
-                    HIPCHK(hipMemcpy2DAsync(w.eps.p, (size_t)nb * D0 * 4, eps + ((size_t)s0 * N + i0) * D0, (size_t)N * D0 * 4, (size_t)nb * D0 * 4, kn, hipMemcpyDefault, st));
-                    e.user = ptr<float>(w.eps);
-                }
-                e.B = nb;
-                const float* hd = head + (size_t)i0 * ldh;
-                if (fused) {
-                    ActChainArgs c;
-                    memset(&c, 0, sizeof(c));
-                    c.img1 = e2[0].imgF; c.img2 = e2[1].imgF; c.imgh = e2[2].imgF;
-                    c.head1 = hd; c.ldH1 = ldh; c.eps1 = e; c.kn = kn; c.D0 = D0; c.D1 = D1;
-                    c.part = ptr<float>(w.part); c.nblk = nblk; c.img0 = i0; c.blk0 = s0 / ACT_BLOCK;
-                    launch_act_chain(c, nb, st);
-                } else {
-                    SampleArgs sm;
-                    memset(&sm, 0, sizeof(sm));
-                    sm.head = hd; sm.ldH = ldh; sm.Dp = Dp0; sm.D = D0; sm.head_per_row = 0;
-                    sm.M = M; sm.Mp = Mp; sm.k = kn; sm.B = nb; sm.eps = e;
-                    sm.lq = ptr<float>(w.rows);
-                    const float* mu2;
-                    int ldm;
-                    if (f32) {      // z1 rows in float32 -> the q(z2|z1) block's two tanh layers and its mu head (the sigma head is not needed)
-                        sm.ZF = ptr<float>(w.z); sm.ldZF = D0;
-                        launch_sample(sm, st);
-                        const KerasLayer* l1 = &m->klayers[e2[0].sub[0]];
-                        const int H = l1->Nout;
-                        // (no K split of few-row products: an image's mu2 must not depend on how many share the launch)
-                        CHK(f32_fwd(m, l1[0], ptr<float>(w.z), D0, M, ptr<float>(w.f32.h1), H, GEMM_EPI_TANH, true));
-                        CHK(f32_fwd(m, l1[1], ptr<float>(w.f32.h1), H, M, ptr<float>(w.f32.h2), H, GEMM_EPI_TANH, true));
-                        CHK(f32_fwd(m, l1[2], ptr<float>(w.f32.h2), H, M, ptr<float>(w.blk.head), D1, GEMM_EPI_NONE, true));
-                        mu2 = ptr<float>(w.blk.head); ldm = D1;
-                    } else {
-                        sm.ZP = ptr<uint16_t>(w.z);
-                        launch_sample(sm, st);
-                        CHK(block_fwd(m, m->enc2, w.blk, ptr<uint16_t>(w.z), M));
-                        mu2 = ptr<float>(w.blk.head); ldm = e2[2].Np32;
-                    }
-                    ActPartialArgs pa;
-                    memset(&pa, 0, sizeof(pa));
-                    pa.head = mu2; pa.ldh = ldm; pa.nb = nb; pa.kn = kn; pa.D1 = D1;
-                    pa.part = ptr<float>(w.part); pa.nblk = nblk; pa.img0 = i0; pa.blk0 = s0 / ACT_BLOCK;
-                    launch_act_partial(pa, st);
-                }
-                HIPCHK(hipGetLastError());
-            }
-        }
-        sa.src = ptr<float>(w.part); sa.ld_img = (long)nblk * D1; sa.ld_blk = D1; sa.nblk = nblk; sa.kdiv = (double)k; sa.D = D1; sa.col = D0;
-        launch_act_stats(sa, st);
-        HIPCHK(hipGetLastError());
-        m->noise_step += 1;
-    }
-    CHK(copy_out(m, activity, w.act.p, (size_t)Dt * 8));
-    if (data_mean) CHK(copy_out(m, data_mean, w.dm.p, (size_t)Dt * 8));
-    if (post_mean) CHK(copy_out(m, post_mean, w.pm.p, (size_t)N * Dt * 4));
-    HIPCHK(hipStreamSynchronize(st));
-    m->have_forward = false;
-    return IWAE_OK;
-}
-
-// Aggregate-posterior decomposition (Hoffman & Johnson 2016; Chen et al. 2018): the samples z = mu_n + sigma_n eps_{s,n} of every image
-// against the mixture of all N encoder posteriors, in sample tiles of AGG_TILE; DESIGN.md section 14
-int iwae_aggregate_posterior(iwae_handle m, const float* x, int32_t N, int32_t S, const float* eps, double* summary, double* unit_kl, double* unit_mi,
-                             float* q_mu, float* q_sigma, float* log_qz, float* log_qzd) {
-    if (!m || !x || !summary) return fail(IWAE_ERR_ARG, "aggregate_posterior: need x and summary");
-    if (N <= 0 || S <= 0) return fail(IWAE_ERR_ARG, "aggregate_posterior: N and S must be positive");
-    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "aggregate_posterior: only the 1-layer model (the 2-layer q(z2|x) is not Gaussian, its p(z1) not N(0,1))");
-    if (m->C != 0) return fail(IWAE_ERR_ARG, "aggregate_posterior: only the unconditional model (cond_dim = 0)");
-    if (N > 1 << 24 || (int64_t)N * S > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "aggregate_posterior: too large (N > 2^24 images or N * S > 2^27 samples)");
-    HIPCHK(hipSetDevice(m->cfg.device));
-    CHK(join_side(m));      // the parameters a deferred update may still be writing
-    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
-    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
-    hipStream_t st = m->stream;
-    iwae_model::AggWs& w = m->agg;
-    const int D = m->D[0], Dp = m->Dp[0], Dpad = round_up(D, AGG_DC);
-    const long SN = (long)S * N;
-    const int P = (N + AGG_RANGE - 1) / AGG_RANGE, Tmax = (int)std::min<long>(SN, AGG_TILE);
-    const float* xd = x;
-    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * m->X * 4)); xd = ptr<float>(w.x); }
-    // ---- encoder heads mu, sigma of the N images (src/iwae1.py:39-42), in the eval precision
-    const float* head;
-    int ldh;
-    CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
-    if (q_mu) HIPCHK(hipMemcpy2DAsync(q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
-    if (q_sigma) HIPCHK(hipMemcpy2DAsync(q_sigma, (size_t)D * 4, head + Dp, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
-    // ---- the draws [S][N][D]: the caller's, or what iwae_debug_eps(N, S, 0) returns at this step and offset
-    const float* ed = eps;
-    if (!eps) {
-        CHK(ensure(w.eps, (size_t)SN * D * 4, st));
-        EpsSrc e;
-        e.user = nullptr; e.B = N; e.seed = m->cfg.seed; e.row_offset = (uint64_t)m->batch_offset * (uint64_t)S; e.step = m->noise_step; e.stream = 0;
-        launch_eps_dump(e, N, S, D, ptr<float>(w.eps), st);
-        HIPCHK(hipGetLastError());
-        ed = ptr<float>(w.eps);
-    } else if (!is_device_ptr(eps, m->cfg.device)) {
-        CHK(copy_in(m, w.eps, eps, (size_t)SN * D * 4));
-        ed = ptr<float>(w.eps);
-    }
-    CHK(ensure(w.mu, (size_t)N * Dpad * 4, st));
-    CHK(ensure(w.inv, (size_t)N * Dpad * 4, st));
-    CHK(ensure(w.nls, (size_t)N * Dpad * 4, st));
-    CHK(ensure(w.invd, (size_t)N * Dpad * 8, st));
-    CHK(ensure(w.nls_sum, (size_t)N * 8, st));
-    CHK(ensure(w.zT, (size_t)Dpad * Tmax * 4, st));
-    CHK(ensure(w.shT, (size_t)Dpad * Tmax * 4, st));
-    CHK(ensure(w.dim_part, (size_t)P * Dpad * Tmax * 4, st));
-    CHK(ensure(w.jmax, (size_t)P * Tmax * 8, st));
-    CHK(ensure(w.jsum, (size_t)P * Tmax * 4, st));
-    CHK(ensure(w.lqz, (size_t)SN * 4, st));
-    CHK(ensure(w.lqzdT, (size_t)Dpad * SN * 4, st));
-    CHK(ensure(w.part, (size_t)(D + 1) * 5 * 8, st));
-    CHK(ensure(w.out, (size_t)(4 + 2 * D) * 8, st));
-    AggCompArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.head = head; ca.ldh = ldh; ca.soff = Dp; ca.N = N; ca.D = D; ca.Dpad = Dpad;
-    ca.mu = ptr<float>(w.mu); ca.inv = ptr<float>(w.inv); ca.nls = ptr<float>(w.nls);
-    ca.invd = ptr<double>(w.invd); ca.nls_sum = ptr<double>(w.nls_sum);
-    launch_agg_comp(ca, st);
-    HIPCHK(hipGetLastError());
-    for (long i0 = 0; i0 < SN; i0 += AGG_TILE) {
-        const int T = (int)std::min<long>(AGG_TILE, SN - i0);
-        AggSampleArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.head = head; sa.ldh = ldh; sa.soff = Dp; sa.N = N; sa.D = D; sa.Dpad = Dpad; sa.eps = ed;
-        sa.mu = ca.mu; sa.inv = ca.inv; sa.nls = ca.nls; sa.i0 = i0; sa.T = T; sa.zT = ptr<float>(w.zT); sa.shT = ptr<float>(w.shT);
-        launch_agg_sample(sa, st);
-        AggMainArgs ma;
-        memset(&ma, 0, sizeof(ma));
-        ma.mu = ca.mu; ma.inv = ca.inv; ma.nls = ca.nls; ma.invd = ca.invd; ma.nls_sum = ca.nls_sum; ma.N = N; ma.Dpad = Dpad;
-        ma.zT = sa.zT; ma.shT = sa.shT; ma.T = T;
-        ma.dim_part = ptr<float>(w.dim_part); ma.joint_max = ptr<double>(w.jmax); ma.joint_sum = ptr<float>(w.jsum);
-        launch_agg_main(ma, st);
-        AggMergeArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.dim_part = ma.dim_part; ga.joint_max = ma.joint_max; ga.joint_sum = ma.joint_sum; ga.shT = sa.shT; ga.P = P; ga.Dpad = Dpad; ga.T = T;
-        ga.log_n = log((double)N); ga.log_qz = ptr<float>(w.lqz); ga.log_qzdT = ptr<float>(w.lqzdT); ga.ldo = SN; ga.i0 = i0;
-        launch_agg_merge(ga, st);
-        HIPCHK(hipGetLastError());
-    }
-    AggReduceArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.head = head; ra.ldh = ldh; ra.soff = Dp; ra.N = N; ra.D = D; ra.eps = ed; ra.SN = SN;
-    ra.log_qz = ptr<float>(w.lqz); ra.log_qzdT = ptr<float>(w.lqzdT); ra.part = ptr<double>(w.part);
-    ra.summary = ptr<double>(w.out); ra.unit_kl = ra.summary + 4; ra.unit_mi = ra.unit_kl + D;
-    launch_agg_reduce(ra, st);
-    HIPCHK(hipGetLastError());
-    CHK(copy_out(m, summary, ra.summary, 4 * 8));
-    if (unit_kl) CHK(copy_out(m, unit_kl, ra.unit_kl, (size_t)D * 8));
-    if (unit_mi) CHK(copy_out(m, unit_mi, ra.unit_mi, (size_t)D * 8));
-    if (log_qz) CHK(copy_out(m, log_qz, w.lqz.p, (size_t)SN * 4));
-    if (log_qzd) {
-        float* dst = log_qzd;
-        const bool dev = is_device_ptr(log_qzd, m->cfg.device);
-        if (!dev) { CHK(ensure(w.lqzd, (size_t)SN * D * 4, st)); dst = ptr<float>(w.lqzd); }
-        launch_agg_untranspose(ptr<float>(w.lqzdT), SN, D, dst, st);
-        HIPCHK(hipGetLastError());
-        if (!dev) CHK(copy_out(m, log_qzd, dst, (size_t)SN * D * 4));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    if (!eps) m->noise_step += 1;
-    m->have_forward = false;
-    return IWAE_OK;
-}
-
-// Transitions per launch of ais_chain_kernel (option ais_t_chunk).  Measured at the timing workload (N = 1 000, C = 16, L = 10, reference
-// dims; profiles/ais_time.txt): one transition takes 4.37 ms there, a launch of 4 takes 17.5 ms -- well under the 50 ms a launch may hold a
-// shared machine -- and the 125 launches of a T = 500 run cost nothing measurable (2.187 s in the kernel of 2.188 s wall).
-#define AIS_T_CHUNK_DEFAULT 4
-
-// Annealed importance sampling with HMC chains (Neal 2001; Wu et al. 2017): DESIGN.md section 15
-int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o, const iwae_ais_outputs* out) {
-    if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "ais: need x, options and outputs");
-    if (o->struct_size != sizeof(iwae_ais_options)) return fail(IWAE_ERR_ARG, "ais: iwae_ais_options.struct_size must be sizeof(iwae_ais_options) = " + std::to_string(sizeof(iwae_ais_options)));
-    if (!out->log_px || !o->betas) return fail(IWAE_ERR_ARG, "ais: betas and log_px are required");
-    if (N <= 0 || o->C <= 0 || o->T <= 0 || o->L <= 0) return fail(IWAE_ERR_ARG, "ais: N, C, T and L must be positive");
-    if (!(o->step_size > 0.0f)) return fail(IWAE_ERR_ARG, "ais: step_size must be positive");
-    if (o->init != IWAE_AIS_INIT_ENCODER && o->init != IWAE_AIS_INIT_PRIOR) return fail(IWAE_ERR_ARG, "ais: init must be IWAE_AIS_INIT_ENCODER or IWAE_AIS_INIT_PRIOR");
-    const int given = (o->eps0 != nullptr) + (o->mom != nullptr) + (o->unif != nullptr);
-    if (given != 0 && given != 3) return fail(IWAE_ERR_ARG, "ais: eps0, mom and unif come all three or not at all");
-    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "ais: only the 1-layer model");
-    if (m->C != 0 || m->has_prior) return fail(IWAE_ERR_ARG, "ais: only the unconditional model (cond_dim = 0, no learned prior)");
-    if ((int64_t)N * o->C > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "ais: too large (N * C > 2^27 chains)");
-    const int D = m->D[0], H = m->H[0], X = m->X, Dp = round_up(D, 16), Hp = round_up(H, 16), Xp = round_up(X, 16), Dh = m->Dp[0];
-    if (Hp > 16 * AIS_NT || Dp > 16 * AIS_DT) return fail(IWAE_ERR_ARG, "ais: needs n_hidden <= " + std::to_string(16 * AIS_NT) + " and n_latent <= " + std::to_string(16 * AIS_DT));
-    HIPCHK(hipSetDevice(m->cfg.device));
-    const int T = o->T, C = o->C;
-    const long R = (long)N * C;
-    std::vector<float> betas(T + 1);
-    HIPCHK(hipMemcpy(betas.data(), o->betas, (size_t)(T + 1) * 4, hipMemcpyDefault));
-    for (float b : betas) if (!(b >= 0.0f && b <= 1.0f)) return fail(IWAE_ERR_ARG, "ais: every beta must lie in [0, 1]");
-    CHK(join_side(m));      // the parameters a deferred update may still be writing
-    if (m->side) HIPCHK(hipStreamSynchronize(m->side));
-    if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
-    hipStream_t st = m->stream;
-    iwae_model::AisWs& w = m->ais;
-    const bool user_noise = given == 3, prior = o->init == IWAE_AIS_INIT_PRIOR;
-    const float* xd = x;
-    if (!is_device_ptr(x, m->cfg.device)) { CHK(copy_in(m, w.x, x, (size_t)N * X * 4)); xd = ptr<float>(w.x); }
-    // ---- base density: the encoder heads in the eval precision, or N(0, I)
-    const float* head = nullptr;
-    int ldh = 0;
-    if (!prior) {
-        CHK(eval_enc_heads(m, xd, N, w.head, w.xP, &head, &ldh));
-        if (out->q_mu) HIPCHK(hipMemcpy2DAsync(out->q_mu, (size_t)D * 4, head, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
-        if (out->q_sigma) HIPCHK(hipMemcpy2DAsync(out->q_sigma, (size_t)D * 4, head + Dh, (size_t)ldh * 4, (size_t)D * 4, N, hipMemcpyDefault, st));
-    } else if (out->q_mu || out->q_sigma) {
-        CHK(ensure(w.head, (size_t)N * D * 4, st));
-        if (out->q_mu) { HIPCHK(hipMemsetAsync(w.head.p, 0, (size_t)N * D * 4, st)); CHK(copy_out(m, out->q_mu, w.head.p, (size_t)N * D * 4)); }
-        if (out->q_sigma) { HIPCHK(hipMemsetD32Async((hipDeviceptr_t)w.head.p, 0x3f800000, (size_t)N * D, st)); CHK(copy_out(m, out->q_sigma, w.head.p, (size_t)N * D * 4)); }
-    }
-    // ---- the decoder's weights in both orientations, padded to multiples of 16 (src/iwae1.py:72-75; Keras kernels [in][out])
-    const KerasLayer* d1 = &m->klayers[m->dec1[0].sub[0]];
-    const size_t nW1 = (size_t)Dp * Hp, nW2 = (size_t)Hp * Hp, nW3 = (size_t)Hp * Xp;
-    CHK(ensure(w.wpad, (2 * (nW1 + nW2 + nW3) + 2 * Hp + Xp) * 4, st));
-    float* wp = ptr<float>(w.wpad);
-    AisChainArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    {
-        float* W1 = wp; float* W1T = W1 + nW1; float* W2 = W1T + nW1; float* W2T = W2 + nW2; float* W3 = W2T + nW2; float* W3T = W3 + nW3;
-        float* b1 = W3T + nW3; float* b2 = b1 + Hp; float* b3 = b2 + Hp;
-        const AisPrepArgs jobs[6] = {{m->param + d1[0].offW, D, H, Dp, Hp, W1, W1T}, {m->param + d1[1].offW, H, H, Hp, Hp, W2, W2T},
-                                     {m->param + d1[2].offW, H, X, Hp, Xp, W3, W3T}, {m->param + d1[0].offb, 1, H, 1, Hp, b1, nullptr},
-                                     {m->param + d1[1].offb, 1, H, 1, Hp, b2, nullptr}, {m->param + d1[2].offb, 1, X, 1, Xp, b3, nullptr}};
-        for (const AisPrepArgs& j : jobs) launch_ais_pad(j, st);
-        HIPCHK(hipGetLastError());
-        ca.W1 = W1; ca.W1T = W1T; ca.W2 = W2; ca.W2T = W2T; ca.W3 = W3; ca.W3T = W3T; ca.b1 = b1; ca.b2 = b2; ca.b3 = b3;
-    }
-    // ---- chain state: e_0 = the caller's draws, (z0 - mu) / sigma, or what iwae_debug_eps(N, C, 0) returns at this step and offset
-    CHK(ensure(w.e, (size_t)R * D * 4, st));
-    CHK(ensure(w.logw, (size_t)R * 8, st));
-    CHK(ensure(w.h, (size_t)R * 4, st));
-    CHK(ensure(w.nacc, (size_t)R * 4, st));
-    CHK(ensure(w.lpx, (size_t)N * 8, st));
-    CHK(copy_in(m, w.betas, betas.data(), (size_t)(T + 1) * 4));
-    const float* z0d = o->z0;
-    if (o->z0 && !is_device_ptr(o->z0, m->cfg.device)) { CHK(copy_in(m, w.z0, o->z0, (size_t)R * D * 4)); z0d = ptr<float>(w.z0); }
-    if (!o->z0) {
-        if (user_noise) HIPCHK(hipMemcpyAsync(w.e.p, o->eps0, (size_t)R * D * 4, hipMemcpyDefault, st));
-        else {
-            EpsSrc e;
-            e.user = nullptr; e.B = N; e.seed = m->cfg.seed; e.row_offset = (uint64_t)m->batch_offset * (uint64_t)C; e.step = m->noise_step; e.stream = 0;
-            launch_eps_dump(e, N, C, D, ptr<float>(w.e), st);
-        }
-    }
-    AisInitArgs ia;
-    memset(&ia, 0, sizeof(ia));
-    ia.z0 = z0d; ia.head = head; ia.ldh = ldh; ia.soff = Dh; ia.N = N; ia.D = D; ia.R = R; ia.step = o->step_size;
-    ia.e = ptr<float>(w.e); ia.log_w = ptr<double>(w.logw); ia.h = ptr<float>(w.h); ia.nacc = ptr<int>(w.nacc);
-    launch_ais_init(ia, st);
-    HIPCHK(hipGetLastError());
-    const float *momd = o->mom, *unifd = o->unif;
-    if (user_noise && !is_device_ptr(o->mom, m->cfg.device)) { CHK(copy_in(m, w.mom, o->mom, (size_t)T * R * D * 4)); momd = ptr<float>(w.mom); }
-    if (user_noise && !is_device_ptr(o->unif, m->cfg.device)) { CHK(copy_in(m, w.unif, o->unif, (size_t)T * R * 4)); unifd = ptr<float>(w.unif); }
-    float* dHd = nullptr;
-    uint8_t* accd = nullptr;
-    if (out->dH) {
-        if (is_device_ptr(out->dH, m->cfg.device)) dHd = out->dH;
-        else { CHK(ensure(w.dH, (size_t)T * R * 4, st)); dHd = ptr<float>(w.dH); }
-    }
-    if (out->accepted || out->accept_rate) {
-        if (out->accepted && is_device_ptr(out->accepted, m->cfg.device)) accd = out->accepted;
-        else { CHK(ensure(w.acc, (size_t)T * R, st)); accd = ptr<uint8_t>(w.acc); }
-    }
-    ca.D = D; ca.H = H; ca.X = X; ca.Dp = Dp; ca.Hp = Hp; ca.Xp = Xp;
-    ca.x = xd; ca.head = head; ca.ldh = ldh; ca.soff = Dh; ca.N = N; ca.C = C; ca.R = R;
-    ca.betas = ptr<float>(w.betas); ca.L = o->L; ca.adapt = o->adapt != 0;
-    ca.mom = user_noise ? momd : nullptr; ca.unif = user_noise ? unifd : nullptr;
-    ca.seed = m->cfg.seed; ca.row_offset = (uint64_t)m->batch_offset * (uint64_t)C; ca.step0 = m->noise_step;
-    ca.e = ia.e; ca.log_w = ia.log_w; ca.h = ia.h; ca.nacc = ia.nacc; ca.dH = dHd; ca.accepted = accd;
-    const int chunk = m->opt.ais_t_chunk > 0 ? m->opt.ais_t_chunk : AIS_T_CHUNK_DEFAULT;
-    m->time_this = m->timing > 0;
-    for (int t0 = 0; t0 < T; t0 += chunk) {
-        ca.t0 = t0; ca.t1 = std::min(T, t0 + chunk);
-        ScopedTimer tm(m, T_AIS_CHAIN, st);
-        launch_ais_chain(ca, st);
-        HIPCHK(hipGetLastError());
-    }
-    m->time_this = false;
-    AisFinishArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.head = head; fa.ldh = ldh; fa.soff = Dh; fa.N = N; fa.C = C; fa.D = D; fa.R = R; fa.e = ia.e; fa.log_w = ia.log_w;
-    fa.log_px = ptr<double>(w.lpx);
-    if (out->ess) { CHK(ensure(w.ess, (size_t)N * 4, st)); fa.ess = ptr<float>(w.ess); }
-    if (out->z) {
-        if (is_device_ptr(out->z, m->cfg.device)) fa.z = out->z;
-        else { CHK(ensure(w.z, (size_t)R * D * 4, st)); fa.z = ptr<float>(w.z); }
-    }
-    launch_ais_finish(fa, st);
-    HIPCHK(hipGetLastError());
-    if (out->accept_rate) {
-        CHK(ensure(w.rate, (size_t)T * 4, st));
-        launch_ais_accept_rate(accd, T, R, ptr<float>(w.rate), st);
-        HIPCHK(hipGetLastError());
-        CHK(copy_out(m, out->accept_rate, w.rate.p, (size_t)T * 4));
-    }
-    CHK(copy_out(m, out->log_px, w.lpx.p, (size_t)N * 8));
-    if (out->log_w) CHK(copy_out(m, out->log_w, w.logw.p, (size_t)R * 8));
-    if (out->ess) CHK(copy_out(m, out->ess, w.ess.p, (size_t)N * 4));
-    if (out->step_out) CHK(copy_out(m, out->step_out, w.h.p, (size_t)R * 4));
-    if (out->z && fa.z != out->z) CHK(copy_out(m, out->z, fa.z, (size_t)R * D * 4));
-    if (out->dH && dHd != out->dH) CHK(copy_out(m, out->dH, dHd, (size_t)T * R * 4));
-    if (out->accepted && accd != out->accepted) CHK(copy_out(m, out->accepted, accd, (size_t)T * R));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!user_noise) m->noise_step += (uint32_t)T + 1u;
-    m->have_forward = false;
-    return IWAE_OK;
-}
-
 // M draws of the training gradient (Rainforth et al. 2018): draw j is what iwae_forward_backward leaves after iwae_set_step(s0 + j, offset),
 // folded into a per-parameter mean and M2 by moments_fold_kernel after each draw, in stream order; one host sync at the end
 int iwae_grad_moments(iwae_handle m, const float* x, int32_t B, int32_t k, float beta, int32_t objective, int32_t M, double* mean, double* var) {
@@ -3656,15 +2762,11 @@ int iwae_grad_moments(iwae_handle m, const float* x, int32_t B, int32_t k, float
     CHK(check_objective(m, objective));
     HIPCHK(hipSetDevice(m->cfg.device));
     const bool f32 = m->cfg.precision == IWAE_PREC_FP32;
-    const int dev = m->cfg.device;
     const size_t n = m->nparam;
     hipStream_t st = m->stream;
     iwae_model::MomWs& w = m->mom_ws;
-    const float* xd = x;
-    if (!is_device_ptr(x, dev)) {        // uploaded once: every draw reads the images in place
-        CHK(copy_in(m, w.x, x, (size_t)B * m->X * 4));
-        xd = ptr<float>(w.x);
-    }
+    const float* xd;
+    CHK(staged_in(m, x, m->ev.x, (size_t)B * m->X * 4, &xd));        // uploaded once: every draw reads the images in place
     CHK(ensure(w.mean, n * 8, st));
     CHK(ensure(w.m2, n * 8, st));
     for (int j = 0; j < M; ++j) {
@@ -3682,15 +2784,16 @@ int iwae_grad_moments(iwae_handle m, const float* x, int32_t B, int32_t k, float
         launch_moments_fold(a, st);
     }
     // var replaces M2 in the workspace unless the caller's buffer is on the device; the mean is copied only to a device buffer
-    const bool mean_dev = is_device_ptr(mean, dev), var_dev = is_device_ptr(var, dev);
     MomentsFinalizeArgs f;
     f.mean = ptr<double>(w.mean); f.m2 = ptr<double>(w.m2); f.n = n; f.M = M;
-    f.out_mean = mean_dev ? mean : nullptr;
-    f.out_var = var_dev ? var : ptr<double>(w.m2);
+    double* mean_d;
+    CHK(staged_out(m, mean, w.mean, n * 8, &mean_d));
+    CHK(staged_out(m, var, w.m2, n * 8, &f.out_var));
+    f.out_mean = mean_d != f.mean ? mean_d : nullptr;
     launch_moments_finalize(f, st);
     HIPCHK(hipGetLastError());
-    if (!mean_dev) CHK(copy_out(m, mean, w.mean.p, n * 8));
-    if (!var_dev) CHK(copy_out(m, var, w.m2.p, n * 8));
+    CHK(finish_out(m, mean, mean_d, n * 8));
+    CHK(finish_out(m, var, f.out_var, n * 8));
     HIPCHK(hipStreamSynchronize(st));
     return IWAE_OK;
 }
