@@ -359,6 +359,63 @@ typedef struct {
 int iwae_ais(iwae_handle h, const float* x, int32_t N,                     /* [N, x_dim], host or device, any values in [0,1] */
              const iwae_ais_options* opt, const iwae_ais_outputs* out);
 
+/* Per-image optimisation of the variational posterior and what the inference-gap split needs from it (Cremer, Li & Duvenaud 2018,
+ * "Inference Suboptimality in Variational Autoencoders"; Kim et al. 2018, semi-amortised VAEs -- the reference's README lists
+ * harvardnlp/sa-vae; no reference counterpart).  Image n gets its own factorised Gaussian q_n = N(mu_n, sigma_n^2), sigma = exp(rho),
+ * started at the caller's mu0 / sigma0 or at the encoder heads (src/iwae1.py:39-42, in the eval precision) and moved by T Adam
+ * iterations that ASCEND a bound of S draws; E evaluation passes of S fresh draws each then score the result.  With e_s ~ N(0, I),
+ * z_s = mu + sigma e_s and c = log(2 pi)/2,
+ *   lj_s    = log p(x|z_s) + sum_d (-z_sd^2/2 - c)   (src/iwae1.py:105-111)      lq_s = sum_d (-e_sd^2/2 - rho_d - c)
+ *   log_w_s = lj_s - lq_s                                                        g_s  = grad_z log p(x|z_s) - z_s
+ *   wt_s    = 1/S (IWAE_LOCAL_ELBO)  or  softmax_s(log_w) (IWAE_LOCAL_IWAE)
+ *   d/dmu_d = sum_s wt_s g_sd                     d/drho_d = sum_s wt_s g_sd (sigma_d e_sd) + 1
+ * -- the reparameterised path derivative with the entropy term (sum_d rho_d) taken analytically; for IWAE_LOCAL_IWAE the gradient of
+ * LSE_s log_w - log S (the + 1 is sum_s wt_s d(-lq_s)/drho).  bound[t] = mean_s log_w (ELBO) or LSE_s log_w - log S (IWAE) on the draws
+ * of iteration t, before its update.  Adam in Keras form (epsilon outside the bias correction), per image, both moments zero at the
+ * start: m = beta_1 m + (1 - beta_1) d, v = beta_2 v + (1 - beta_2) d^2, theta += lr sqrt(1 - beta_2^t) / (1 - beta_1^t) m / (sqrt(v) + epsilon),
+ * t = 1..T.  After the last iteration: elbo[n] = mean over the E S evaluation draws of log_w, iwae[n] = LSE over them - log(E S), both
+ * accumulated in double from float32 log_w in pass order, then sample order.
+ * Arithmetic: the row products are float32 (v_mfma_f32_16x16x4_f32) as in iwae_ais, whatever iwae_set_eval_precision says (only the
+ * encoder start follows it); an image's sums over s run in sample order in float32.
+ * Noise: with eps == NULL iteration t (0-based) uses exactly what iwae_debug_eps(N, S, 0) returns at step s0 + t, s0 the handle's noise
+ * step (latent stream 0, row (batch_offset + n) S + s), evaluation pass j the draws of step s0 + T + j, and the call advances the step by
+ * T + E; so T = 0, E = 1 from the encoder start gives iwae[n] = iwae_eval_llh's per-image value at k = S on the same step.  With the
+ * caller's eps [T + E, S, N, D] (the first T blocks: the iterations; the last E: the evaluation) the step is left alone.
+ * Determinism: an image's outputs depend only on the weights, the image, its start, its draws and the options -- not on N, its position,
+ * the other images or the launch chunking (option local_t_chunk: passes per launch) -- and repeat bitwise.
+ * Models: the 1-layer unconditional model with n_hidden <= 208 and n_latent <= 128 (the chain kernel's limits); a 2-layer handle,
+ * cond_dim > 0 or cond_prior: IWAE_ERR_ARG.  N <= 0, S outside 1..64, T < 0, E < 1, lr < 0, a beta outside [0, 1), epsilon <= 0, an
+ * objective other than the two, exactly one of mu0 / sigma0, a wrong struct_size, x / opt / out / elbo NULL, N S > 2^27 or T or E > 2^24: IWAE_ERR_ARG
+ * before any launch, the noise step unchanged.  sigma0 > 0 is the caller's precondition (rho = log sigma0 is not checked).
+ * Workspace: 24 N D + 24 N bytes of state, two padded copies of the decoder's weights (as iwae_ais), per output asked for its own size and,
+ * with the caller's eps on the host, its copy (4 (T + E) S N D bytes).
+ * x, mu0, sigma0, eps: host or device.  Outputs: each host or device, NULL = not wanted. */
+typedef enum { IWAE_LOCAL_ELBO = 0, IWAE_LOCAL_IWAE = 1 } iwae_local_objective;
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(iwae_local_options) (64); ABI guard like iwae_ais_options' */
+    int32_t S;                 /* draws per image per pass, 1..64 */
+    int32_t T;                 /* Adam iterations, >= 0 */
+    int32_t E;                 /* evaluation passes after the last iteration, >= 1, S fresh draws each */
+    int32_t objective;         /* iwae_local_objective: what the iterations ascend */
+    float lr, beta_1, beta_2, epsilon;   /* Adam (the shims default to 0.9, 0.999, 1e-4 as the project trains, main.py:93) */
+    const float* mu0;          /* [N,D] start; both or none; NULL = the encoder heads in the eval precision */
+    const float* sigma0;       /* [N,D] > 0 */
+    const float* eps;          /* [T+E,S,N,D] the caller's N(0,1) draws, or NULL */
+} iwae_local_options;
+typedef struct {
+    double* elbo;              /* [N]      required: mean over the E S evaluation draws of log_w */
+    double* iwae;              /* [N]      LSE over the E S draws - log(E S) */
+    float* mu;                 /* [N,D]    optimised */
+    float* sigma;              /* [N,D]    optimised */
+    float* q_mu;               /* [N,D]    where it started */
+    float* q_sigma;            /* [N,D]    where it started */
+    float* bound;              /* [T,N]    the S-draw objective of each iteration, before its update; T = 0: not written */
+    float* grad;               /* [N,2D]   the last iteration's ascent direction (d/dmu | d/drho); T = 0: not written */
+    float* log_w;              /* [E S,N]  evaluation log-weights, pass-major (the caller's standard errors) */
+} iwae_local_outputs;
+int iwae_local_posterior(iwae_handle h, const float* x, int32_t N,        /* [N, x_dim], host or device, any values in [0,1] */
+                         const iwae_local_options* opt, const iwae_local_outputs* out);
+
 /* Data pipeline on the device (main.py:59-65,117-120 + src/utils.py:26-27): the grey-level training set
  * stays resident in HBM as uint8 [n, x_dim]; every epoch gets a visiting order (tf.data shuffle) and a
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),
@@ -383,7 +440,7 @@ int iwae_train_step_dataset(iwae_handle h, int32_t start, int32_t B, int32_t k, 
  * step (an event record costs a few us of stream bubble, so bench.py samples rather than timing every launch); 0 switches
  * it off.  name: "decoder_fwd" (whole decoder forward + log-likelihood), "out_bwd" (output-layer backward), "decoder_bwd" (the decoder's whole dX chain where it is one launch), "wgrad_out",
  * "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent" (the decoder's other backward kernels), "latent_bwd",
- * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on).  A kernel a configuration does not launch reports 0 launches. */
+ * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel).  A kernel a configuration does not launch reports 0 launches. */
 int iwae_enable_timing(iwae_handle h, int32_t enable);
 int iwae_kernel_time(iwae_handle h, const char* name, double* avg_us, int64_t* launches);
 

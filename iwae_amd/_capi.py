@@ -53,6 +53,24 @@ class AisOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in AIS_OUTPUT_FIELDS]
 
 
+class LocalOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("S", C.c_int32), ("T", C.c_int32), ("E", C.c_int32), ("objective", C.c_int32),
+                ("lr", C.c_float), ("beta_1", C.c_float), ("beta_2", C.c_float), ("epsilon", C.c_float),
+                ("mu0", C.c_void_p), ("sigma0", C.c_void_p), ("eps", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(LocalOptions)   # the ABI guard iwae_local_posterior checks
+
+
+LOCAL_OUTPUT_FIELDS = ("elbo", "iwae", "mu", "sigma", "q_mu", "q_sigma", "bound", "grad", "log_w")
+LOCAL_OBJECTIVES = {"elbo": 0, "iwae": 1}
+
+
+class LocalOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LOCAL_OUTPUT_FIELDS]
+
+
 # every symbol include/iwae_amd.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -93,6 +111,7 @@ SYMBOLS = {
     "iwae_latent_activity": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "iwae_aggregate_posterior": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P, _P]),
     "iwae_ais": (C.c_int, [_P, _P, C.c_int32, C.POINTER(AisOptions), C.POINTER(AisOutputs)]),
+    "iwae_local_posterior": (C.c_int, [_P, _P, C.c_int32, C.POINTER(LocalOptions), C.POINTER(LocalOutputs)]),
     "iwae_grad_moments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "iwae_dataset_upload": (C.c_int, [_P, _P, C.c_int32]),
     "iwae_dataset_begin_epoch": (C.c_int, [_P, C.c_uint32, _P, C.c_int32]),
@@ -109,7 +128,7 @@ SYMBOLS = {
 
 _lib = None
 
-_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "model.h", "model.hip", "moments_kernels.hip",
+_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "fp32_kernels.hip", "grid_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "local_kernels.hip", "model.h", "model.hip", "moments_kernels.hip",
                os.path.join("..", "..", "include", "iwae_amd.h"))
 
 

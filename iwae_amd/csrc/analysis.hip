@@ -1,8 +1,9 @@
-// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior and iwae_ais: the analyses that start from the encoder heads of N images
-// (host code; kernels in the four *_kernels.hip).  Each reads in five parts: argument checks, eval_begin, its own buffers and launches, its own copy-outs, eval_end.
+// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior, iwae_ais and iwae_local_posterior: the analyses that start from the
+// encoder heads of N images (host code; kernels in the five *_kernels.hip).  Each reads in five parts: argument checks, eval_begin, its own buffers and launches, its own copy-outs, eval_end.
 #include <math.h>
 #include <string.h>
 #include <algorithm>
+#include <new>
 #include "model.h"       // (the HIP runtime, include/iwae_amd.h and kernels.h come with it)
 #include "layout.h"
 
@@ -77,6 +78,31 @@ int dump_eps(iwae_model* m, int N, int S, int D, DevBuf& ws) {
 // dims; profiles/ais_time.txt): one transition takes 4.37 ms there, a launch of 4 takes 17.5 ms -- well under the 50 ms a launch may hold a
 // shared machine -- and the 125 launches of a T = 500 run cost nothing measurable (2.187 s in the kernel of 2.188 s wall).
 #define AIS_T_CHUNK_DEFAULT 4
+
+// Passes per launch of local_q_kernel (option local_t_chunk).  Measured at the timing workload (N = 1 000, S = 16, T = 500, E = 8, reference
+// dims; profiles/local_q_time.txt): one pass takes 0.404 ms there (one row evaluation of 16 000 rows; an AIS transition at L = 10 is eleven:
+// 4.38 ms), a full launch of 32 takes 32 x 0.404 = 12.9 ms (the file's 12.84 ms averages in the shorter last launch) -- well under the 50 ms a launch may hold a shared machine -- and launches of 8 change nothing
+// measurable (0.207 s in the kernel against 0.205 s), so nothing is gained by going lower and nothing by going higher.
+#define LOCAL_T_CHUNK_DEFAULT 32
+#define LOCAL_PASSES_MAX (1 << 24)      // T and E each: T + E and the step-size table stay far inside int and host memory
+
+// The decoder's weights in both orientations, padded to multiples of 16 (src/iwae1.py:72-75; Keras kernels [in][out]), into m->ais.wpad
+struct DecPad { const float *W1, *W1T, *W2, *W2T, *W3, *W3T, *b1, *b2, *b3; };
+int pad_decoder(iwae_model* m, hipStream_t st, int Dp, int Hp, int Xp, DecPad& p) {
+    const int D = m->D[0], H = m->H[0], X = m->X;
+    const KerasLayer* d1 = &m->klayers[m->dec1[0].sub[0]];
+    const size_t nW1 = (size_t)Dp * Hp, nW2 = (size_t)Hp * Hp, nW3 = (size_t)Hp * Xp;
+    CHK(ensure(m->ais.wpad, (2 * (nW1 + nW2 + nW3) + 2 * Hp + Xp) * 4, st));
+    float* W1 = ptr<float>(m->ais.wpad); float* W1T = W1 + nW1; float* W2 = W1T + nW1; float* W2T = W2 + nW2; float* W3 = W2T + nW2; float* W3T = W3 + nW3;
+    float* b1 = W3T + nW3; float* b2 = b1 + Hp; float* b3 = b2 + Hp;
+    const AisPrepArgs jobs[6] = {{m->param + d1[0].offW, D, H, Dp, Hp, W1, W1T}, {m->param + d1[1].offW, H, H, Hp, Hp, W2, W2T},
+                                 {m->param + d1[2].offW, H, X, Hp, Xp, W3, W3T}, {m->param + d1[0].offb, 1, H, 1, Hp, b1, nullptr},
+                                 {m->param + d1[1].offb, 1, H, 1, Hp, b2, nullptr}, {m->param + d1[2].offb, 1, X, 1, Xp, b3, nullptr}};
+    for (const AisPrepArgs& j : jobs) launch_ais_pad(j, st);
+    HIPCHK(hipGetLastError());
+    p = DecPad{W1, W1T, W2, W2T, W3, W3T, b1, b2, b3};
+    return IWAE_OK;
+}
 
 }  // namespace
 
@@ -431,22 +457,13 @@ int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o
         if (out->q_sigma) { HIPCHK(hipMemsetD32Async((hipDeviceptr_t)hb.p, 0x3f800000, (size_t)N * D, st)); CHK(copy_out(m, out->q_sigma, hb.p, (size_t)N * D * 4)); }
     }
     const float* head = c.head; const int ldh = c.ldh;
-    // ---- the decoder's weights in both orientations, padded to multiples of 16 (src/iwae1.py:72-75; Keras kernels [in][out])
-    const KerasLayer* d1 = &m->klayers[m->dec1[0].sub[0]];
-    const size_t nW1 = (size_t)Dp * Hp, nW2 = (size_t)Hp * Hp, nW3 = (size_t)Hp * Xp;
-    CHK(ensure(w.wpad, (2 * (nW1 + nW2 + nW3) + 2 * Hp + Xp) * 4, st));
-    float* wp = ptr<float>(w.wpad);
+    // ---- the decoder's weights in both orientations, padded to multiples of 16
     AisChainArgs ca;
     memset(&ca, 0, sizeof(ca));
     {
-        float* W1 = wp; float* W1T = W1 + nW1; float* W2 = W1T + nW1; float* W2T = W2 + nW2; float* W3 = W2T + nW2; float* W3T = W3 + nW3;
-        float* b1 = W3T + nW3; float* b2 = b1 + Hp; float* b3 = b2 + Hp;
-        const AisPrepArgs jobs[6] = {{m->param + d1[0].offW, D, H, Dp, Hp, W1, W1T}, {m->param + d1[1].offW, H, H, Hp, Hp, W2, W2T},
-                                     {m->param + d1[2].offW, H, X, Hp, Xp, W3, W3T}, {m->param + d1[0].offb, 1, H, 1, Hp, b1, nullptr},
-                                     {m->param + d1[1].offb, 1, H, 1, Hp, b2, nullptr}, {m->param + d1[2].offb, 1, X, 1, Xp, b3, nullptr}};
-        for (const AisPrepArgs& j : jobs) launch_ais_pad(j, st);
-        HIPCHK(hipGetLastError());
-        ca.W1 = W1; ca.W1T = W1T; ca.W2 = W2; ca.W2T = W2T; ca.W3 = W3; ca.W3T = W3T; ca.b1 = b1; ca.b2 = b2; ca.b3 = b3;
+        DecPad p;
+        CHK(pad_decoder(m, st, Dp, Hp, Xp, p));
+        ca.W1 = p.W1; ca.W1T = p.W1T; ca.W2 = p.W2; ca.W2T = p.W2T; ca.W3 = p.W3; ca.W3T = p.W3T; ca.b1 = p.b1; ca.b2 = p.b2; ca.b3 = p.b3;
     }
     // ---- chain state: e_0 = the caller's draws, (z0 - mu) / sigma, or what iwae_debug_eps(N, C, 0) returns at this step and offset
     CHK(ensure(w.e, (size_t)R * D * 4, st));
@@ -511,6 +528,102 @@ int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o
     CHK(finish_out(m, out->accepted, accd, (size_t)T * R));
     CHK(eval_end(c));
     if (!user_noise) m->noise_step += (uint32_t)T + 1u;
+    return IWAE_OK;
+}
+
+// Per-image optimisation of a factorised Gaussian q and its evaluation (Cremer, Li & Duvenaud 2018): DESIGN.md section 16
+int iwae_local_posterior(iwae_handle m, const float* x, int32_t N, const iwae_local_options* o, const iwae_local_outputs* out) {
+    if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "local_posterior: need x, options and outputs");
+    if (o->struct_size != sizeof(iwae_local_options)) return fail(IWAE_ERR_ARG, "local_posterior: iwae_local_options.struct_size must be sizeof(iwae_local_options) = " + std::to_string(sizeof(iwae_local_options)));
+    if (!out->elbo) return fail(IWAE_ERR_ARG, "local_posterior: elbo is required");
+    if (N <= 0 || o->S < 1 || o->S > LOCAL_S_MAX || o->T < 0 || o->E < 1) return fail(IWAE_ERR_ARG, "local_posterior: needs N > 0, 1 <= S <= " + std::to_string(LOCAL_S_MAX) + ", T >= 0 and E >= 1");
+    if (o->T > LOCAL_PASSES_MAX || o->E > LOCAL_PASSES_MAX) return fail(IWAE_ERR_ARG, "local_posterior: too many passes (T or E > 2^24)");
+    if (o->objective != IWAE_LOCAL_ELBO && o->objective != IWAE_LOCAL_IWAE) return fail(IWAE_ERR_ARG, "local_posterior: objective must be IWAE_LOCAL_ELBO or IWAE_LOCAL_IWAE");
+    if (!(o->lr >= 0.0f) || !(o->beta_1 >= 0.0f && o->beta_1 < 1.0f) || !(o->beta_2 >= 0.0f && o->beta_2 < 1.0f) || !(o->epsilon > 0.0f))
+        return fail(IWAE_ERR_ARG, "local_posterior: needs lr >= 0, beta_1 and beta_2 in [0, 1) and epsilon > 0");
+    if ((o->mu0 != nullptr) != (o->sigma0 != nullptr)) return fail(IWAE_ERR_ARG, "local_posterior: mu0 and sigma0 come both or not at all");
+    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "local_posterior: only the 1-layer model");
+    if (m->C != 0 || m->has_prior) return fail(IWAE_ERR_ARG, "local_posterior: only the unconditional model (cond_dim = 0, no learned prior)");
+    if ((int64_t)N * o->S > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "local_posterior: too large (N * S > 2^27 rows)");
+    const int D = m->D[0], H = m->H[0], X = m->X, Dp = round_up(D, 16), Hp = round_up(H, 16), Xp = round_up(X, 16), Dh = m->Dp[0];
+    if (Hp > 16 * AIS_NT || Dp > 16 * AIS_DT) return fail(IWAE_ERR_ARG, "local_posterior: needs n_hidden <= " + std::to_string(16 * AIS_NT) + " and n_latent <= " + std::to_string(16 * AIS_DT));
+    const int S = o->S, T = o->T, E = o->E;
+    std::vector<float> alpha;
+    try { alpha.resize(T); } catch (const std::bad_alloc&) { return fail(IWAE_ERR_NOMEM, "local_posterior: no host memory for the step sizes of " + std::to_string(T) + " iterations"); }
+    EvalCall c;
+    CHK(eval_begin(m, x, N, c));
+    hipStream_t st = c.st;
+    iwae_model::LocalWs& w = m->loc;
+    // ---- the start: the caller's, or the encoder heads in the eval precision
+    const float *mu0d = nullptr, *sg0d = nullptr;
+    if (o->mu0) {
+        CHK(staged_in(m, o->mu0, w.mu0, (size_t)N * D * 4, &mu0d));
+        CHK(staged_in(m, o->sigma0, w.sg0, (size_t)N * D * 4, &sg0d));
+    } else {
+        CHK(eval_heads(c, N));
+    }
+    LocalArgs la;
+    memset(&la, 0, sizeof(la));
+    {
+        DecPad p;
+        CHK(pad_decoder(m, st, Dp, Hp, Xp, p));
+        la.W1 = p.W1; la.W1T = p.W1T; la.W2 = p.W2; la.W2T = p.W2T; la.W3 = p.W3; la.W3T = p.W3T; la.b1 = p.b1; la.b2 = p.b2; la.b3 = p.b3;
+    }
+    // ---- per-image state, Adam's step sizes (the bias correction in double, rounded once)
+    CHK(ensure(w.st, (size_t)N * 6 * D * 4, st));
+    CHK(ensure(w.acc, (size_t)N * 3 * 8, st));
+    CHK(ensure(w.qmu, (size_t)N * D * 4, st));
+    CHK(ensure(w.qsg, (size_t)N * D * 4, st));
+    CHK(ensure(w.mu, (size_t)N * D * 4, st));
+    CHK(ensure(w.sg, (size_t)N * D * 4, st));
+    CHK(ensure(w.elbo, (size_t)N * 8, st));
+    CHK(ensure(w.iwae, (size_t)N * 8, st));
+    for (int t = 1; t <= T; ++t) alpha[t - 1] = (float)((double)o->lr * sqrt(1.0 - pow((double)o->beta_2, t)) / (1.0 - pow((double)o->beta_1, t)));
+    if (T > 0) CHK(copy_in(m, w.alpha, alpha.data(), (size_t)T * 4));      // (alpha lives until eval_end has synchronised)
+    const float* epsd = nullptr;
+    if (o->eps) CHK(staged_in(m, o->eps, w.eps, (size_t)(T + E) * S * N * D * 4, &epsd));
+    LocalInitArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.head = c.head; ia.ldh = c.ldh; ia.soff = Dh; ia.mu0 = mu0d; ia.sigma0 = sg0d; ia.N = N; ia.D = D;
+    ia.st = ptr<float>(w.st); ia.acc = ptr<double>(w.acc); ia.q_mu = ptr<float>(w.qmu); ia.q_sigma = ptr<float>(w.qsg);
+    launch_local_init(ia, st);
+    HIPCHK(hipGetLastError());
+    float *boundd = nullptr, *gradd = nullptr, *logwd = nullptr;
+    if (out->bound && T > 0) CHK(staged_out(m, out->bound, w.bound, (size_t)T * N * 4, &boundd));
+    if (out->grad && T > 0) CHK(staged_out(m, out->grad, w.grad, (size_t)N * 2 * D * 4, &gradd));
+    if (out->log_w) CHK(staged_out(m, out->log_w, w.logw, (size_t)E * S * N * 4, &logwd));
+    la.D = D; la.H = H; la.X = X; la.Dp = Dp; la.Hp = Hp; la.Xp = Xp;
+    la.x = c.xd; la.N = N; la.S = S; la.ipw = 64 / S; la.T = T; la.objective = o->objective;
+    la.alpha = ptr<float>(w.alpha); la.beta1 = o->beta_1; la.beta2 = o->beta_2; la.epsilon = o->epsilon;
+    la.inv_S = 1.0f / (float)S; la.log_S = logf((float)S);
+    la.eps = epsd; la.seed = m->cfg.seed; la.row_offset = (uint64_t)m->batch_offset * (uint64_t)S; la.step0 = m->noise_step;
+    la.st = ia.st; la.acc = ia.acc; la.bound = boundd; la.grad = gradd; la.log_w = logwd;
+    const int chunk = m->opt.local_t_chunk > 0 ? m->opt.local_t_chunk : LOCAL_T_CHUNK_DEFAULT;
+    m->time_this = m->timing > 0;
+    for (int t0 = 0; t0 < T + E; t0 += chunk) {
+        la.t0 = t0; la.t1 = std::min(T + E, t0 + chunk);
+        ScopedTimer tm(m, T_LOCAL_Q, st);
+        launch_local_q(la, st);
+        HIPCHK(hipGetLastError());
+    }
+    m->time_this = false;
+    LocalFinishArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.st = ia.st; fa.acc = ia.acc; fa.N = N; fa.D = D; fa.ES = E * S;
+    fa.mu = ptr<float>(w.mu); fa.sigma = ptr<float>(w.sg); fa.elbo = ptr<double>(w.elbo); fa.iwae = ptr<double>(w.iwae);
+    launch_local_finish(fa, st);
+    HIPCHK(hipGetLastError());
+    CHK(copy_out(m, out->elbo, w.elbo.p, (size_t)N * 8));
+    if (out->iwae) CHK(copy_out(m, out->iwae, w.iwae.p, (size_t)N * 8));
+    if (out->mu) CHK(copy_out(m, out->mu, w.mu.p, (size_t)N * D * 4));
+    if (out->sigma) CHK(copy_out(m, out->sigma, w.sg.p, (size_t)N * D * 4));
+    if (out->q_mu) CHK(copy_out(m, out->q_mu, w.qmu.p, (size_t)N * D * 4));
+    if (out->q_sigma) CHK(copy_out(m, out->q_sigma, w.qsg.p, (size_t)N * D * 4));
+    if (boundd) CHK(finish_out(m, out->bound, boundd, (size_t)T * N * 4));      // (T = 0: neither was staged, neither is written)
+    if (gradd) CHK(finish_out(m, out->grad, gradd, (size_t)N * 2 * D * 4));
+    if (logwd) CHK(finish_out(m, out->log_w, logwd, (size_t)E * S * N * 4));
+    CHK(eval_end(c));
+    if (!o->eps) m->noise_step += (uint32_t)(T + E);
     return IWAE_OK;
 }
 

@@ -571,4 +571,41 @@ void launch_ais_chain(const AisChainArgs& a, hipStream_t st);
 void launch_ais_finish(const AisFinishArgs& a, hipStream_t st);
 void launch_ais_accept_rate(const uint8_t* accepted, int T, long R, float* rate, hipStream_t st);
 
+// ---- per-image posterior optimisation (local_kernels.hip; iwae_local_posterior): S draws per image and pass, float32, ais_chain_kernel's
+// blocking and row evaluation.  A workgroup (4 waves x 16 rows) owns ipw = 64 / S whole images, rows image-major (local row i S + s), the rest
+// dead; between passes an image's state st [N][6][D] = mu | rho = log sigma | Adam's m, v of mu | m, v of rho lives in HBM / L2.  Pass t < T
+// is an Adam iteration on the draws of step0 + t; pass T + j evaluation pass j (no update): log_w summed into acc [N][3] (double).
+#define LOCAL_S_MAX 64
+struct LocalInitArgs {                // local_init_kernel: the start (the caller's, else the encoder heads), m = v = 0, acc = (0, -inf, 0)
+    const float* head; int ldh, soff; // encoder heads per image (used where mu0 is null)
+    const float *mu0, *sigma0;        // [N][D] or null
+    int N, D;
+    float* st; double* acc;
+    float *q_mu, *q_sigma;            // [N][D]: where it started
+};
+struct LocalArgs {
+    const float *W1, *W1T, *W2, *W2T, *W3, *W3T, *b1, *b2, *b3;      // padded to multiples of 16 (ais_pad_kernel): W [in][out], WT [out][in]
+    int D, H, X, Dp, Hp, Xp;
+    const float* x;                   // [N][X]
+    int N, S, ipw;
+    int t0, t1, T, objective;         // passes [t0, t1) of this launch; T iterations in all; iwae_local_objective
+    const float* alpha;               // [T] on the device: lr sqrt(1 - beta_2^t) / (1 - beta_1^t), t = pass + 1
+    float beta1, beta2, epsilon, inv_S, log_S;
+    const float* eps;                 // the caller's draws [T + E][S][N][D] or null: Philox stream 0 at step0 + pass, row row_offset + n S + s
+    uint64_t seed, row_offset; uint32_t step0;
+    float* st; double* acc;
+    float* bound;                     // [T][N] or null
+    float* grad;                      // [N][2 D] or null: the ascent direction of iteration T - 1
+    float* log_w;                     // [E S][N] or null
+};
+struct LocalFinishArgs {              // local_finish_kernel: mu, sigma = exp(rho); elbo = sum / (E S), iwae = max + log(sum exp) - log(E S)
+    const float* st; const double* acc;
+    int N, D, ES;
+    float *mu, *sigma; double *elbo, *iwae;
+};
+size_t local_q_lds_bytes(int Dp, int Hp);
+void launch_local_init(const LocalInitArgs& a, hipStream_t st);
+void launch_local_q(const LocalArgs& a, hipStream_t st);
+void launch_local_finish(const LocalFinishArgs& a, hipStream_t st);
+
 }  // namespace iwae

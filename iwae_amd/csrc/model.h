@@ -53,7 +53,7 @@ template <class Ws> void free_all(Ws& ws) {
 }
 
 // kernels iwae_enable_timing brackets with HIP events (on the stream each is launched on); names: iwae_kernel_time
-enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_COUNT };
+enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_COUNT };
 
 // What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
 // images and samples in chunks and needs log_w only.
@@ -142,6 +142,7 @@ struct StepOptions {
     int eval_rows = 0;                        // data rows per evaluator launch (option eval_rows): images x samples, k chunked beyond it; 0 = eval_rows_auto()
     int grid_chunk = 0;                       // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT)
     int ais_t_chunk = 0;                      // iwae_ais: transitions per launch of ais_chain_kernel (option ais_t_chunk; 0 = AIS_T_CHUNK_DEFAULT)
+    int local_t_chunk = 0;                    // iwae_local_posterior: passes per launch of local_q_kernel (option local_t_chunk; 0 = LOCAL_T_CHUNK_DEFAULT)
 };
 
 // The kernels and streams of one bf16 step.  plan_step decides all of it from shapes and options before forward_impl launches or allocates
@@ -234,6 +235,9 @@ struct iwae_model {
     // iwae_ais's buffers: the decoder's padded weights, the schedule, the chain state (e, log_w, h, accept counts), the
     // caller's noise and initial states when they arrive on the host, and the outputs
     struct AisWs { DevBuf wpad, betas, e, logw, h, nacc, z0, mom, unif, dH, acc, rate, z, lpx, ess; } ais;
+    // iwae_local_posterior's buffers (the padded weights are ais.wpad): the per-image state and double sums, Adam's step sizes, the
+    // caller's start and noise when they arrive on the host, and the outputs
+    struct LocalWs { DevBuf st, acc, alpha, mu0, sg0, eps, qmu, qsg, mu, sg, elbo, iwae, bound, grad, logw; } loc;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective

@@ -20,6 +20,8 @@ static_assert(sizeof(iwae_config) == 64 && offsetof(iwae_config, struct_size) ==
 static_assert(sizeof(iwae_scalars) == 64 && sizeof(iwae_tensors) == 12 * sizeof(void*), "ABI struct layout");
 static_assert(sizeof(iwae_ais_options) == 72 && offsetof(iwae_ais_options, betas) == 16 && offsetof(iwae_ais_options, step_size) == 24 && offsetof(iwae_ais_options, z0) == 40 &&
               offsetof(iwae_ais_options, unif) == 64 && sizeof(iwae_ais_outputs) == 10 * sizeof(void*), "iwae_ais_options / iwae_ais_outputs layout is part of the ABI (iwae_amd/_capi.py)");
+static_assert(sizeof(iwae_local_options) == 64 && offsetof(iwae_local_options, objective) == 16 && offsetof(iwae_local_options, lr) == 20 && offsetof(iwae_local_options, epsilon) == 32 &&
+              offsetof(iwae_local_options, mu0) == 40 && offsetof(iwae_local_options, eps) == 56 && sizeof(iwae_local_outputs) == 9 * sizeof(void*), "iwae_local_options / iwae_local_outputs layout is part of the ABI (iwae_amd/_capi.py)");
 
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -65,7 +67,8 @@ static int load_rccl() {
 static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgrad_out", "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent",
                                                  "latent_bwd", "encoder_fwd", "reduce_adam", "decoder_bwd",
                                                  "allreduce_enc", "allreduce_dec",       // (the data-parallel step's two ncclAllReduce calls, each on its own stream)
-                                                 "ais_chain"};                           // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
+                                                 "ais_chain",                            // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
+                                                 "local_q"};                             // (iwae_local_posterior: likewise local_q_kernel)
 
 namespace {
 
@@ -2215,6 +2218,7 @@ void iwae_destroy(iwae_handle m) {
     free_all(m->mom_ws);
     free_all(m->agg);
     free_all(m->ais);
+    free_all(m->loc);
     for (BlockWs* w : {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior}) free_all(*w);
     free_all(m->wdec1);
     free_all(m->f32);
@@ -2460,6 +2464,7 @@ int iwae_set_option(iwae_handle m, const char* name, int64_t value) {
     else if (n == "wg9") m->opt.wg_shape9 = iv;                           // bit mask: layers that take the 8 + 8-wave / 128-feature wgradws shape
     else if (n == "grid_chunk") m->opt.grid_chunk = iv > 0 ? std::max(16, iv) : 0;      // iwae_grid_posterior: grid points per chunk (0: the default)
     else if (n == "ais_t_chunk") m->opt.ais_t_chunk = iv > 0 ? iv : 0;                 // iwae_ais: transitions per launch (0: the default)
+    else if (n == "local_t_chunk") m->opt.local_t_chunk = iv > 0 ? iv : 0;             // iwae_local_posterior: passes per launch (0: the default)
     else if (n == "eval_rows") m->opt.eval_rows = iv > 0 ? std::max(64, iv) : 0;       // data rows per evaluator launch
     else if (n == "no_bern_pipe") m->opt.allow_bern_pipe = !on;           // the Bernoulli forward on dense_kernel<EPI_BERN>
     else if (n == "no_block_fused") m->opt.allow_block_fused = !on;       // a BasicBlock on few rows as three dense_kernel launches

@@ -108,3 +108,33 @@ class IWAE(BaseIWAE):
         upper = -(m + np.log(np.mean(np.exp(lw - m[None]), axis=0)))
         lower = fwd["log_px"]
         return {"x": x, "z": z, "lower": lower, "upper": upper, "gap": float(np.mean(upper - lower)), "forward": fwd, "reverse": rev}
+
+    # ---- per-image posterior optimisation and the inference-gap split (Cremer, Li & Duvenaud 2018)
+    def _local_scope(self):
+        if self._net.cond_dim:
+            raise NotImplementedError("per-image posterior optimisation covers the unconditional 1-layer model only")
+
+    def local_posterior(self, X, n_samples=16, n_iters=200, n_eval=8, **kwargs):
+        """The best factorised Gaussian q*(z|x) of every image of X found by n_iters Adam iterations on (mu, log sigma) from the encoder's
+        q(z|x) (iwae_local_posterior; kwargs: objective, lr, start, noise, trace, beta_1, beta_2, epsilon).  Returns the binding's dict."""
+        self._local_scope()
+        return self._net.local_posterior(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), n_samples=n_samples, n_iters=n_iters,
+                                         n_eval=n_eval, **kwargs)
+
+    def inference_gaps(self, X, n_samples=16, n_iters=200, n_eval=64, lr=0.05, ais=None):
+        """log p(x) - ELBO[q_enc] of every image of X split into the approximation gap log p(x) - ELBO[q*] (what no factorised Gaussian
+        can close) and the amortisation gap ELBO[q*] - ELBO[q_enc] (what the encoder loses against the best one).  log p(x): annealed
+        importance sampling (ais: the arguments of ais_log_likelihood); ELBO[q_enc]: n_eval passes of n_samples draws from the encoder's
+        q (no iterations); ELBO[q*]: the same after n_iters ELBO iterations.  Returns per-image float64 arrays log_px, elbo_amortized,
+        elbo_local, approximation_gap, amortization_gap, the standard errors elbo_amortized_se and elbo_local_se of the two means (from the
+        evaluation log-weights), log_px_se (delta method over the chains) and the three runs' dicts (ais, amortized, local)."""
+        self._local_scope()
+        X = np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim)
+        _, a = self.ais_log_likelihood(X, **(ais or {}))
+        amort = self._net.local_posterior(X, n_samples=n_samples, n_iters=0, n_eval=n_eval, objective="elbo")
+        local = self._net.local_posterior(X, n_samples=n_samples, n_iters=n_iters, n_eval=n_eval, objective="elbo", lr=lr)
+        out = utils.inference_gap_split(a["log_px"], amort["elbo"], local["elbo"])
+        out["elbo_amortized_se"], out["elbo_local_se"] = utils.mean_se(amort["log_w"]), utils.mean_se(local["log_w"])
+        out["log_px_se"] = utils.log_mean_exp_se(a["log_w"])
+        out.update(ais=a, amortized=amort, local=local)
+        return out

@@ -46,3 +46,10 @@ class IWAE(BaseIWAE):
 
     def bdmc(self, n, n_chains=16, n_temps=1000, seed=0, **kwargs):
         self.ais_log_likelihood(None)
+
+    def local_posterior(self, X, n_samples=16, n_iters=200, n_eval=8, **kwargs):
+        raise NotImplementedError("per-image posterior optimisation covers the 1-layer model only: the 2-layer q(z2|z1) q(z1|x) is not one "
+                                  "factorised Gaussian per image")
+
+    def inference_gaps(self, X, **kwargs):
+        self.local_posterior(None)

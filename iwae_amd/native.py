@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import AIS_INITS, OBJECTIVES, PRECISIONS, AisOptions, AisOutputs, Config, Scalars, Tensors, check
+from ._capi import AIS_INITS, LOCAL_OBJECTIVES, OBJECTIVES, PRECISIONS, AisOptions, AisOutputs, Config, LocalOptions, LocalOutputs, Scalars, Tensors, check
 
 _SCALAR_NAMES = ("vae_elbo", "vae_elbo_kl", "iwae_elbo", "iwae_eq14", "inference_loss",
                  "mean_lpxz", "mean_lpz", "mean_lqzx", "mean_kl")
@@ -412,6 +412,48 @@ class NativeModel:
         check(self.lib.iwae_ais(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
         res["step_size"] = res.pop("step_out")
         res["betas"] = b
+        return res
+
+    def local_posterior(self, x, n_samples=16, n_iters=200, n_eval=8, objective="elbo", lr=0.05, start=None, noise=None, trace=False,
+                        beta_1=0.9, beta_2=0.999, epsilon=1e-4):
+        """iwae_local_posterior: a factorised Gaussian q per image of x [N, x_dim], moved by n_iters Adam iterations that ascend the
+        n_samples-draw bound `objective` ("elbo" or "iwae") from start = (mu0, sigma0) [N, D] each (None: the encoder heads), then scored
+        on n_eval passes of n_samples fresh draws.  noise [n_iters + n_eval, n_samples, N, D] replaces the device generator (and leaves
+        the noise step alone).  Returns elbo, iwae [N] (float64), mu, sigma (optimised), q_mu, q_sigma (the start) [N, D], log_w
+        [n_eval n_samples, N]; with trace=True also bound [n_iters, N] and grad [N, 2 D] (the last iteration's; absent at n_iters = 0)."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        N, D, S, T, E = x.shape[0], self.n_latent[0], int(n_samples), int(n_iters), int(n_eval)
+        if objective not in LOCAL_OBJECTIVES:
+            raise ValueError("local_posterior: objective must be 'elbo' or 'iwae', got %r" % (objective,))
+        o = LocalOptions()
+        o.S, o.T, o.E, o.objective = S, T, E, LOCAL_OBJECTIVES[objective]
+        o.lr, o.beta_1, o.beta_2, o.epsilon = float(lr), float(beta_1), float(beta_2), float(epsilon)
+        keep = []
+        if start is not None:
+            mu0, sg0 = (_f32(v) for v in start)
+            if mu0.shape != (N, D) or sg0.shape != (N, D):
+                raise ValueError("local_posterior: start must be (mu0, sigma0) of shape %s each, got %s, %s" % ((N, D), mu0.shape, sg0.shape))
+            o.mu0, o.sigma0 = mu0.ctypes.data, sg0.ctypes.data
+            keep += [mu0, sg0]
+        n0, s0, t0, e0 = max(N, 0), max(S, 0), max(T, 0), max(E, 0)      # (bad counts: the library rejects them; nothing is written)
+        if noise is not None:
+            e = _f32(noise)
+            if e.shape != (t0 + e0, s0, n0, D):
+                raise ValueError("local_posterior: noise must be [n_iters + n_eval, n_samples, N, %d] = %s, got %s" % (D, (t0 + e0, s0, n0, D), e.shape))
+            o.eps = e.ctypes.data
+            keep.append(e)
+        res = {"elbo": np.empty(n0, dtype=np.float64), "iwae": np.empty(n0, dtype=np.float64)}
+        for name in ("mu", "sigma", "q_mu", "q_sigma"):
+            res[name] = np.empty((n0, D), dtype=np.float32)
+        res["log_w"] = np.empty((e0 * s0, n0), dtype=np.float32)
+        if trace:
+            res["bound"] = np.empty((t0, n0), dtype=np.float32)
+            if t0 > 0:
+                res["grad"] = np.empty((n0, 2 * D), dtype=np.float32)
+        outs = LocalOutputs()
+        for name, arr in res.items():
+            setattr(outs, name, arr.ctypes.data)
+        check(self.lib.iwae_local_posterior(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
         return res
 
     def grad_moments(self, x, k, draws, beta=1.0, objective="iwae_elbo"):

@@ -152,3 +152,24 @@ def get_bias(Xtrain=None):
     if Xtrain.dtype == np.uint8:
         Xtrain = Xtrain / 255
     return bias_from_mean(np.mean(Xtrain, axis=0))
+
+
+def mean_se(log_w):
+    """Standard error of the mean over axis 0 (the E S evaluation draws of iwae_local_posterior's log_w [E S, N]) per image, float64."""
+    lw = np.asarray(log_w, dtype=np.float64)
+    return lw.std(axis=0, ddof=1) / np.sqrt(lw.shape[0]) if lw.shape[0] > 1 else np.full(lw.shape[1:], np.nan)
+
+
+def log_mean_exp_se(log_w):
+    """Delta-method standard error of log mean_c exp(log_w) over axis 0 per image: std(w) / (mean(w) sqrt(C))."""
+    lw = np.asarray(log_w, dtype=np.float64)
+    if lw.shape[0] < 2:
+        return np.full(lw.shape[1:], np.nan)
+    w = np.exp(lw - lw.max(axis=0)[None])
+    return w.std(axis=0, ddof=1) / (w.mean(axis=0) * np.sqrt(lw.shape[0]))
+
+
+def inference_gap_split(log_px, elbo_amortized, elbo_local):
+    """Cremer, Li & Duvenaud (2018): log p(x) - ELBO[q_enc] = (log p(x) - ELBO[q*]) + (ELBO[q*] - ELBO[q_enc]), per image in float64."""
+    lp, ea, el = (np.asarray(v, dtype=np.float64) for v in (log_px, elbo_amortized, elbo_local))
+    return {"log_px": lp, "elbo_amortized": ea, "elbo_local": el, "approximation_gap": lp - el, "amortization_gap": el - ea}
