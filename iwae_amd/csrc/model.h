@@ -190,6 +190,50 @@ struct StepPlan {
     OnStream tail = ON_SIDE;    // the side stream that finishes last (carries the decoder's reduction / exchange / update)
 };
 
+// How a training step ends: what becomes of the weight-gradient slabs once every layer's are written.
+enum StepEnd {
+    END_GRAD = 0,           // the flat gradient, every stream joined (iwae_forward_backward, iwae_grad_moments, the train step that hands out tensors)
+    END_GRAD_SPLIT,         // ... the decoder's segment left on the side stream, unjoined (iwae_forward_backward_split)
+    END_GRAD_SPLIT_HELD,    // ... and its slab reduction not launched either: dp_finish does, behind the wait that orders the step's two all-reduces
+    END_UPDATE              // Adam in the epilogue of the slab sums (the single-GPU iwae_train_step)
+};
+struct BlockRange { int first = 0, count = 0; };
+// Where each block of layers begins in the layer table (order enc1 | enc2 | dec2 | dec1 | prior): .r in the slab-reduce grid, .e in the
+// elementwise grid.  build_descs computes them; nothing else looks a boundary up.
+struct TableBounds {
+    struct At { int r = 0, e = 0; };
+    At enc1_end, enc2, dec2;      // (1-layer model: all three are where the image encoder ends)
+    At dec1, dec1_out, dec1_end;  // the decoder's first layer, its output layer, the first entry behind it
+    At end;                       // the whole table: the grids' sizes
+};
+// What a step left behind on the side streams: planned by plan_step_end, written once at the end of backward_impl / backward_f32, consumed by
+// join_side and dp_finish, reported by iwae_forward_backward_split.
+// Single-GPU train step: the decoder's slab reduction + Adam (90 % of the slab bytes) stays on the side stream and is
+// NOT joined at the end of the step -- nothing needs the decoder's new weights before the next step's d1 layer, so it
+// runs beside the next encoder forward.  join_side() waits for it, and every entry point that touches parameters, gradients or the decoder calls that.
+struct StepLeft {
+    bool dec = false;           // ev_dec (recorded behind the tail stream's reduction / update) has not been waited for yet
+    bool dec2 = false;          // ... ev_dec2 (the other side stream's own deferred update)
+    BlockRange held;            // count > 0: the decoder's slab reduction over these blocks is not launched yet: dp_finish does
+    size_t split_offset = 0;    // first float of the flat gradient that was left on the side stream (nparam: none)
+    OnStream on = ON_SIDE;      // the stream that carries it
+};
+// The end of one bf16 step, decided by plan_step_end from the plan, the options, the layer table and the caller's StepEnd; backward_impl
+// executes it.  A side stream sums (and, `update`, updates) the layers whose weight gradients it carried, in ONE launch of up to two ranges.
+// EARLY: gradient only, the decoder's sums on the tail stream, joined behind the main stream's | _SPLIT: not joined | _HELD: not even launched
+enum EndCase { ENDS_JOINED = 0, ENDS_DEC_ROWS, ENDS_EARLY, ENDS_EARLY_SPLIT, ENDS_EARLY_HELD, ENDS_DEFER, ENDS_SPLIT_UPD, ENDS_DEFER2, ENDS_DEFER2_SPLIT };
+enum SideWait { WAIT_NONE = 0, WAIT_FORK2, WAIT_SIDE };      // what a side stream waits for in front of its sums: nothing more | the dX chain's event | `side` (ev_join2, recorded there)
+struct SideSum { OnStream on = ON_SIDE; BlockRange a, b; SideWait behind = WAIT_NONE; bool second_event = false; };      // (second_event: completes ev_dec2, not ev_dec)
+struct StepEndPlan {
+    EndCase how = ENDS_JOINED;
+    bool update = false;        // Adam in every reduction's epilogue
+    bool join_both = false;     // ENDS_JOINED: the main stream waits for `side` as well as for the tail stream
+    BlockRange main_a, main_b;  // the main stream's share of the table
+    int nside = 0;
+    SideSum side[2];            // in host enqueue order
+    StepLeft left;              // what the step will have left behind when all of this is enqueued
+};
+
 struct iwae_model {
     iwae_config cfg;
     int X, Xp32;
@@ -248,10 +292,12 @@ struct iwae_model {
     // layer descriptor table
     std::vector<iwae::LayerDesc> descs;
     iwae::LayerDesc* d_descs = nullptr;
-    int elem_blocks = 0, reduce_blocks = 0;
+    TableBounds tb;
     bool descs_dirty = true;
     StepOptions opt;
     StepPlan plan;             // the kernels and streams of the step in flight: written by plan_step (forward_impl), read by the backward pass and the entry points behind it
+    StepEndPlan end;           // ... and how it ends: written by plan_step_end (backward_impl)
+    StepLeft left;
     // per-call state: written by begin_forward only (the backward pass and eps_src read the forward's copy)
     FwdCall call;
     int B = 0, k = 0, M = 0, Mp = 0, Bp = 0;
@@ -299,24 +345,14 @@ struct iwae_model {
     hipStream_t side2 = nullptr;       // the hidden layers' weight gradients beside the output layer's (option no_side2: behind it on `side`)
     hipEvent_t ev_s2 = nullptr;
     hipEvent_t ev_ar = nullptr;        // data-parallel step: recorded behind the encoder segment's all-reduce (dp_finish)
-    bool early_held = false;           // in-library data-parallel step: backward_impl left the decoder's slab reduction to dp_finish
     hipEvent_t ev_lse = nullptr;
     hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_blk = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_dec = nullptr;
-    // Single-GPU train step: the decoder's slab reduction + Adam (90 % of the slab bytes) stays on the side stream and is
-    // NOT joined at the end of the step -- nothing needs the decoder's new weights before the next step's d1 layer, so it
-    // runs beside the next encoder forward.  dec_pending: ev_dec (recorded behind it) has not been waited for yet;
-    // join_side() does that, and every entry point that touches parameters, gradients or the decoder calls it.
-    bool dec_pending = false;
-    size_t split_offset = 0;    // iwae_forward_backward_split: first float of the flat gradient that was left on the side stream
     int fake_s = 0;             // DIAG builds: byte ablations of s (option fake_s)
     int abl_skip = 0;           // DIAG builds: launch ablations of the full-size step (option abl_skip; timing only, results wrong): 1 no output-layer weight gradient,
                                 // 2 no hidden-layer weight gradients, 4 no deferred decoder reduction + update, 8 no latent_bwd_kernel, 16 no noise draw ahead
     int wg_debug = 0;           // option wg_debug (DIAG builds): diagnostic ablations of wgradp_kernel (kernels.h)
     int num_cus = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    int early_first2 = -1;      // 2-layer model: first reduce block behind the image encoder's layers (everything whose weight gradients run on the side streams)
-    bool dec2_pending = false;
     hipEvent_t ev_dec2 = nullptr;
-    int early_first = -1;       // first reduce block of the decoder's layers when they are the tail of the table, else -1
     int timing = 0;            // 0 off, n > 0: time every n-th forward (event records cost a few us of stream bubble each)
     int64_t timing_calls = 0;
     bool time_this = false;

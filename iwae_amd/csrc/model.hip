@@ -173,7 +173,7 @@ std::vector<Linear*> all_linears(iwae_model* m) {
 }
 
 // table order enc1 | enc2 | dec2 | dec1 [| prior]: are the decoder's three layers (one table entry each) the tail of the table / does the
-// 2-layer model's share of it start with the per-sample encoder?  (build_descs turns these into early_first / early_first2)
+// 2-layer model's share of it start with the per-sample encoder?  (plan_step_end asks: only then do TableBounds::dec1 / enc2 open a side stream's range)
 bool dec_layers_last(const iwae_model* m) {
     const int d0 = m->dec1[0].sub[0];
     return m->dec1[0].nsub == 1 && m->dec1[1].nsub == 1 && m->dec1[2].nsub == 1 && m->dec1[1].sub[0] == d0 + 1 && m->dec1[2].sub[0] == d0 + 2 && d0 + 3 == (int)m->klayers.size();
@@ -206,11 +206,14 @@ int build_descs(iwae_model* m) {
         blocks += (d.Kin * d.Nout + d.Nout + 255) / 256;
         rblocks += ((d.Kin + 1) * ((d.Nout + 3) / 4) + 63) / 64;     // float4 groups: (Kin weight rows + bias row) x ceil(Nout/4)
     }
-    m->elem_blocks = blocks;
-    m->reduce_blocks = rblocks;
-    m->early_first = -1;
-    m->early_first2 = side_layers_from_enc2(m) ? m->descs[m->enc2[0].sub[0]].rblock_begin : -1;      // (table order: enc1, enc2, dec2, dec1)
-    if (dec_layers_last(m)) m->early_first = m->descs[m->dec1[0].sub[0]].rblock_begin;
+    auto at = [&](int i) { return i < (int)m->descs.size() ? TableBounds::At{m->descs[i].rblock_begin, m->descs[i].block_begin} : TableBounds::At{rblocks, blocks}; };
+    const bool two = m->cfg.n_layers == 2;
+    TableBounds& t = m->tb;      // (table order: enc1, enc2, dec2, dec1, prior)
+    t.enc1_end = at(m->enc1[2].sub[m->enc1[2].nsub - 1] + 1);
+    t.enc2 = two ? at(m->enc2[0].sub[0]) : t.enc1_end;
+    t.dec2 = two ? at(m->dec2[0].sub[0]) : t.enc1_end;
+    t.dec1 = at(m->dec1[0].sub[0]); t.dec1_out = at(m->dec1[2].sub[0]); t.dec1_end = at(m->dec1[2].sub[0] + 1);
+    t.end = at((int)m->descs.size());
     if (!m->d_descs) HIPCHK(hipMalloc((void**)&m->d_descs, sizeof(LayerDesc) * m->descs.size()));
     HIPCHK(hipMemcpyAsync(m->d_descs, m->descs.data(), sizeof(LayerDesc) * m->descs.size(), hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -221,9 +224,24 @@ int build_descs(iwae_model* m) {
     return IWAE_OK;
 }
 
+// The two kernels that walk the layer table, with the handle's constants filled in.
+// reduce_blocks: the slabs of reduce blocks a (and b, same launch) summed into the flat gradient on st; update: Adam (alpha) + the weight-image
+// refresh in the epilogue; done: its completion event, riding on the dispatch packet; with_means: one extra block makes the step's batch means
+void reduce_blocks(iwae_model* m, hipStream_t st, BlockRange a, BlockRange b, float alpha, bool update, hipEvent_t done, bool with_means) {
+    const float* per_b = with_means ? ptr<float>(m->per_b) : nullptr;
+    if (done) set_launch_stop_event(done);
+    launch_reduce_grads(m->d_descs, (int)m->descs.size(), a.first, a.count, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, update ? 1 : 0,
+                        per_b, per_b ? m->B : 0, !per_b ? 0.f : m->cfg.n_layers == 2 ? 1.f : m->beta, per_b ? m->d_scalars : nullptr, st, b.first, b.count);
+}
+// adam_blocks: Adam on elementwise blocks [first, first + count) of the flat gradient times grad_scale; done as above (update = false: the weight images only)
+void adam_blocks(iwae_model* m, hipStream_t st, int first, int count, float alpha, float grad_scale, hipEvent_t done = nullptr, bool update = true) {
+    if (done) set_launch_stop_event(done);
+    launch_adam(m->d_descs, (int)m->descs.size(), count, m->param, m->grad, m->mom, m->vel, alpha, grad_scale, m->adam_b1, m->adam_b2, m->adam_eps, update ? 1 : 0, st, first);
+}
+
 int refresh_images(iwae_model* m) {   // rebuild bf16 A-images from the fp32 master weights
     if (m->descs_dirty) CHK(build_descs(m));
-    launch_adam(m->d_descs, (int)m->descs.size(), m->elem_blocks, m->param, m->grad, m->mom, m->vel, 0.f, 1.f, m->adam_b1, m->adam_b2, m->adam_eps, 0, m->stream);
+    adam_blocks(m, m->stream, 0, m->tb.end.e, 0.f, 1.f, nullptr, false);
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
@@ -681,6 +699,75 @@ StepPlan plan_step(const iwae_model* m, int B, int k, int objective, bool bwd, c
     return p;
 }
 
+// How that step ends, from its plan and the caller's StepEnd: who sums which weight-gradient slabs, on which stream, behind which wait, with or without
+// Adam, and what that leaves behind.  As pure as plan_step: it reads the plan, the options and the layer table (TableBounds) and touches no stream,
+// event or buffer; it fills e in place.
+void plan_step_end(const iwae_model* m, const StepPlan& p, StepEnd mode, StepEndPlan& e) {
+    const StepOptions& o = m->opt;
+    const TableBounds& t = m->tb;
+    const bool two = m->cfg.n_layers == 2;
+    const bool fuse = mode == END_UPDATE, split = mode == END_GRAD_SPLIT || mode == END_GRAD_SPLIT_HELD;
+    const bool dec_own = !two && !p.dec_rows && dec_layers_last(m);      // the decoder's layers can be summed apart from the rest: by the stream that carried their gradients
+    // the decoder's slab sums + Adam stay on the side stream and are NOT joined at the end of the step (join_side)
+    const bool defer = fuse && o.allow_defer && dec_own;      // (2-layer: the main stream needs the side-stream block gradients anyway)
+    // ... as one deferred update per side stream, each behind the weight gradients it carried (option defer_split)
+    const bool split_upd = defer && o.defer_split && p.hid_on == ON_SIDE2 && !p.group3 && p.early_wout;
+    // gradient only: the decoder's layers are summed into the flat gradient on the side stream, right behind their weight gradients
+    const bool early = !fuse && dec_own;
+    // 2-layer training step at large row counts (round 3): every layer behind the image encoder has its weight gradients on the side
+    // streams; their slab sums + Adam follow there, instead of the main stream waiting for both side streams and then summing all 94 MB itself
+    const bool defer2 = fuse && two && o.allow_defer && o.allow_defer2 && side_layers_from_enc2(m) && p.chain2_bwd && p.early_wout && o.use_side2 && !split;
+    // ... one update per side stream, each for the layers whose weight gradients IT carried
+    const bool defer2_split = defer2 && p.tail == ON_SIDE2 && o.allow_defer2_split && m->dec2[0].nsub == 1 && m->dec1[0].nsub == 1 && m->dec1[2].nsub == 1;
+    e = StepEndPlan();
+    e.update = fuse;
+    e.how = early ? (mode == END_GRAD_SPLIT_HELD ? ENDS_EARLY_HELD : split ? ENDS_EARLY_SPLIT : ENDS_EARLY) : defer2 ? (defer2_split ? ENDS_DEFER2_SPLIT : ENDS_DEFER2) :
+            p.dec_rows ? ENDS_DEC_ROWS : defer ? (split_upd ? ENDS_SPLIT_UPD : ENDS_DEFER) : ENDS_JOINED;
+    // joined: every weight gradient launched on a side stream is in its slabs before the main stream sums them -- the 2-layer model's per-sample
+    // blocks' went to `side` behind the output layer's, so where that is not the tail both side streams join.  (early / defer: the side stream
+    // sums its own; defer2: likewise, nothing to join; dec_rows: nothing ran on a side stream)
+    e.join_both = e.how == ENDS_JOINED && two && p.tail != ON_SIDE;
+    // the main stream's share of the table: [lo, hi) -- empty when wgrad_rows_kernel took the encoder and everything else is
+    // deferred to the side streams (the full-size 1- and 2-layer steps) or rode in the same launch (few data rows: p.dec_rows, where
+    // the decoder's three layers drop out of the range and leave two)
+    const int lo = p.rows_enc ? t.enc1_end.r : 0, hi = (defer || early) ? t.dec1.r : defer2 ? t.enc2.r : t.end.r;
+    const int d0 = p.dec_rows ? t.dec1.r : hi, d1 = p.dec_rows ? t.dec1_end.r : hi;
+    e.main_a = BlockRange{lo, std::max(0, std::min(d0, hi) - lo)};
+    e.main_b = BlockRange{d1, std::max(0, hi - d1)};
+    e.left.split_offset = early && split ? m->klayers[m->dec1[0].sub[0]].offW : m->nparam;
+    e.left.on = p.tail;
+    if (e.how == ENDS_JOINED || e.how == ENDS_DEC_ROWS) return;
+    // the side streams' shares, in the order they are enqueued
+    auto sum = [&](OnStream on, TableBounds::At a0, TableBounds::At a1, TableBounds::At b0, TableBounds::At b1, SideWait behind = WAIT_NONE, bool second = false) {
+        e.side[e.nside++] = SideSum{on, BlockRange{a0.r, a1.r - a0.r}, BlockRange{b0.r, b1.r - b0.r}, behind, second};
+    };
+    if (e.how == ENDS_DEFER2_SPLIT) {
+        // each side stream sums and updates the layers whose weight gradients IT carried, as soon as its own chain ends: the second one the
+        // encode block q(z2|z1) and the decoder's two tanh layers, the first one the decode block p(z1|z2) and the output layer (two block
+        // ranges per launch: table order enc2 | dec2 | dec1).  The next forward waits for both events (join_side).
+        sum(ON_SIDE2, t.enc2, t.dec2, t.dec1, t.dec1_out);
+        sum(ON_SIDE, t.dec2, t.dec1, t.dec1_out, t.end, WAIT_NONE, true);
+    } else if (e.how == ENDS_DEFER2) {
+        sum(p.tail, t.enc2, t.end, t.end, t.end, p.tail != ON_SIDE ? WAIT_SIDE : WAIT_NONE);
+    } else if (e.how == ENDS_SPLIT_UPD) {
+        // Round 5: one deferred update per side stream, each behind the weight gradients it carried -- no hand-off between the two side
+        // streams in front of the update, and the output layer's share (54 % of the decoder's slabs) is done ~20 us before the hidden layers'
+        // gradients end.  The output layer's gradient forked behind the decoder FORWARD: its update rewrites the W3 image dec_bwd_kernel
+        // reads, so `side` waits for that kernel's event first (long complete by then).
+        sum(ON_SIDE, t.dec1_out, t.end, t.end, t.end, WAIT_FORK2, true);
+        sum(ON_SIDE2, t.dec1, t.dec1_out, t.end, t.end);
+    } else {      // ENDS_DEFER and the three ENDS_EARLY cases
+        // The decoder's layers (90 % of the slab bytes): slab sums [+ Adam] on the side stream, behind its weight gradients
+        // (which wait for ev_fork2, i.e. for dX of d1, the last reader of the decoder's weight images -- without that order
+        // the trajectory test caught a stale-image race), joined by the next user of the decoder (join_side): it runs beside
+        // the encoder's backward pass / update and the next step's encoder forward.  (held: planned here, launched by dp_finish)
+        sum(p.tail, t.dec1, t.end, t.end, t.end);
+        if (e.how == ENDS_EARLY_HELD) e.left.held = e.side[0].a;
+    }
+    e.left.dec = e.how != ENDS_EARLY;      // (ENDS_EARLY: the main stream has waited for ev_dec itself by the end of the step)
+    e.left.dec2 = e.nside == 2;
+}
+
 // log_w / log-mean-exp arguments of the call in flight (lse_kernel, or the kernel that does its work: StepPlan::lse_at); the buffers exist (lse_alloc)
 void lse_args(iwae_model* m, int objective, bool bwd, const iwae_tensors* want, LseArgs& a) {
     const bool two = m->cfg.n_layers == 2;
@@ -1013,29 +1100,18 @@ float adam_alpha(iwae_model* m, float lr) {      // keras Adam: lr_t = lr * sqrt
     return (float)((double)lr * sqrt(1.0 - pow((double)m->adam_b2, t)) / (1.0 - pow((double)m->adam_b1, t)));
 }
 
-// fused_lr >= 0: the optimizer update runs inside the slab reduction (single-GPU train step); < 0: gradient only
-// hold_early (the in-library data-parallel step): the decoder's slab reduction is NOT launched here but by dp_finish, behind the wait that
-// orders the step's two all-reduces (m->early_held)
-int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool split = false, bool hold_early = false) {
+// end: how the step ends (StepEnd); lr: Adam's learning rate where that is END_UPDATE.  plan_step_end decides everything about it up front
+int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
     if (!m->have_forward) return fail(IWAE_ERR_STATE, "backward without forward");
     if (m->fwd_was_f32) return fail(IWAE_ERR_STATE, "the last forward ran in float32 mode");
     const StepPlan& p = m->plan;
     const StepOptions& o = m->opt;
     const bool two = m->cfg.n_layers == 2;
     const int B = m->B, k = m->k, M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X, Xp = m->Xp32;
-    // ---- the end of the step, from the plan and this call's own arguments (nothing further down decides anything)
-    const bool fuse = fused_lr >= 0.0f;
-    // the decoder's slab sums + Adam stay on the side stream and are NOT joined at the end of the step (join_side)
-    const bool defer = fuse && o.allow_defer && dec_layers_last(m) && !two && !p.dec_rows;      // (2-layer: the main stream needs the side-stream block gradients anyway)
-    // ... as one deferred update per side stream, each behind the weight gradients it carried (option defer_split)
-    const bool split_upd = defer && o.defer_split && p.hid_on == ON_SIDE2 && !p.group3 && p.early_wout;
-    // gradient only: the decoder's layers are summed into the flat gradient on the side stream, right behind their weight gradients
-    const bool early = !fuse && dec_layers_last(m) && !two && !p.dec_rows;
-    // 2-layer training step at large row counts (round 3): every layer behind the image encoder has its weight gradients on the side
-    // streams; their slab sums + Adam follow there, instead of the main stream waiting for both side streams and then summing all 94 MB itself
-    const bool defer2 = fuse && two && o.allow_defer && o.allow_defer2 && side_layers_from_enc2(m) && p.chain2_bwd && p.early_wout && o.use_side2 && !split;
-    // ... one update per side stream, each for the layers whose weight gradients IT carried
-    const bool defer2_split = defer2 && p.tail == ON_SIDE2 && o.allow_defer2_split && m->dec2[0].nsub == 1 && m->dec1[0].nsub == 1 && m->dec1[2].nsub == 1;
+    // (planned up front although build_descs may still run below: TableBounds depends on the layers' Kin, Nout and table positions alone, fixed at
+    // creation -- a rebuild for new row splits or slab pointers moves no block boundary)
+    plan_step_end(m, p, end, m->end);
+    const StepEndPlan& e = m->end;
     hipStream_t st = m->stream, tail = on_stream(m, p.tail);
     MlpWs& w = m->wdec1;
     const int Hp = m->dec1[0].Np32;
@@ -1183,9 +1259,9 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
         }
         HIPCHK(hipGetLastError());
     }
-    if (p.hid_on == ON_SIDE2 && !split_upd) HIPCHK(hipStreamWaitEvent(m->side2, m->ev_s2, 0));
+    if (p.hid_on == ON_SIDE2 && e.how != ENDS_SPLIT_UPD) HIPCHK(hipStreamWaitEvent(m->side2, m->ev_s2, 0));
     }      // (!group3)
-    const float alpha = fuse ? adam_alpha(m, fused_lr) : 0.0f;
+    const float alpha = e.update ? adam_alpha(m, lr) : 0.0f;
     if (m->descs_dirty) CHK(build_descs(m));
 
     const float* dz1 = ptr<float>(w.dz);
@@ -1263,8 +1339,7 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
     if (m->has_prior) CHK(block_bwd(m, m->prior, m->wprior, ptr<uint16_t>(m->condP), B, false, false));
     CHK(block_bwd(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, false, false, false, nullptr, p.rows_enc, p.lat_fuse ? &lat_args : nullptr));
     if (m->descs_dirty) CHK(build_descs(m));      // (the encoder's splits were planned after the first build)
-    const int enc_end = m->enc1[2].sub[m->enc1[2].nsub - 1] + 1;      // first table entry behind the image encoder's layers
-    const int rb_lo = !p.rows_enc ? 0 : enc_end < (int)m->descs.size() ? m->descs[enc_end].rblock_begin : m->reduce_blocks;
+    // ---- the end of the step, as planned (StepEndPlan): optional join, the main stream's sums, per side stream at most one wait and one launch
     // split (data-parallel step, iwae_forward_backward_split): the decoder's layers are summed into the flat gradient on the
     // side stream, right behind their weight gradients, and NOT joined here -- the caller's all-reduce of that segment is
     // ordered behind the side stream and runs beside the encoder's backward pass; join_side() (every later entry point) joins.
@@ -1272,93 +1347,32 @@ int backward_impl(iwae_model* m, int objective, float fused_lr = -1.0f, bool spl
     // reduction runs on the side stream and the main stream joins it behind its own, shorter, encoder reduction.
     // (2-layer deferred update: the next forward joins in front of z1 (join_side).  The image rewrite is safe for the same reason as in the 1-layer
     // step: the side streams' weight gradients wait for the events behind the dX chains (ev_fork2, ev_blk), the last readers of those images.)
-    m->split_offset = m->nparam;
-    m->early_held = false;
-    if (early) {
-        if (hold_early && split) m->early_held = true;
-        else {
-        set_launch_stop_event(m->ev_dec);
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                            m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, tail);
+    const bool side_first = e.how == ENDS_EARLY || e.how == ENDS_EARLY_SPLIT;      // (gradient only: the decoder's slabs are ready first, its sums are enqueued first)
+    auto side_sums = [&]() -> int {
+        for (int i = 0; i < e.nside; ++i) {
+            const SideSum& s = e.side[i];
+            hipStream_t ss = on_stream(m, s.on);
+            if (s.behind == WAIT_FORK2) HIPCHK(hipStreamWaitEvent(ss, m->ev_fork2, 0));
+            if (s.behind == WAIT_SIDE) { HIPCHK(hipEventRecord(m->ev_join2, m->side)); HIPCHK(hipStreamWaitEvent(ss, m->ev_join2, 0)); }
+            if (e.how == ENDS_DEFER && (m->abl_skip & 4)) HIPCHK(hipEventRecord(m->ev_dec, ss));      // (DIAG builds, timing only: no deferred reduction + update)
+            else reduce_blocks(m, ss, s.a, s.b, alpha, e.update, s.second_event ? m->ev_dec2 : m->ev_dec, false);
         }
-        m->dec_pending = true;
-        if (split) m->split_offset = m->descs[m->dec1[0].sub[0]].offW;
-    } else if (defer2) {       // (the side streams' layers are summed and updated there, further down: nothing to join)
-    } else if (p.dec_rows) {     // (nothing ran on a side stream)
-    } else if (!defer) {       // join: every weight gradient launched on the side stream is in its slabs
+        return IWAE_OK;
+    };
+    if (e.how == ENDS_JOINED) {
         HIPCHK(hipEventRecord(m->ev_join, tail));
         HIPCHK(hipStreamWaitEvent(st, m->ev_join, 0));
-        if (two && tail != m->side) {      // the per-sample blocks' weight gradients went to `side` behind the output layer's: both side streams join
-            HIPCHK(hipEventRecord(m->ev_join2, m->side));
-            HIPCHK(hipStreamWaitEvent(st, m->ev_join2, 0));
-        }
+        if (e.join_both) { HIPCHK(hipEventRecord(m->ev_join2, m->side)); HIPCHK(hipStreamWaitEvent(st, m->ev_join2, 0)); }
     }
-    {
-        // the main stream's share of the table: [rb_lo, rb_hi) -- empty when wgrad_rows_kernel took the encoder and everything else is
-        // deferred to the side streams (the full-size 1- and 2-layer steps) or rode in the same launch (few data rows: p.dec_rows); that
-        // kernel's extra block makes the batch means whenever it runs
-        const int rb_hi = (defer || early) ? m->early_first : defer2 ? m->early_first2 : m->reduce_blocks;
-        const int rb_d0 = p.dec_rows ? m->descs[m->dec1[0].sub[0]].rblock_begin : rb_hi;        // (p.dec_rows: the decoder's three layers drop out of the range)
-        const int d_end = m->dec1[2].sub[0] + 1;
-        const int rb_d1 = !p.dec_rows ? rb_hi : d_end < (int)m->descs.size() ? m->descs[d_end].rblock_begin : m->reduce_blocks;
+    if (side_first) CHK(side_sums());
+    {   // (wgrad_rows_kernel's extra block makes the batch means whenever it runs, else the reduction's)
         ScopedTimer tm_red(m, T_REDUCE);
-        if (p.rows_enc) CHK(block_wgrad_rows(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, alpha, fuse, true, p.dec_rows));
-        const int n1 = std::max(0, std::min(rb_d0, rb_hi) - rb_lo), n2 = std::max(0, rb_hi - rb_d1);
-        if (!p.rows_enc || n1 + n2 > 0)
-            launch_reduce_grads(m->d_descs, (int)m->descs.size(), rb_lo, n1, m->grad, m->param, m->mom, m->vel,
-                                alpha, m->adam_b1, m->adam_b2, m->adam_eps, fuse ? 1 : 0, p.rows_enc ? nullptr : ptr<float>(m->per_b), B, two ? 1.f : m->beta, m->d_scalars, st,
-                                rb_d1, n2);
+        if (p.rows_enc) CHK(block_wgrad_rows(m, m->enc1, m->wenc1, ptr<uint16_t>(m->xP), B, alpha, e.update, true, p.dec_rows));
+        if (!p.rows_enc || e.main_a.count + e.main_b.count > 0) reduce_blocks(m, st, e.main_a, e.main_b, alpha, e.update, nullptr, !p.rows_enc);
     }
-    if (early && !split) CHK(join_side(m));
-    if (defer2_split) {
-        // each side stream sums and updates the layers whose weight gradients IT carried, as soon as its own chain ends: the second one the
-        // encode block q(z2|z1) and the decoder's two tanh layers, the first one the decode block p(z1|z2) and the output layer (two block
-        // ranges per launch: table order enc2 | dec2 | dec1).  The next forward waits for both events (join_side).
-        const int b_dec2 = m->descs[m->dec2[0].sub[0]].rblock_begin, b_dec1 = m->descs[m->dec1[0].sub[0]].rblock_begin, b_out = m->descs[m->dec1[2].sub[0]].rblock_begin;
-        set_launch_stop_event(m->ev_dec);
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first2, b_dec2 - m->early_first2, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1,
-                            m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, m->side2, b_dec1, b_out - b_dec1);
-        set_launch_stop_event(m->ev_dec2);
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), b_dec2, b_dec1 - b_dec2, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1, m->adam_b2,
-                            m->adam_eps, 1, nullptr, 0, 0.f, nullptr, m->side, b_out, m->reduce_blocks - b_out);
-        m->dec_pending = true; m->dec2_pending = true;
-    } else if (defer2) {
-        if (tail != m->side) {
-            HIPCHK(hipEventRecord(m->ev_join2, m->side));
-            HIPCHK(hipStreamWaitEvent(tail, m->ev_join2, 0));
-        }
-        set_launch_stop_event(m->ev_dec);
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first2, m->reduce_blocks - m->early_first2, m->grad, m->param, m->mom,
-                            m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, tail);
-        m->dec_pending = true;
-    }
-    if (split_upd) {
-        // Round 5: one deferred update per side stream, each behind the weight gradients it carried -- no hand-off between the two side
-        // streams in front of the update, and the output layer's share (54 % of the decoder's slabs) is done ~20 us before the hidden layers'
-        // gradients end.  The output layer's gradient forked behind the decoder FORWARD: its update rewrites the W3 image dec_bwd_kernel
-        // reads, so `side` waits for that kernel's event first (long complete by then).
-        const int b_out = m->descs[m->dec1[2].sub[0]].rblock_begin;
-        HIPCHK(hipStreamWaitEvent(m->side, m->ev_fork2, 0));
-        set_launch_stop_event(m->ev_dec2);
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), b_out, m->reduce_blocks - b_out, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1,
-                            m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, m->side);
-        set_launch_stop_event(m->ev_dec);
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, b_out - m->early_first, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1,
-                            m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, m->side2);
-        m->dec_pending = true; m->dec2_pending = true;
-    } else if (defer) {
-        // The decoder's layers (90 % of the slab bytes): slab sums + Adam on the side stream, behind its weight gradients
-        // (which wait for ev_fork2, i.e. for dX of d1, the last reader of the decoder's weight images -- without that order
-        // the trajectory test caught a stale-image race), joined by the next user of the decoder (join_side): it runs beside
-        // the encoder's backward pass / update and the next step's encoder forward.
-        if (m->abl_skip & 4) HIPCHK(hipEventRecord(m->ev_dec, tail));
-        else {
-        set_launch_stop_event(m->ev_dec);
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                            m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, 1, nullptr, 0, 0.f, nullptr, tail);
-        }
-        m->dec_pending = true;
-    }
+    if (e.how == ENDS_EARLY) HIPCHK(hipStreamWaitEvent(st, m->ev_dec, 0));
+    if (!side_first && e.how != ENDS_EARLY_HELD) CHK(side_sums());
+    m->left = e.left;
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
@@ -1437,7 +1451,7 @@ int check_objective(iwae_model* m, int objective) {
 int adam_impl(iwae_model* m, float lr, float gscale) {
     if (m->descs_dirty) CHK(build_descs(m));
     const float alpha = adam_alpha(m, lr);
-    launch_adam(m->d_descs, (int)m->descs.size(), m->elem_blocks, m->param, m->grad, m->mom, m->vel, alpha, gscale, m->adam_b1, m->adam_b2, m->adam_eps, 1, m->stream);
+    adam_blocks(m, m->stream, 0, m->tb.end.e, alpha, gscale);
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
@@ -1785,10 +1799,12 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
 // Round 5: two streams.  The decoder's three weight gradients (58 % of the backward pass's FLOPs, needed by nobody until the update) go to the
 // side stream: the hidden layers' behind the dX product that makes their operand, the output layer's LAST -- it needs only s, g2 and the
 // row weights, so it is what runs beside the main stream's few-row tail (dz, the latent sums, the encoder's seven launches on the batch's
-// images: 64 workgroups each on 256 CUs).  fused_lr >= 0 (the single-GPU train step): the update is part of it -- the encoder's
+// images: 64 workgroups each on 256 CUs).  END_UPDATE (the single-GPU train step): the update is part of it -- the encoder's
 // layers on the main stream, the decoder's on the side stream behind its own slab reduction, DEFERRED: the next step's encoder forward
 // and sampling run beside the output layer's gradient, and forward_f32 joins (ev_dec) in front of the decoder forward.
-int backward_f32(iwae_model* m, int objective, float fused_lr = -1.0f) {
+// (end: END_GRAD or END_UPDATE; this path leaves no segment of the gradient unjoined for a caller, so the split ends are END_GRAD)
+int backward_f32(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
+    const bool update = end == END_UPDATE;
     m->f32_slab_want_step = 0;
     if (!m->have_forward || !m->fwd_was_f32) return fail(IWAE_ERR_STATE, "backward without a float32 forward");
     const bool two = m->cfg.n_layers == 2;
@@ -1891,45 +1907,38 @@ int backward_f32(iwae_model* m, int objective, float fused_lr = -1.0f) {
         CHK(f32_block_bwd(m, m->prior[0].sub[0], m->f32.prior, ptr<float>(m->cond) + (size_t)m->call.cond_row0 * m->C, m->C, B, Dp0, nullptr, 0));
     CHK(f32_block_bwd(m, m->enc1[0].sub[0], m->f32.enc1, m->C > 0 ? ptr<float>(m->f32.xcat) : m->f32_x, X + m->C, B, Dp0, nullptr, 0));
     m->f32_slab_want = std::max(m->f32_slab_want, m->f32_slab_want_step);
-    m->split_offset = m->nparam;       // (data-parallel step: one all-reduce of the whole gradient)
+    // what the step leaves: nothing for a caller's own all-reduce (split_offset = n: the data-parallel step exchanges the whole gradient at once);
+    // with the side stream, the decoder's sums [+ update] there (join_side: whoever reads the decoder's gradient or parameters next)
+    m->left = StepLeft{use_side, false, BlockRange(), m->nparam, ON_SIDE};
     if (!use_side) {
         CHK(f32_flush_reductions(m));      // every row-split gradient's slabs -> the flat gradient, one launch
-        if (fused_lr >= 0.0f) CHK(adam_impl(m, fused_lr, 1.0f));
+        if (update) CHK(adam_impl(m, lr, 1.0f));
         HIPCHK(hipGetLastError());
         return IWAE_OK;
     }
-    const int b0 = m->descs[b_dec1].block_begin;
-    const float alpha = fused_lr >= 0.0f ? adam_alpha(m, fused_lr) : 0.0f;
+    const int b0 = m->tb.dec1.e;
+    const float alpha = update ? adam_alpha(m, lr) : 0.0f;
     CHK(f32_flush_reductions(m, 0));       // the slabs of the main stream's gradients (every block but the decoder)
-    if (fused_lr >= 0.0f)
-        launch_adam(m->d_descs, (int)m->descs.size(), b0, m->param, m->grad, m->mom, m->vel, alpha, 1.0f, m->adam_b1, m->adam_b2, m->adam_eps, 1, st, 0);
+    if (update) adam_blocks(m, st, 0, b0, alpha, 1.0f);
     CHK(f32_flush_reductions(m, 1));       // the decoder's, on the side stream
-    if (fused_lr >= 0.0f)
-        launch_adam(m->d_descs, (int)m->descs.size(), m->elem_blocks - b0, m->param, m->grad, m->mom, m->vel, alpha, 1.0f, m->adam_b1, m->adam_b2, m->adam_eps, 1, m->side, b0);
+    if (update) adam_blocks(m, m->side, b0, m->tb.end.e - b0, alpha, 1.0f);
     HIPCHK(hipEventRecord(m->ev_dec, m->side));
-    m->dec_pending = true;                 // (join_side: whoever reads the decoder's gradient or parameters next)
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
 
-// Data-parallel step, second half (the gradient of this rank's shard is in m->grad; backward_impl(split) left the decoder's
-// segment on the side stream, unjoined): all-reduce + Adam(grad_scale 1/N) of the decoder's layers on the SIDE stream -- they run
+// Data-parallel step, second half (the gradient of this rank's shard is in m->grad; backward_impl(END_GRAD_SPLIT_HELD) left the decoder's
+// segment to the side stream, its slabs not yet summed): all-reduce + Adam(grad_scale 1/N) of the decoder's layers on the SIDE stream -- they run
 // beside the encoder's backward pass and the next encoder forward, as the single-GPU step's deferred update does -- and of the
 // encoder's layers on the main stream.  Models without such a segment: one all-reduce + Adam on the main stream.
 int dp_finish(iwae_model* m, float lr) {
     const float alpha = adam_alpha(m, lr);
     const float gs = 1.0f / (float)m->comm_world;
     if (m->descs_dirty) CHK(build_descs(m));
-    const size_t n = m->nparam, off = m->split_offset;
-    if (m->early_held && !(off < n && m->dec_pending)) {      // (cannot happen on today's call paths -- nothing joins between backward_impl and here --; kept correct anyway: the held reduction runs now, joined)
-        launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                            m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, on_stream(m, m->plan.tail));
-        HIPCHK(hipEventRecord(m->ev_join, on_stream(m, m->plan.tail)));
-        HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
-        m->early_held = false;
-    }
-    if (off < n && m->dec_pending) {
-        const int b0 = m->descs[m->dec1[0].sub[0]].block_begin;
+    const size_t n = m->nparam, off = m->left.split_offset;
+    if (m->left.held.count > 0) {      // (set only with a segment, off < n, that nothing has joined: iwae_train_step calls nothing that joins between backward_impl and here)
+        hipStream_t tail = on_stream(m, m->left.on);
+        const int b0 = m->tb.dec1.e;
         // Two communicators, one per stream.  Until an N > 1 run has shown that the two collectives may be co-resident, they are ORDERED
         // on the device, and in the order in which their inputs become ready: the encoder's segment first (main stream: its gradient is
         // complete ~30 us before the decoder's, whose reduction waits for the hidden layers' weight gradients), the decoder's behind an
@@ -1939,25 +1948,19 @@ int dp_finish(iwae_model* m, float lr) {
         { ScopedTimer tm(m, T_AR_ENC); NCCLCHK(g_rccl.AllReduce(m->grad, m->grad, off, ncclFloat32, ncclSum, m->comm_main, m->stream)); }
         // Round 5: the order costs (almost) nothing.  The event rides on the dispatch packet of the encoder's update (the kernel right behind
         // the all-reduce: no record bubble on the main stream), and the tail stream waits for it IN FRONT of the decoder's slab reduction --
-        // which backward_impl left to this function (early_held) -- i.e. right behind the wait for the output layer's gradient it performs
+        // which backward_impl left to this function (StepLeft::held) -- i.e. right behind the wait for the output layer's gradient it performs
         // there anyway, ~15 us before the decoder's exchange instead of directly in front of it (a barrier packet costs its 6-10 us wherever
         // its event stands; here it falls into the shadow of the hidden layers' gradients).  Measured in the one-rank rehearsal: see DESIGN.md 8.
-        if (!m->opt.dp_concurrent) set_launch_stop_event(m->ev_ar);
-        launch_adam(m->d_descs, (int)m->descs.size(), b0, m->param, m->grad, m->mom, m->vel, alpha, gs, m->adam_b1, m->adam_b2, m->adam_eps, 1, m->stream, 0);
-        if (!m->opt.dp_concurrent) HIPCHK(hipStreamWaitEvent(on_stream(m, m->plan.tail), m->ev_ar, 0));
-        if (m->early_held) {
-            launch_reduce_grads(m->d_descs, (int)m->descs.size(), m->early_first, m->reduce_blocks - m->early_first, m->grad, m->param, m->mom,
-                                m->vel, 0.0f, m->adam_b1, m->adam_b2, m->adam_eps, 0, nullptr, 0, 0.f, nullptr, on_stream(m, m->plan.tail));
-            m->early_held = false;
-        }
-        { ScopedTimer tm(m, T_AR_DEC, on_stream(m, m->plan.tail)); NCCLCHK(g_rccl.AllReduce(m->grad + off, m->grad + off, n - off, ncclFloat32, ncclSum, m->comm_side, on_stream(m, m->plan.tail))); }
-        set_launch_stop_event(m->ev_dec);           // join_side() now waits for the decoder's UPDATE, not just its gradient
-        launch_adam(m->d_descs, (int)m->descs.size(), m->elem_blocks - b0, m->param, m->grad, m->mom, m->vel, alpha, gs, m->adam_b1, m->adam_b2, m->adam_eps, 1,
-                    on_stream(m, m->plan.tail), b0);
+        adam_blocks(m, m->stream, 0, b0, alpha, gs, m->opt.dp_concurrent ? nullptr : m->ev_ar);
+        if (!m->opt.dp_concurrent) HIPCHK(hipStreamWaitEvent(tail, m->ev_ar, 0));
+        reduce_blocks(m, tail, m->left.held, BlockRange(), 0.0f, false, nullptr, false);
+        m->left.held = BlockRange();
+        { ScopedTimer tm(m, T_AR_DEC, tail); NCCLCHK(g_rccl.AllReduce(m->grad + off, m->grad + off, n - off, ncclFloat32, ncclSum, m->comm_side, tail)); }
+        adam_blocks(m, tail, b0, m->tb.end.e - b0, alpha, gs, m->ev_dec);           // join_side() now waits for the decoder's UPDATE, not just its gradient
     } else {
         CHK(join_side(m));
         { ScopedTimer tm(m, T_AR_ENC); NCCLCHK(g_rccl.AllReduce(m->grad, m->grad, n, ncclFloat32, ncclSum, m->comm_main, m->stream)); }
-        launch_adam(m->d_descs, (int)m->descs.size(), m->elem_blocks, m->param, m->grad, m->mom, m->vel, alpha, gs, m->adam_b1, m->adam_b2, m->adam_eps, 1, m->stream, 0);
+        adam_blocks(m, m->stream, 0, m->tb.end.e, alpha, gs);
     }
     HIPCHK(hipGetLastError());
     return IWAE_OK;
@@ -1987,13 +1990,9 @@ void free_buf(DevBuf& b) {
 
 // orders the main stream behind a deferred decoder update (and the noise prefetch in front of it) still on the side stream
 int join_side(iwae_model* m) {
-    if (m->dec2_pending) {      // (2-layer step: the first side stream's own deferred update)
-        HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec2, 0));
-        m->dec2_pending = false;
-    }
-    if (!m->dec_pending) return IWAE_OK;
-    HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec, 0));
-    m->dec_pending = false;
+    if (m->left.dec2) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec2, 0));      // (the first side stream's own deferred update)
+    if (m->left.dec) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_dec, 0));
+    m->left.dec = m->left.dec2 = false;
     return IWAE_OK;
 }
 
@@ -2359,10 +2358,10 @@ int iwae_forward_backward(iwae_handle m, const float* x, int32_t B, int32_t k, f
     CHK(check_objective(m, objective));
     if (m->cfg.precision == IWAE_PREC_FP32) {
         CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
-        CHK(backward_f32(m, objective));
+        CHK(backward_f32(m, objective, END_GRAD));
     } else {
         CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
-        CHK(backward_impl(m, objective));
+        CHK(backward_impl(m, objective, END_GRAD));
     }
     CHK(fetch_outputs(m, scalars, want));
     m->noise_step += 1;
@@ -2376,14 +2375,14 @@ int iwae_forward_backward_split(iwae_handle m, const float* x, int32_t B, int32_
     CHK(check_objective(m, objective));
     if (m->cfg.precision == IWAE_PREC_FP32) {       // float32 mode: nothing is left on the side stream (*side_offset = n)
         CHK(forward_f32(m, x, B, k, beta, eps, objective, true, nullptr, FwdCall{m->batch_offset}));
-        CHK(backward_f32(m, objective));
+        CHK(backward_f32(m, objective, END_GRAD_SPLIT));
         CHK(join_side(m));
     } else {
         CHK(forward_impl(m, x, B, k, beta, eps, objective, true, nullptr, FwdCall{m->batch_offset}));
-        CHK(backward_impl(m, objective, -1.0f, true));
+        CHK(backward_impl(m, objective, END_GRAD_SPLIT));
     }
-    *side_stream = (void*)on_stream(m, m->plan.tail);
-    *side_offset = m->split_offset;
+    *side_stream = (void*)on_stream(m, m->left.on);
+    *side_offset = m->left.split_offset;
     m->noise_step += 1;
     return IWAE_OK;
 }
@@ -2518,12 +2517,12 @@ int iwae_train_step(iwae_handle m, const float* x, int32_t B, int32_t k, float b
     if (m->cfg.precision == IWAE_PREC_FP32) {   // float32 mode: forward, closed-form backward, [exchange,] Adam -- all in float32
         CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
         if (m->comm_main || want) {
-            CHK(backward_f32(m, objective));
+            CHK(backward_f32(m, objective, m->comm_main ? END_GRAD_SPLIT_HELD : END_GRAD));
             if (want) CHK(fetch_outputs(m, nullptr, want));      // tensors refer to the pre-update forward (src/iwae1.py:162)
             if (m->comm_main) CHK(dp_finish(m, lr));
             else { CHK(join_side(m)); CHK(adam_impl(m, lr, 1.0f)); }
         } else {
-            CHK(backward_f32(m, objective, lr));   // the update rides behind the gradients, the decoder's on the side stream (deferred)
+            CHK(backward_f32(m, objective, END_UPDATE, lr));   // the update rides behind the gradients, the decoder's on the side stream (deferred)
         }
         CHK(fetch_outputs(m, scalars, nullptr));
         m->noise_step += 1;
@@ -2531,15 +2530,15 @@ int iwae_train_step(iwae_handle m, const float* x, int32_t B, int32_t k, float b
     }
     CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want, FwdCall{m->batch_offset}));
     if (m->comm_main) {                         // data-parallel step: exchange between gradient and update (iwae_comm_init)
-        CHK(backward_impl(m, objective, -1.0f, true, true));
+        CHK(backward_impl(m, objective, END_GRAD_SPLIT_HELD));
         if (want) CHK(fetch_outputs(m, nullptr, want));
         CHK(dp_finish(m, lr));
     } else if (want) {
-        CHK(backward_impl(m, objective));
+        CHK(backward_impl(m, objective, END_GRAD));
         CHK(fetch_outputs(m, nullptr, want));   // tensors refer to the pre-update forward (src/iwae1.py:162)
         CHK(adam_impl(m, lr, 1.0f));
     } else {
-        CHK(backward_impl(m, objective, lr));   // Adam fused into the gradient reduction
+        CHK(backward_impl(m, objective, END_UPDATE, lr));   // Adam fused into the gradient reduction
     }
     CHK(fetch_outputs(m, scalars, nullptr));
     m->noise_step += 1;
@@ -2777,10 +2776,10 @@ int iwae_grad_moments(iwae_handle m, const float* x, int32_t B, int32_t k, float
     for (int j = 0; j < M; ++j) {
         if (f32) {
             CHK(forward_f32(m, xd, B, k, beta, nullptr, objective, true, nullptr, FwdCall{m->batch_offset}));
-            CHK(backward_f32(m, objective));
+            CHK(backward_f32(m, objective, END_GRAD));
         } else {
             CHK(forward_impl(m, xd, B, k, beta, nullptr, objective, true, nullptr, FwdCall{m->batch_offset}));
-            CHK(backward_impl(m, objective));
+            CHK(backward_impl(m, objective, END_GRAD));
         }
         m->noise_step += 1;
         CHK(join_side(m));               // the fold reads the whole gradient: behind every stream that wrote part of it

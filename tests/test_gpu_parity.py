@@ -645,6 +645,62 @@ def test_two_layer_deferred_update_is_bitwise_equivalent(gpu):
     assert t0 == t1 == 12
 
 
+@pytest.mark.parametrize("layers,B,k,cond,opts", [
+    (1, 20, 5, False, {}),                          # 100 rows: the decoder's gradients ride in the encoder's launch, two block ranges in one main-stream reduction, no side stream
+    (1, 60, 50, False, {}),                         # 3 000 rows (2 048 < M <= 4 096): the grouped side-stream launch, the second side stream is the tail
+    (1, 100, 50, False, {}),                        # 5 000 rows: below the 8 192-row kernels, above the grouped launch
+    (1, 170, 50, False, {}),                        # 8 500 rows, the full-size streams: deferred update | early reduction | the one dp_finish launches
+    (1, 170, 50, False, {"defer_split": 1}),        # ... one deferred update per side stream
+    (2, 170, 50, False, {}),                        # 2-layer, 8 500 rows: one deferred update per side stream
+    (2, 170, 50, False, {"no_defer2_split": 1}),    # ... one, on the tail stream
+    (1, 6, 5, True, {}),                            # conditional prior: its block sits behind the decoder in the table, so no end defers
+    (1, 170, 50, True, {}),                         # ... at the full-size stream layout
+])
+def test_every_end_of_the_step_lands_on_the_same_parameters(gpu, layers, B, k, cond, opts):
+    """A training step ends in one of four ways (backward_impl's StepEnd): the update fused into the slab sums, the gradient joined and
+    updated by the caller (with tensors in between, or as forward_backward + adam_step), and the in-library data-parallel step (here
+    with ONE rank: the decoder's sums held for dp_finish, two all-reduces that are the identity).  They differ in streams, events and
+    launches only: three steps on the device's own noise land on bit-identical parameters, Adam moments and step count.  The shapes
+    are the smallest that reach each branch of the end-of-step plan."""
+    from iwae_amd.native import NativeModel
+    nh, nl = (200, 100) if layers == 1 else ([200, 100], [100, 50])
+    C, lr = (10 if cond else 0), 1e-3
+    x = O.synthetic_binarized(B, 17)
+    y = np.eye(10, dtype=np.float32)[np.random.default_rng(B + k).integers(0, 10, B)]
+    P = O.init_params(layers, nh, nl, 23, x_mean=O.synthetic_pixel_means(), **({"cond_dim": C, "cond_prior": True} if cond else {}))
+
+    def run(end):
+        m = NativeModel(layers, nh, nl, seed=123, cond_dim=C, cond_prior=cond, options=opts)
+        m.set_params(O.flatten_params(P))
+        if end == "dp":
+            m.comm_init(NativeModel.comm_unique_id(), 1, 0)
+        for t in range(3):
+            m.set_step(t, 0)
+            if cond:
+                m.set_condition(y)
+            if end == "fused" or end == "dp":
+                m.train_step(x, k, 1.0, lr, "iwae_elbo", scalars=False)
+            elif end == "tensors":
+                m.train_step(x, k, 1.0, lr, "iwae_elbo", want=("lpxz",), scalars=False)
+            else:
+                m.forward_backward(x, k, 1.0, "iwae_elbo")
+                m.adam_step(lr)
+        out = m.get_params().copy(), m.get_adam_state()
+        if end == "dp":
+            m.comm_destroy()
+        m.close()
+        return out
+
+    p0, (m0, v0, t0) = run("fused")
+    assert t0 == 3
+    for end in ("tensors", "grad_then_adam", "dp"):
+        p1, (m1, v1, t1) = run(end)
+        np.testing.assert_array_equal(p0, p1, err_msg="parameters, fused vs " + end)
+        np.testing.assert_array_equal(m0, m1, err_msg="first moments, fused vs " + end)
+        np.testing.assert_array_equal(v0, v1, err_msg="second moments, fused vs " + end)
+        assert t1 == t0, end
+
+
 @pytest.mark.parametrize("B,k,obj,nh,nl,xd", [(6, 5, "iwae_elbo", 200, 100, 784), (9, 3, "vae_elbo_kl", 64, 20, 48), (170, 50, "iwae_elbo", 200, 100, 784)])
 def test_conditional_model_matches_oracle(gpu, B, k, obj, nh, nl, xd):
     """tasks/task05.py:101-168 (CIWAE): encoder on concat(x, onehot(y)), decoder on concat(z, onehot(y)); the condition
