@@ -18,7 +18,7 @@ import _activity_common as LA
 import _aggregate_common as AP
 import _grad_moments_common as GM
 from _parity_common import (EMU_ROW_ATOL, EMU_SCALAR_ATOL, EMU_GRAD_REL, EXACT_SCALAR_ATOL, EXACT_GRAD_REL, F32_SCALAR_REL, F32_GRAD_REL,
-                            F32_ROW_ATOL, _grad_rel_errors, _densities_at_device_head, _densities_at_device_heads_2layer)
+                            F32_ROW_ATOL, _grad_rel_errors, _elementwise_ok, _densities_at_device_head, _densities_at_device_heads_2layer)
 
 pytestmark = pytest.mark.gpu
 
@@ -57,19 +57,6 @@ def _oracle(layers, nh, nl, xd, B, k, seed, obj, beta, emu):
     else:
         res, g = O.loss_grads_2layer(P, x, eps[0], eps[1], 1.0, obj, rnd=rnd)
     return x, P, eps, res, g
-
-
-def _elementwise_ok(flat, grads):
-    """|d| <= 3 % of the tensor's largest element, per tensor (a mis-addressed strip shows as a block of wrong columns, not in a norm)."""
-    off, worst = 0, 0.0
-    for dW, db in grads:
-        for t in (dW, db):
-            got = flat[off:off + t.size].reshape(t.shape).astype(np.float64)
-            off += t.size
-            d, top = float(np.max(np.abs(got - t))), float(np.max(np.abs(t)))
-            assert d <= 3e-2 * top + 1e-9, (d, top)
-            worst = max(worst, d / (top + 1e-30))
-    return worst
 
 
 def _adam_ref(P, g):
