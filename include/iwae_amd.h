@@ -158,7 +158,10 @@ int iwae_forward_backward_split(iwae_handle h, const float* x, int32_t B, int32_
 int iwae_adam_step(iwae_handle h, float lr, float grad_scale);      /* keras Adam(lr, epsilon=1e-4), main.py:93 */
 /* keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon) hyper-parameters of this handle's optimizer; the default
  * is what the reference trains with: Adam(lr, epsilon=1e-4) = (0.9, 0.999, 1e-4), main.py:93.  Keras form: epsilon is
- * added to sqrt(v) outside the bias correction. */
+ * added to sqrt(v) outside the bias correction.  They take effect with the next update and are NOT part of the saved
+ * state: iwae_get_adam_state / iwae_set_adam_state carry m, v and the step count only, so whoever resumes from a checkpoint
+ * calls iwae_set_adam again (a new handle starts at the default).  A rejected call (beta outside [0, 1), epsilon <= 0,
+ * NaN) changes nothing. */
 int iwae_set_adam(iwae_handle h, float beta_1, float beta_2, float epsilon);
 /* conditional model (cond_dim > 0): y [n, cond_dim] (host or device) for the NEXT forward / train step / eval_llh / decode
  * of n images -- tasks/task05.py:108-118 (y_onehot), :185-190 (sample(z, y)).  Stays set until replaced. */
