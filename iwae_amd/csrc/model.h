@@ -1,5 +1,6 @@
-// What the host translation units of libiwae_amd.so share: the handle (iwae_model), its workspaces, and the helpers model.hip defines and
-// analysis.hip calls.  Internal to the library -- everything here has hidden visibility, the exported surface is include/iwae_amd.h alone.
+// What the host translation units of libiwae_amd.so share: the handle (iwae_model), its workspaces, the helpers model.hip defines and
+// analysis.hip and step_f32.hip call, and the float32 step's entry points (step_f32.hip).  Internal to the library -- everything here has
+// hidden visibility, the exported surface is include/iwae_amd.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -190,6 +191,34 @@ struct StepPlan {
     OnStream tail = ON_SIDE;    // the side stream that finishes last (carries the decoder's reduction / exchange / update)
 };
 
+// The kernels and streams of one float32 step, as StepPlan is the bf16 step's.  plan_step_f32 decides all of it from shapes, options and the
+// staged input (the one-launch decoder reads x in 16-byte segments, and a caller's device pointer is read in place: dec_fwd_f32_ok); forward_f32,
+// backward_f32 and f32_dw read it and decide nothing themselves.  Every float32 forward writes m->f32_plan anew (fwd_was_f32 says which of the
+// two plans is the valid one); the backward half is valid only from a training forward to the backward_f32 of that same step.
+enum F32DecFwd { F32_DEC_GEMMS = 0, F32_DEC_ONE_LAUNCH };                    // the decoder forward: three GEMM launches | dec_fwd_f32_kernel
+enum F32PxFrom { F32_PX_BERN_PASS = 0, F32_PX_GEMM_EPILOGUE, F32_PX_DEC_KERNEL };      // log p(x|z): bern_f32_kernel over the stored logits | the output layer's GEMM epilogue (px_parts partial sums per row) | dec_fwd_f32_kernel (whole)
+// the host enqueue order of the decoder's three weight gradients among its dX products (backward_f32)
+enum F32DwOrder {
+    F32_DW_ONE_STREAM = 0,      // each in front of its layer's dX product, on the main stream
+    F32_DW_WOUT_FIRST,          // side stream: the output layer's first, the hidden layers' each behind the dX product that makes its operand
+    F32_DW_WOUT_LAST,           // ... the output layer's behind the hidden layers' (option f32_wout_last)
+    F32_DW_BEHIND_DX            // ... all three behind the whole dX chain, first layer first (option f32_dw_last)
+};
+struct F32Plan {
+    const float* x = nullptr;   // device x [B][X] of the call (stage_input): the backward pass reads it again
+    // ---- forward
+    F32DecFwd dec_fwd = F32_DEC_GEMMS;
+    F32PxFrom px_from = F32_PX_BERN_PASS;
+    int px_parts = 1;           // > 1: log p(x|z) arrives in px_part as that many partial sums per row
+    bool keeps_s = false;       // the forward left s = x - sigmoid(l) where the logits would have gone (the backward pass takes the row weight in its two consumers)
+    bool want_dreg = false;     // the call wants the second (DReG) log q per sample
+    bool lme_only = false;      // forward-only call that hands out no tensor: lse_kernel makes the log-mean-exp alone
+    // ---- backward (filled when the forward is a training step's)
+    F32DwOrder dw_order = F32_DW_ONE_STREAM;
+    int dw_tile_mode = 0;       // tile mode of the decoder's weight gradients (F32_DW_BEHIND_DX; 0: tiles as picked, 1: 4-wave tiles, 2: ... at 3 waves per SIMD)
+    bool side() const { return dw_order != F32_DW_ONE_STREAM; }      // the decoder's weight gradients + sums [+ update] run on the side stream
+};
+
 // How a training step ends: what becomes of the weight-gradient slabs once every layer's are written.
 enum StepEnd {
     END_GRAD = 0,           // the flat gradient, every stream joined (iwae_forward_backward, iwae_grad_moments, the train step that hands out tensors)
@@ -217,6 +246,8 @@ struct StepLeft {
     BlockRange held;            // count > 0: the decoder's slab reduction over these blocks is not launched yet: dp_finish does
     size_t split_offset = 0;    // first float of the flat gradient that was left on the side stream (nparam: none)
     OnStream on = ON_SIDE;      // the stream that carries it
+    bool z_pending = false;     // float32 step: ev_join (recorded on the side stream behind the gradient of the decoder's first layer, which reads z) has not been
+                                // waited for yet: the next forward of either precision waits in front of its sampling
 };
 // The end of one bf16 step, decided by plan_step_end from the plan, the options, the layer table and the caller's StepEnd; backward_impl
 // executes it.  A side stream sums (and, `update`, updates) the layers whose weight gradients it carried, in ONE launch of up to two ranges.
@@ -258,8 +289,6 @@ struct iwae_model {
     // backward_f32 (reduce_slabs_multi_f32_kernel): jobs queued by f32_dw, slab offsets in floats (the buffer may still grow while they queue)
     struct F32Pending { size_t off; size_t stride; size_t n; float* out; int nsplit; int seg; };
     std::vector<F32Pending> f32_pending; size_t f32_slab_used = 0;
-    bool f32_side_active = false;      // float32 step: the decoder's weight gradients + update run on the side stream
-    bool f32_z_pending = false;
     bool bf16_side_used = false;      // a bf16 call may have left a speculative draw on a side stream (forward_f32 waits for it on the host)
     size_t f32_slab_want = 0, f32_slab_want_step = 0;      // floats of slabs the last whole step asked for (the buffer's target size) / this step so far
     // An evaluation call's images when they arrive on the host, their bf16 rows and float32 encoder heads (analysis.hip): nothing is read after the call that filled it, so all calls share
@@ -283,7 +312,6 @@ struct iwae_model {
     // caller's start and noise when they arrive on the host, and the outputs
     struct LocalWs { DevBuf st, acc, alpha, mu0, sg0, eps, qmu, qsg, mu, sg, elbo, iwae, bound, grad, logw; } loc;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
-    const float* f32_x = nullptr;             // device x [B][X] of the last float32 forward
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
     ncclComm_t comm_main = nullptr, comm_side = nullptr;
     int comm_world = 1, comm_rank = 0;
@@ -297,6 +325,7 @@ struct iwae_model {
     StepOptions opt;
     StepPlan plan;             // the kernels and streams of the step in flight: written by plan_step (forward_impl), read by the backward pass and the entry points behind it
     StepEndPlan end;           // ... and how it ends: written by plan_step_end (backward_impl)
+    F32Plan f32_plan;          // the float32 step in flight: written by plan_step_f32 (forward_f32), read by backward_f32 and f32_dw
     StepLeft left;
     // per-call state: written by begin_forward only (the backward pass and eps_src read the forward's copy)
     FwdCall call;
@@ -311,7 +340,6 @@ struct iwae_model {
     // lse_kernel's outputs once more, written by the copy of it that runs on the side stream (see forward_impl): the output layer's
     // weight gradient takes its row weights from there
     DevBuf logw2, wn2, gx2, cf2, per_b2;
-    bool f32_keeps_s = false;      // float32 step: the output layer's GEMM epilogue left s where the logits would have gone
     bool g2w_descs = false;     // the layer table was built for a step with plan.g2w
     BlockWs wenc1, wenc2, wdec2, wprior;
     MlpWs wdec1;
@@ -393,8 +421,21 @@ int join_side(iwae_model* m);
 int dense_fwd(iwae_model* m, Linear& L, int epi, const uint16_t* XP, int rows, uint16_t* YP, float* YF, int ldYF, const iwae::SampleArgs* zin = nullptr);
 int block_alloc(iwae_model* m, Linear* blk, BlockWs& w, int R, int Rp, bool bwd, bool need_dx);
 int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R, const float* xf = nullptr, int xdim = 0);
+// (the float32 step's share)
+int begin_forward(iwae_model* m, const float* x, int B, int k, float beta, const FwdCall& call, const float** cond);
+int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float** xd);
+int draw_eps(iwae_model* m, int par, uint32_t step, int M, hipStream_t gs, int max_blocks = 0);
+iwae::EpsSrc eps_src(iwae_model* m, int layer);
+int build_descs(iwae_model* m);
+float adam_alpha(iwae_model* m, float lr);
+void adam_blocks(iwae_model* m, hipStream_t st, int first, int count, float alpha, float grad_scale, hipEvent_t done = nullptr, bool update = true);
+int adam_impl(iwae_model* m, float lr, float gscale);
+
+// ---- defined in step_f32.hip
 int f32_fwd(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, int rows, float* Y, long ldy, int epi, bool no_ksplit);
 int f32_block_fwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, float* head, int Dp, bool no_ksplit);
+int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd, const iwae_tensors* want, const FwdCall& call);
+int backward_f32(iwae_model* m, int objective, StepEnd end, float lr = 0.0f);
 
 // ---- a caller's array may live on the host or on the handle's device.  Input: a device pointer is read in place, host memory is uploaded into ws
 template <class T> int staged_in(iwae_model* m, const T* user, DevBuf& ws, size_t bytes, const T** dev) {

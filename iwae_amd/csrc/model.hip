@@ -70,7 +70,7 @@ static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgra
                                                  "ais_chain",                            // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
                                                  "local_q"};                             // (iwae_local_posterior: likewise local_q_kernel)
 
-namespace {
+namespace {      // (closed and reopened around each helper that model.h declares for step_f32.hip; what is added in between stays internal)
 
 void init_linear(Linear& L, int Kin, int Nspace, bool need_B, bool kmajor) {
     L.Kin = Kin;
@@ -180,6 +180,7 @@ bool dec_layers_last(const iwae_model* m) {
 }
 bool side_layers_from_enc2(const iwae_model* m) { return m->cfg.n_layers == 2 && m->enc2[0].nsub >= 1; }
 
+}  // namespace -- build_descs: external (hidden) linkage, declared in model.h, step_f32.hip calls it too
 int build_descs(iwae_model* m) {
     m->descs.assign(m->klayers.size(), LayerDesc());
     for (Linear* L : all_linears(m)) {
@@ -223,6 +224,7 @@ int build_descs(iwae_model* m) {
     m->g2w_descs = m->plan.g2w;
     return IWAE_OK;
 }
+namespace {      // (internal linkage again)
 
 // The two kernels that walk the layer table, with the handle's constants filled in.
 // reduce_blocks: the slabs of reduce blocks a (and b, same launch) summed into the flat gradient on st; update: Adam (alpha) + the weight-image
@@ -233,11 +235,13 @@ void reduce_blocks(iwae_model* m, hipStream_t st, BlockRange a, BlockRange b, fl
     launch_reduce_grads(m->d_descs, (int)m->descs.size(), a.first, a.count, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, update ? 1 : 0,
                         per_b, per_b ? m->B : 0, !per_b ? 0.f : m->cfg.n_layers == 2 ? 1.f : m->beta, per_b ? m->d_scalars : nullptr, st, b.first, b.count);
 }
+}  // namespace -- adam_blocks: external (hidden) linkage, declared in model.h, step_f32.hip calls it too
 // adam_blocks: Adam on elementwise blocks [first, first + count) of the flat gradient times grad_scale; done as above (update = false: the weight images only)
-void adam_blocks(iwae_model* m, hipStream_t st, int first, int count, float alpha, float grad_scale, hipEvent_t done = nullptr, bool update = true) {
+void adam_blocks(iwae_model* m, hipStream_t st, int first, int count, float alpha, float grad_scale, hipEvent_t done, bool update) {
     if (done) set_launch_stop_event(done);
     launch_adam(m->d_descs, (int)m->descs.size(), count, m->param, m->grad, m->mom, m->vel, alpha, grad_scale, m->adam_b1, m->adam_b2, m->adam_eps, update ? 1 : 0, st, first);
 }
+namespace {      // (internal linkage again)
 
 int refresh_images(iwae_model* m) {   // rebuild bf16 A-images from the fp32 master weights
     if (m->descs_dirty) CHK(build_descs(m));
@@ -249,6 +253,7 @@ int refresh_images(iwae_model* m) {   // rebuild bf16 A-images from the fp32 mas
 // row stride of the cached draws: the latent width rounded to 4, NOT the 32-padded operand width -- D = 100: 400 B instead of 512 B per row,
 // 5.7 MB less per pass over the k = 50, B = 1 024 step's draws (written once, read by the decoder kernel and by latent_bwd_kernel)
 static inline int eps_ld(const iwae_model* m, int layer) { return 4 * ((m->D[layer] + 3) / 4); }
+}  // namespace -- eps_src: external (hidden) linkage, declared in model.h, step_f32.hip calls it too
 EpsSrc eps_src(iwae_model* m, int layer) {
     EpsSrc e;
     e.user = nullptr;
@@ -266,6 +271,7 @@ EpsSrc eps_src(iwae_model* m, int layer) {
     }
     return e;
 }
+namespace {      // (internal linkage again)
 
 // diagnostic (STAMPS=1 build + options dense_stamps_epi / dense_stamps_kt): record the phase stamps of the matching dense launch
 int attach_dense_stamps(iwae_model* m, int epi, DenseArgs& a) {
@@ -489,8 +495,9 @@ int block_wgrad_rows(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* inP
 }
 
 // ---------------------------------------------------------------- the forward pass
+}  // namespace -- draw_eps: external (hidden) linkage, declared in model.h, step_f32.hip calls it too
 // fills eps buffer `par` with the draws of (step, current batch offset) for M data rows on stream gs
-int draw_eps(iwae_model* m, int par, uint32_t step, int M, hipStream_t gs, int max_blocks = 0) {
+int draw_eps(iwae_model* m, int par, uint32_t step, int M, hipStream_t gs, int max_blocks) {
     const int Mp = round_up(M, 128);
     iwae_model::EpsTag& tg = m->eps_tag[par];
     tg.valid = false;
@@ -504,6 +511,7 @@ int draw_eps(iwae_model* m, int par, uint32_t step, int M, hipStream_t gs, int m
     tg.valid = true; tg.step = step; tg.row_offset = (uint64_t)m->call.batch_offset * (uint64_t)m->k; tg.M = M;
     return IWAE_OK;
 }
+namespace {      // (internal linkage again)
 
 #define EPSM_STEPS 8
 // few rows: draws of steps [step0, step0 + EPSM_STEPS) into multi-step buffer `buf` (stream order on gs protects the buffer: see iwae_model::epsm)
@@ -815,6 +823,7 @@ int lse_alloc(iwae_model* m) {
     return IWAE_OK;
 }
 
+}  // namespace -- begin_forward, stage_input: external (hidden) linkage, declared in model.h, step_f32.hip calls them too
 // What both forward passes start with: the argument checks, the conditional model's y rows of these images (*cond, null without) and the
 // handle's per-call state.  A call that is refused leaves that state as it was.
 int begin_forward(iwae_model* m, const float* x, int B, int k, float beta, const FwdCall& call, const float** cond) {
@@ -854,6 +863,7 @@ int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float
     } else CHK(staged_in(m, x, m->xin, (size_t)B * m->X * 4, xd));
     return IWAE_OK;
 }
+namespace {      // (internal linkage again)
 
 int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd,
                  const iwae_tensors* want, const FwdCall& call) {
@@ -863,7 +873,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     const StepPlan& p = m->plan;
     const bool two = m->cfg.n_layers == 2;
     m->bf16_side_used = true;
-    if (m->f32_z_pending) { HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->f32_z_pending = false; }      // (ev_join is this path's too)
+    if (m->left.z_pending) { HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->left.z_pending = false; }      // (ev_join is this path's too)
     m->time_this = m->timing > 0 && (m->timing_calls++ % m->timing) == 0;
     const int M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X, Xp = m->Xp32, Xinp = m->Xinp;
     hipStream_t st = m->stream;
@@ -1094,11 +1104,13 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
 }
 
 // ---------------------------------------------------------------- the backward pass
+}  // namespace -- adam_alpha: external (hidden) linkage, declared in model.h, step_f32.hip calls it too
 float adam_alpha(iwae_model* m, float lr) {      // keras Adam: lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t); advances t
     m->adam_t += 1;
     const double t = (double)m->adam_t;
     return (float)((double)lr * sqrt(1.0 - pow((double)m->adam_b2, t)) / (1.0 - pow((double)m->adam_b1, t)));
 }
+namespace {      // (internal linkage again)
 
 // end: how the step ends (StepEnd); lr: Adam's learning rate where that is END_UPDATE.  plan_step_end decides everything about it up front
 int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
@@ -1448,6 +1460,7 @@ int check_objective(iwae_model* m, int objective) {
     return IWAE_OK;
 }
 
+}  // namespace -- adam_impl: external (hidden) linkage, declared in model.h, step_f32.hip calls it too
 int adam_impl(iwae_model* m, float lr, float gscale) {
     if (m->descs_dirty) CHK(build_descs(m));
     const float alpha = adam_alpha(m, lr);
@@ -1455,477 +1468,7 @@ int adam_impl(iwae_model* m, float lr, float gscale) {
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
-
-// =================================================================== float32 mode
-// The reference's own arithmetic: Keras Dense layers in float32 (src/iwae1.py:31-34,72-75).  Same step structure as the bf16
-// path with plain row-major float32 tensors and one generic MFMA GEMM (fp32_kernels.hip); the per-sample kernels that already
-// work in float32 (sampling + densities, lse_kernel, latent_bwd_kernel, gauss_*_kernel, Adam) are shared.
-int f32_gemm(iwae_model* m, const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc, int M, int N, int K,
-             const float* bias, int epi, const float* ACT, long ldact, bool accumulate, const float* brow_scale = nullptr, const float* orow_scale = nullptr,
-             hipStream_t st = nullptr, bool no_ksplit = false) {
-    GemmF32Args a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.sam = sam; a.sak = sak; a.B = B; a.sbk = sbk; a.sbn = sbn; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
-    a.bias = bias; a.epi = epi; a.ACT = ACT; a.ldact = ldact; a.accumulate = accumulate ? 1 : 0; a.kchunk = K; a.slab_stride = 0;
-    a.brow_scale = brow_scale; a.orow_scale = orow_scale;
-    {   // few rows (the encoder on the batch's images): K split + one reduction pass that carries the epilogue
-        hipStream_t s_ = st ? st : m->stream;
-        // (no_ksplit, iwae_eval_llh: the split depends on how many images a launch holds, and an image's estimate must not -- the evaluator's
-        // encoder is 419 rows beside 2^21 decoder rows, nothing to gain there: test_eval_llh_images_per_launch_are_invisible)
-        const int ns = no_ksplit ? 1 : gemm_f32_fewrows_split(m->opt.gemm_f32, M, N, K);
-        if (ns > 1 && !brow_scale) {
-            a.avec = a.bvec = 0;
-            CHK(ensure(m->f32.kslab, (size_t)ns * M * N * 4, s_));
-            launch_gemm_f32_fewrows(m->opt.gemm_f32, a, ptr<float>(m->f32.kslab), s_);
-            HIPCHK(hipGetLastError());
-            return IWAE_OK;
-        }
-    }
-#ifdef IWAE_DENSE_STAMPS
-    if (m->dstamp_epi == 12 && orow_scale && M >= 4096) {      // diagnostic (STAMPS=1 build, option dense_stamps_epi = 12): phase stamps of the output layer's dX product
-        m->dstamp_waves = ((M + 63) / 64) * ((N + 223) / 224) * 4;
-        CHK(ensure(m->dstamps, (size_t)m->dstamp_waves * 64, st ? st : m->stream));
-        a.stamps = ptr<unsigned long long>(m->dstamps);
-    }
-#endif
-    launch_gemm_f32(m->opt.gemm_f32, a, 1, st ? st : m->stream);
-    HIPCHK(hipGetLastError());
-    return IWAE_OK;
-}
-// DX (+)= (G W^T) * (1 - ACT^2)   (ACT = the stored tanh output of the layer below, or null)
-// (rowscale: row r of G counts with weight rowscale[r] -- applied to the product's rows, in front of the tanh' factor)
-int f32_dx(iwae_model* m, const KerasLayer& kl, const float* G, long ldg, int rows, float* DX, long lddx, const float* ACT, long ldact, bool accumulate,
-           const float* rowscale = nullptr) {
-    return f32_gemm(m, G, ldg, 1, m->param + kl.offW, 1, kl.Nout, DX, lddx, rows, kl.Kin, kl.Nout, nullptr, ACT ? GEMM_EPI_DTANH : GEMM_EPI_NONE, ACT, ldact, accumulate,
-                    nullptr, rowscale);
-}
-// the queued slab sums of this step's float32 weight gradients, one launch per segment (f32_dw): seg 0 = the gradients made on the main stream,
-// seg 1 = the decoder's, made on the side stream (backward_f32); seg < 0: whatever is queued, each segment on its own stream
-int f32_flush_reductions(iwae_model* m, int seg = -1) {
-    for (int sg = 0; sg < 2; ++sg) {
-        if (seg >= 0 && sg != seg) continue;
-        ReduceSlabsJobs jobs;
-        memset(&jobs, 0, sizeof(jobs));
-        for (const auto& p : m->f32_pending) {
-            if (p.seg != sg) continue;
-            ReduceSlabsJob& j = jobs.job[jobs.n++];
-            j.slabs = ptr<float>(m->f32.slab) + p.off; j.stride = p.stride; j.n = p.n; j.out = p.out; j.nsplit = p.nsplit;
-        }
-        if (jobs.n > 0) {
-            launch_reduce_slabs_multi_f32(jobs, sg == 1 ? m->side : m->stream);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    if (seg < 0) m->f32_pending.clear();
-    else m->f32_pending.erase(std::remove_if(m->f32_pending.begin(), m->f32_pending.end(), [seg](const iwae_model::F32Pending& p) { return p.seg == seg; }), m->f32_pending.end());
-    if (m->f32_pending.empty()) m->f32_slab_used = 0;
-    return IWAE_OK;
-}
-// grad W = X^T G, grad b = column sums of G: the row axis is split into fp32 slabs summed in a fixed order (deterministic)
-// (rowscale: G's row r is multiplied by rowscale[r] as it is fetched -- the values the separate g_r s pass used to store)
-int f32_dw(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, const float* G, long ldg, int rows, const float* rowscale = nullptr, int seg = 0, int tile_mode = 0) {
-    hipStream_t st = seg == 1 ? m->side : m->stream;
-    // row splits: enough workgroups to fill the machine (~1 000 tiles of 64 x 64 or 128 x 128), at least 64 rows per split
-    const int tiles = (int)gemm_f32_tiles(m->opt.gemm_f32, kl.Kin + 1, kl.Nout, tile_mode);      // (+ 1: the row of ones whose product row is the bias gradient)
-    const int slots = std::min(m->opt.f32_dw_tiles, gemm_f32_slots(m->opt.gemm_f32, kl.Kin + 1, kl.Nout, tile_mode));
-    int nsplit = std::max(1, std::min(std::min(256, rows / m->opt.f32_dw_min_rows), slots / tiles));      // (rounded DOWN: 1 027 workgroups on 1 024 slots are a second round of 3)
-    while (nsplit > 8 && (tiles * nsplit) % 8 != 0) --nsplit;      // (a multiple of 8 workgroups: gemm_f32_v2_kernel then keeps a split's tiles on one XCD)
-    const size_t nW = (size_t)kl.Kin * kl.Nout;
-    // (round 5: the slabs of every gradient of the step stay until ONE reduction launch at the end of the backward pass; the buffer is sized for a
-    // whole step -- a step that outgrows it falls back to the reduction per tensor, and the buffer grows for the next step)
-    const size_t need = ((size_t)nsplit * (nW + kl.Nout) + 3) & ~(size_t)3;      // (a multiple of 4 floats: the next gradient's slabs stay 16-byte aligned)
-    const bool queue = m->opt.allow_f32_multi_reduce && nsplit > 1 && (m->f32_slab_used + need) * 4 <= m->f32.slab.cap && m->f32_pending.size() + 2 <= REDUCE_SLABS_MAX_JOBS;
-    if (!queue) {
-        if (!m->f32_pending.empty()) CHK(f32_flush_reductions(m));      // (queued jobs still read the buffer ensure() may replace)
-        if (m->f32_side_active) { HIPCHK(hipStreamSynchronize(m->side)); HIPCHK(hipStreamSynchronize(m->stream)); }      // (first steps only: the buffer is still growing)
-        CHK(ensure(m->f32.slab, std::max(need, m->f32_slab_want) * 4, st));
-    }
-    m->f32_slab_want_step += need;
-    float* slabW = ptr<float>(m->f32.slab) + (queue ? m->f32_slab_used : 0);
-    float* slabB = slabW + (size_t)nsplit * nW;
-    GemmF32Args a;
-    memset(&a, 0, sizeof(a));
-    a.A = X; a.sam = 1; a.sak = ldx; a.B = G; a.sbk = ldg; a.sbn = 1; a.M = kl.Kin; a.N = kl.Nout; a.K = rows;
-    a.brow_scale = rowscale; a.tile_mode = tile_mode;
-    a.kchunk = (rows + nsplit - 1) / nsplit; a.kchunk = (a.kchunk + 15) / 16 * 16;
-    const int ns = (rows + a.kchunk - 1) / a.kchunk;
-    // the bias gradient = the column sums of (weighted) G = the product row of a row of ONES appended to X^T (GemmF32Args.Cones): no pass of its own
-    if (ns == 1) {
-        a.C = m->grad + kl.offW; a.ldc = kl.Nout; a.slab_stride = 0; a.Cones = m->grad + kl.offb; a.cones_stride = 0;
-        launch_gemm_f32(m->opt.gemm_f32, a, 1, st);
-    } else {
-        a.C = slabW; a.ldc = kl.Nout; a.slab_stride = nW; a.Cones = slabB; a.cones_stride = (size_t)kl.Nout;
-#ifdef IWAE_DENSE_STAMPS
-        if (m->dstamp_epi == 13 && rowscale) {      // diagnostic (STAMPS=1 build, option dense_stamps_epi = 13): phase stamps of the output layer's weight gradient
-            m->dstamp_waves = ((kl.Kin + 1 + 223) / 224) * ((kl.Nout + 63) / 64) * ns * 4;
-            CHK(ensure(m->dstamps, (size_t)m->dstamp_waves * 64, st));
-            a.stamps = ptr<unsigned long long>(m->dstamps);
-        }
-#endif
-        launch_gemm_f32(m->opt.gemm_f32, a, ns, st);
-        if (queue) {
-            m->f32_pending.push_back({(size_t)(slabW - ptr<float>(m->f32.slab)), nW, nW, m->grad + kl.offW, ns, seg});
-            m->f32_pending.push_back({(size_t)(slabB - ptr<float>(m->f32.slab)), (size_t)kl.Nout, (size_t)kl.Nout, m->grad + kl.offb, ns, seg});
-            m->f32_slab_used += need;
-        } else {
-            launch_reduce_slabs_f32(slabW, nW, ns, nW, m->grad + kl.offW, st);
-            launch_reduce_slabs_f32(slabB, kl.Nout, ns, kl.Nout, m->grad + kl.offb, st);
-            if (m->f32_side_active) { HIPCHK(hipStreamSynchronize(st)); }      // (the next unqueued gradient reuses the buffer's front from another stream)
-        }
-    }
-    HIPCHK(hipGetLastError());
-    return IWAE_OK;
-}
-// backward of a BasicBlock from dhead [R][2Dp] (d mu | d pre-exp): all four weight gradients, optionally dX [R][lddx]
-int f32_block_bwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, int Dp, float* dX, long lddx) {
-    const KerasLayer *l1 = &m->klayers[base], *l2 = l1 + 1, *lmu = l1 + 2, *lsd = l1 + 3;
-    const int H = l1->Nout;
-    const float* dh = ptr<float>(w.dhead);
-    CHK(ensure(w.d2, (size_t)R * H * 4, m->stream));
-    CHK(ensure(w.d1, (size_t)R * H * 4, m->stream));
-    CHK(f32_dw(m, *lmu, ptr<float>(w.h2), H, dh, 2 * Dp, R));
-    CHK(f32_dw(m, *lsd, ptr<float>(w.h2), H, dh + Dp, 2 * Dp, R));
-    CHK(f32_dx(m, *lmu, dh, 2 * Dp, R, ptr<float>(w.d2), H, ptr<float>(w.h2), H, false));
-    CHK(f32_dx(m, *lsd, dh + Dp, 2 * Dp, R, ptr<float>(w.d2), H, ptr<float>(w.h2), H, true));
-    CHK(f32_dw(m, *l2, ptr<float>(w.h1), H, ptr<float>(w.d2), H, R));
-    CHK(f32_dx(m, *l2, ptr<float>(w.d2), H, R, ptr<float>(w.d1), H, ptr<float>(w.h1), H, false));
-    CHK(f32_dw(m, *l1, X, ldx, ptr<float>(w.d1), H, R));
-    if (dX) CHK(f32_dx(m, *l1, ptr<float>(w.d1), H, R, dX, lddx, nullptr, 0, false));
-    return IWAE_OK;
-}
-
-int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd, const iwae_tensors* want,
-                const FwdCall& call) {
-    const float* cond;      // conditional models (tasks/task05.py, tasks/task04.py): y of these images
-    CHK(begin_forward(m, x, B, k, beta, call, &cond));
-    const bool two = m->cfg.n_layers == 2, nks = call.no_ksplit;
-    m->time_this = false;
-    const int M = m->M, Mp = m->Mp, Bp = m->Bp, X = m->X;
-    hipStream_t st = m->stream;
-    if (m->bf16_side_used) {      // a bf16 call's deferred update / speculative draw may sit on either side stream
-        CHK(join_side(m));
-        if (m->side) HIPCHK(hipStreamSynchronize(m->side));
-        if (m->side2) HIPCHK(hipStreamSynchronize(m->side2));
-        m->bf16_side_used = false;
-    }
-    // (a float32 step's own deferred decoder update is joined in front of the decoder forward: the encoder and the sampling run beside it)
-    m->user_eps = eps != nullptr;
-    m->epsc_ptr[0] = m->epsc_ptr[1] = nullptr;
-    if (!eps) {       // the step's draws, kept for the backward pass and the 2-layer densities (same generator as the bf16 path)
-        const int np = (m->epsc_par + 1) % 3;
-        CHK(draw_eps(m, np, m->noise_step, M, st));
-        if (call.k_total > 0) m->eps_tag[np].valid = false;      // a k-chunk's draws: the tag (step, offset, rows) does not describe them
-        if (bwd) m->epsc_par = np;      // (forward-only calls reuse one slot, as in forward_impl)
-        for (int l = 0; l < m->cfg.n_layers; ++l) m->epsc_ptr[l] = ptr<float>(m->epsc[np][l]);
-    } else {
-        CHK(copy_in(m, m->epsbuf, eps, (size_t)M * (m->D[0] + (two ? m->D[1] : 0)) * 4));
-    }
-    const float* xd;
-    CHK(stage_input(m, x, B, true, &xd));
-    m->f32_x = xd;
-    // ---- encoder on the images (conditional models: on concat(x, y), tasks/task05.py:113-118)
-    const int b_enc1 = m->enc1[0].sub[0];
-    CHK(ensure(m->wenc1.head, (size_t)Bp * 2 * m->Dp[0] * 4, st));
-    const float* xenc = xd;
-    if (m->C > 0) {
-        CHK(ensure(m->f32.xcat, (size_t)B * (X + m->C) * 4, st));
-        launch_concat_f32(xd, X, cond, m->C, B, ptr<float>(m->f32.xcat), st);
-        xenc = ptr<float>(m->f32.xcat);
-    }
-    CHK(f32_block_fwd(m, b_enc1, m->f32.enc1, xenc, X + m->C, B, ptr<float>(m->wenc1.head), m->Dp[0], nks));
-    if (m->has_prior) {     // p(z|y) = N(mu_p(y), sigma_p(y)): the prior block on the B condition rows (tasks/task04.py:108,124)
-        CHK(ensure(m->wprior.head, (size_t)Bp * 2 * m->Dp[0] * 4, st));
-        CHK(f32_block_fwd(m, m->prior[0].sub[0], m->f32.prior, cond, m->C, B, ptr<float>(m->wprior.head), m->Dp[0], nks));
-    }
-    for (int i = 0; i < 6; ++i) CHK(ensure(m->rows[i], (size_t)Mp * 4, st));
-    float* lpxz = ptr<float>(m->rows[0]);
-    float* t1 = ptr<float>(m->rows[1]);
-    float* t2 = ptr<float>(m->rows[2]);
-    float* t3 = ptr<float>(m->rows[3]);
-    float* t4 = ptr<float>(m->rows[4]);
-    float* lqd = ptr<float>(m->rows[5]);
-    // ---- z (z1) = mu + sigma*eps and its densities (iwae1.py:59,107,109)
-    const int Dz = m->D[0] + m->C;      // row width of the decoder's input: z, or concat(z, y) (tasks/task05.py:185)
-    if (m->f32_z_pending) {      // the previous step's gradient of the decoder's first layer reads z on the side stream
-        HIPCHK(hipStreamWaitEvent(st, m->ev_join, 0));
-        m->f32_z_pending = false;
-    }
-    CHK(ensure(m->f32.z[0], (size_t)Mp * Dz * 4, st));
-    {
-        SampleArgs s;
-        memset(&s, 0, sizeof(s));
-        s.head = ptr<float>(m->wenc1.head); s.ldH = 2 * m->Dp[0]; s.Dp = m->Dp[0]; s.D = m->D[0]; s.head_per_row = 0;
-        s.M = M; s.Mp = Mp; s.k = k; s.B = B; s.eps = eps_src(m, 0);
-        s.ZP = nullptr; s.ZF = ptr<float>(m->f32.z[0]); s.ldZF = Dz;
-        s.cond = cond; s.C = m->C;      // (the sampling kernel writes y into features D .. D + C - 1 of every row)
-        s.prior_head = m->has_prior ? ptr<float>(m->wprior.head) : nullptr;
-        s.lp_prior = two ? nullptr : t1;
-        s.lq = two ? t3 : t2;
-        const bool want_dreg = !two && (objective == OBJ_DREG || (!bwd && !call.log_w_only));
-        s.lq_dreg = want_dreg ? lqd : nullptr;
-        launch_sample(s, st);
-    }
-    if (two) {       // q(z2|z1), z2, p(z1|z2)  (iwae2.py:63-65, :90, :118-124)
-        const int b_enc2 = m->enc2[0].sub[0], b_dec2 = m->dec2[0].sub[0];
-        CHK(ensure(m->wenc2.head, (size_t)Mp * 2 * m->Dp[1] * 4, st));
-        CHK(f32_block_fwd(m, b_enc2, m->f32.enc2, ptr<float>(m->f32.z[0]), m->D[0], M, ptr<float>(m->wenc2.head), m->Dp[1], nks));
-        CHK(ensure(m->f32.z[1], (size_t)Mp * m->D[1] * 4, st));
-        SampleArgs s;
-        memset(&s, 0, sizeof(s));
-        s.head = ptr<float>(m->wenc2.head); s.ldH = 2 * m->Dp[1]; s.Dp = m->Dp[1]; s.D = m->D[1]; s.head_per_row = 1;
-        s.M = M; s.Mp = Mp; s.k = k; s.B = B; s.eps = eps_src(m, 1);
-        s.ZP = nullptr; s.ZF = ptr<float>(m->f32.z[1]); s.ldZF = m->D[1];
-        s.lp_prior = t2; s.lq = t4; s.lq_dreg = nullptr;
-        launch_sample(s, st);
-        CHK(ensure(m->wdec2.head, (size_t)Mp * 2 * m->Dp[0] * 4, st));
-        CHK(f32_block_fwd(m, b_dec2, m->f32.dec2, ptr<float>(m->f32.z[1]), m->D[1], M, ptr<float>(m->wdec2.head), m->Dp[0], nks));
-        GaussLpArgs g;
-        memset(&g, 0, sizeof(g));
-        g.zhead = ptr<float>(m->wenc1.head); g.ldZH = 2 * m->Dp[0]; g.Dzp = m->Dp[0];
-        g.phead = ptr<float>(m->wdec2.head); g.ldPH = 2 * m->Dp[0]; g.Dpp = m->Dp[0];
-        g.D = m->D[0]; g.M = M; g.k = k; g.eps = eps_src(m, 0); g.out = t1;
-        launch_gauss_lp(g, st);
-    }
-    // ---- decoder + Bernoulli log-likelihood (iwae1.py:81-83,111)
-    const int b_dec1 = m->dec1[0].sub[0];
-    const KerasLayer *d1 = &m->klayers[b_dec1], *d2 = d1 + 1, *d3 = d1 + 2;
-    const int H = d1->Nout;
-    CHK(join_side(m));      // the decoder's parameters (and g1, g2, s, which the previous step's weight gradients still read)
-    // Round 4: the whole decoder forward in ONE launch where its shapes fit (dec_fwd_f32_kernel: rows stationary, activations in LDS, the
-    // weights streamed from the float32 master parameters; log p(x|z) per row comes out whole) -- the k = 5000 evaluator's three GEMM launches
-    // ran at 0.35 of the f32 MFMA peak between them.  A training step also keeps g1, g2 and s = x - sigmoid(l) for the backward pass.
-    DecFwdF32Args df;
-    memset(&df, 0, sizeof(df));
-    df.Z = ptr<float>(m->f32.z[0]); df.ldz = Dz; df.Din = Dz; df.M = M; df.H = H; df.X = X;
-    df.W1 = m->param + d1->offW; df.b1 = m->param + d1->offb; df.W2 = m->param + d2->offW; df.b2 = m->param + d2->offb;
-    df.W3 = m->param + d3->offW; df.b3 = m->param + d3->offb;
-    df.XB = xd; df.k = k; df.lpxz = lpxz; df.zero = m->d_zero; df.ldg = H; df.ldS = X;
-    // (round 5: a TRAINING step takes the three GEMM launches again -- with gemm_f32_v2_kernel they are faster than the fused kernel once g1, g2 and s
-    // have to be stored anyway: 1.280 -> 1.248 ms; option f32_dec_fused_train = 1 for the fused kernel)
-    int px_parts = 1;      // > 1: log p(x|z) arrives in px_part as that many partial sums per row
-    const bool fused_dec = m->opt.allow_f32_dec_fused && (!bwd || m->opt.f32_dec_fused_train) && !(want && want->logits) && M >= 4096 && dec_fwd_f32_ok(df);
-    if (bwd || !fused_dec) {
-        CHK(ensure(m->f32.g1, (size_t)M * H * 4, st));
-        CHK(ensure(m->f32.g2, (size_t)M * H * 4, st));
-    }
-    if (fused_dec) {
-        px_parts = 1;
-        m->f32_keeps_s = false;
-        if (bwd) {
-            CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
-            df.G1 = ptr<float>(m->f32.g1); df.G2 = ptr<float>(m->f32.g2); df.S = ptr<float>(m->f32.logits);
-            m->f32_keeps_s = true;
-        }
-#ifdef IWAE_DENSE_STAMPS
-        if (m->dstamp_epi == 11) {      // diagnostic (STAMPS=1 build, option dense_stamps_epi = 11): phase stamps of dec_fwd_f32_kernel
-            m->dstamp_waves = ((M + 63) / 64) * 4;
-            CHK(ensure(m->dstamps, (size_t)m->dstamp_waves * 64, st));
-            df.stamps = ptr<unsigned long long>(m->dstamps);
-        }
-#endif
-        launch_dec_fwd_f32(df, st);
-    } else {
-    CHK(f32_fwd(m, *d1, ptr<float>(m->f32.z[0]), Dz, M, ptr<float>(m->f32.g1), H, GEMM_EPI_TANH, nks));
-    CHK(f32_fwd(m, *d2, ptr<float>(m->f32.g1), H, M, ptr<float>(m->f32.g2), H, GEMM_EPI_TANH, nks));
-    // forward-only calls at large row counts (the k = 5000 evaluator): log p(x|z) in the epilogue of the output layer's GEMM -- the float32
-    // logits (1.6 GB per launch of 2^19 rows) are neither written nor read back; per 64-column half tile a partial sum that lse_kernel adds
-    // Round 3, training step: the same epilogue also leaves s = x - sigmoid(l) where the logits would have gone -- the backward pass reads s and
-    // takes the row weight g_r inside its two consumers (f32_dw / f32_dx with rowscale) instead of a pass that rewrites 160 MB into dl = g_r s.
-    const bool fuse_bern = m->opt.allow_f32_bern_fused && !(want && want->logits) && gemm_f32_takes_big(M, X, 1);
-    px_parts = 1;
-    m->f32_keeps_s = false;
-    if (fuse_bern) {
-        px_parts = 2 * ((X + 127) / 128);
-        CHK(ensure(m->px_part, (size_t)px_parts * Mp * 4, st));
-        GemmF32Args ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.A = ptr<float>(m->f32.g2); ga.sam = H; ga.sak = 1; ga.B = m->param + d3->offW; ga.sbk = d3->Nout; ga.sbn = 1; ga.M = M; ga.N = X; ga.K = H;
-        ga.bias = m->param + d3->offb; ga.epi = GEMM_EPI_BERN; ga.kchunk = H;
-        if (bwd) {
-            CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
-            ga.C = ptr<float>(m->f32.logits); ga.ldc = X;
-            m->f32_keeps_s = true;
-        }
-        ga.XB = xd; ga.bern_k = k; ga.bern_X = X; ga.part = ptr<float>(m->px_part); ga.part_stride = (size_t)Mp;
-        launch_gemm_f32(m->opt.gemm_f32, ga, 1, st);
-    } else {
-    CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
-    CHK(f32_fwd(m, *d3, ptr<float>(m->f32.g2), H, M, ptr<float>(m->f32.logits), X, GEMM_EPI_NONE, nks));
-    launch_bern_f32(ptr<float>(m->f32.logits), X, xd, X, M, k, lpxz, st);
-    }
-    }      // (!fused_dec)
-    if (want && want->logits) {      // reference [k,B,X] order
-        CHK(ensure(m->scratch, (size_t)M * X * 4, st));
-        launch_export_mat(ptr<float>(m->f32.logits), B, k, X, ptr<float>(m->scratch), st);
-        CHK(copy_out(m, want->logits, m->scratch.p, (size_t)M * X * 4));
-    }
-    // ---- log_w, log-mean-exp over k, objectives (iwae1.py:113-139): the shared kernel
-    CHK(ensure(m->logw, (size_t)Mp * 4, st));
-    CHK(ensure(m->wn, (size_t)Mp * 4, st));
-    {   // (as forward_impl: wgrad_rows_kernel's row-weighted path reads gx in whole 32-row stages -- 0 x a non-finite pad would be NaN)
-        const void* before = m->gx.p;
-        CHK(ensure(m->gx, (size_t)Mp * 4, st));
-        if (m->gx.p != before) HIPCHK(hipMemsetAsync(m->gx.p, 0, m->gx.cap, st));
-    }
-    CHK(ensure(m->cf, (size_t)Mp * 16, st));
-    CHK(ensure(m->per_b, (size_t)PB_COUNT * B * 4, st));
-    {
-        LseArgs a;
-        memset(&a, 0, sizeof(a));
-        if (!two) {
-            a.term[0] = lpxz; a.coef[0] = 1.f; a.term[1] = t1; a.coef[1] = beta; a.term[2] = t2; a.coef[2] = -beta;
-            a.head = ptr<float>(m->wenc1.head); a.ldH = 2 * m->Dp[0]; a.D = m->D[0]; a.Dp = m->Dp[0]; a.cz_on = 1.f;
-        } else {
-            a.term[0] = lpxz; a.coef[0] = 1.f; a.term[1] = t1; a.coef[1] = 1.f; a.term[2] = t2; a.coef[2] = 1.f;
-            a.term[3] = t3; a.coef[3] = -1.f; a.term[4] = t4; a.coef[4] = -1.f; a.head = nullptr; a.cz_on = 0.f;
-        }
-        a.lq_dreg = (!two && (objective == OBJ_DREG || (!bwd && !call.log_w_only))) ? lqd : nullptr;
-        a.B = B; a.k = k; a.beta = two ? 1.f : beta; a.objective = objective;
-        a.lme_only = (!bwd && call.log_w_only && !want) ? 1 : 0;
-        a.logw = ptr<float>(m->logw); a.wn = ptr<float>(m->wn); a.gx = ptr<float>(m->gx);
-        a.cf = ptr<float4>(m->cf); a.per_b = ptr<float>(m->per_b);
-        a.n_px_part = px_parts; a.px_stride = (size_t)Mp; a.term0_out = lpxz;
-        if (px_parts > 1) a.term[0] = ptr<float>(m->px_part);      // (the fused Bernoulli epilogue's per-half-tile partial sums)
-        launch_lse(a, st);
-        launch_scalars(ptr<float>(m->per_b), B, two ? 1.f : beta, m->d_scalars, st);
-    }
-    HIPCHK(hipGetLastError());
-    m->have_forward = true;
-    m->fwd_was_f32 = true;
-    return IWAE_OK;
-}
-
-// closed-form backward in float32: leaves the flat gradient in m->grad
-// Round 5: two streams.  The decoder's three weight gradients (58 % of the backward pass's FLOPs, needed by nobody until the update) go to the
-// side stream: the hidden layers' behind the dX product that makes their operand, the output layer's LAST -- it needs only s, g2 and the
-// row weights, so it is what runs beside the main stream's few-row tail (dz, the latent sums, the encoder's seven launches on the batch's
-// images: 64 workgroups each on 256 CUs).  END_UPDATE (the single-GPU train step): the update is part of it -- the encoder's
-// layers on the main stream, the decoder's on the side stream behind its own slab reduction, DEFERRED: the next step's encoder forward
-// and sampling run beside the output layer's gradient, and forward_f32 joins (ev_dec) in front of the decoder forward.
-// (end: END_GRAD or END_UPDATE; this path leaves no segment of the gradient unjoined for a caller, so the split ends are END_GRAD)
-int backward_f32(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
-    const bool update = end == END_UPDATE;
-    m->f32_slab_want_step = 0;
-    if (!m->have_forward || !m->fwd_was_f32) return fail(IWAE_ERR_STATE, "backward without a float32 forward");
-    const bool two = m->cfg.n_layers == 2;
-    const int B = m->B, k = m->k, M = m->M, Mp = m->Mp, X = m->X;
-    hipStream_t st = m->stream;
-    const int b_dec1 = m->dec1[0].sub[0];
-    const KerasLayer *d1 = &m->klayers[b_dec1], *d2 = d1 + 1, *d3 = d1 + 2;
-    const int H = d1->Nout, D0 = m->D[0], Dp0 = m->Dp[0];
-    float* dl = ptr<float>(m->f32.logits);
-    const float* rw = nullptr;      // the row weight g_r, where the forward pass kept s instead of the logits (forward_f32): taken by the two consumers
-    if (m->f32_keeps_s) rw = ptr<float>(m->gx);
-    else launch_dl_f32(dl, X, m->f32_x, X, M, k, ptr<float>(m->gx), st);        // dl = g_r (x - sigmoid(l)), in place
-    CHK(ensure(m->f32.d2, (size_t)M * H * 4, st));
-    CHK(ensure(m->f32.d1, (size_t)M * H * 4, st));
-    CHK(ensure(m->wdec1.dz, (size_t)Mp * Dp0 * 4, st));
-    if (m->descs_dirty) CHK(build_descs(m));
-    // (the conditional prior's block sits BEHIND the decoder in the flat parameters: its gradient is made on the main stream -- one stream for that model)
-    const bool use_side = m->opt.allow_f32_side && m->side && !m->has_prior && M >= 4096 && b_dec1 + 3 == (int)m->klayers.size();
-    m->f32_side_active = use_side;
-    const int sg = use_side ? 1 : 0;
-    const bool dw_last = use_side && m->opt.f32_dw_last > 0;      // option: every decoder weight gradient behind the dX chain, beside the main stream's few-row tail
-    if (use_side) {
-        HIPCHK(hipEventRecord(m->ev_fork, st));      // s, g1, g2, z, the row weights
-        HIPCHK(hipStreamWaitEvent(m->side, m->ev_fork, 0));
-        if (m->opt.f32_wout_first && !dw_last) CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw, 1));
-    } else {
-        CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw));
-    }
-    CHK(f32_dx(m, *d3, dl, X, M, ptr<float>(m->f32.d2), H, ptr<float>(m->f32.g2), H, false, rw));
-    if (use_side && !dw_last) { HIPCHK(hipEventRecord(m->ev_fork2, st)); HIPCHK(hipStreamWaitEvent(m->side, m->ev_fork2, 0)); }
-    if (!dw_last) CHK(f32_dw(m, *d2, ptr<float>(m->f32.g1), H, ptr<float>(m->f32.d2), H, M, nullptr, sg));
-    CHK(f32_dx(m, *d2, ptr<float>(m->f32.d2), H, M, ptr<float>(m->f32.d1), H, ptr<float>(m->f32.g1), H, false));
-    if (use_side && !dw_last) { HIPCHK(hipEventRecord(m->ev_blk, st)); HIPCHK(hipStreamWaitEvent(m->side, m->ev_blk, 0)); }
-    if (!dw_last) {
-        CHK(f32_dw(m, *d1, ptr<float>(m->f32.z[0]), D0 + m->C, ptr<float>(m->f32.d1), H, M, nullptr, sg));
-        if (use_side) { HIPCHK(hipEventRecord(m->ev_join, m->side)); m->f32_z_pending = true; }      // (z is free for the next step's sampling)
-        if (use_side && !m->opt.f32_wout_first) CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw, 1));
-    }
-    CHK(f32_dx(m, *d1, ptr<float>(m->f32.d1), H, M, ptr<float>(m->wdec1.dz), Dp0, nullptr, 0, false));
-    if (dw_last) {
-        const int tmode = m->opt.f32_dw_last - 1;      // (1: tiles as picked, 2: 4-wave tiles, 3: 4-wave tiles at 3 waves per SIMD)
-        HIPCHK(hipEventRecord(m->ev_blk, st));
-        HIPCHK(hipStreamWaitEvent(m->side, m->ev_blk, 0));
-        CHK(f32_dw(m, *d1, ptr<float>(m->f32.z[0]), D0 + m->C, ptr<float>(m->f32.d1), H, M, nullptr, 1, tmode));
-        HIPCHK(hipEventRecord(m->ev_join, m->side));
-        m->f32_z_pending = true;
-        CHK(f32_dw(m, *d2, ptr<float>(m->f32.g1), H, ptr<float>(m->f32.d2), H, M, nullptr, 1, tmode));
-        CHK(f32_dw(m, *d3, ptr<float>(m->f32.g2), H, dl, X, M, rw, 1, tmode));
-    }
-    const float *dz1_b = nullptr, *dz1_c = nullptr;
-    if (two) {
-        const int b_enc2 = m->enc2[0].sub[0], b_dec2 = m->dec2[0].sub[0];
-        const int Dp1 = m->Dp[1];
-        CHK(ensure(m->dzdir, (size_t)Mp * Dp0 * 4, st));
-        CHK(ensure(m->f32.dec2.dhead, (size_t)Mp * 2 * Dp0 * 4, st));
-        CHK(ensure(m->f32.dec2.dx, (size_t)Mp * Dp1 * 4, st));
-        CHK(ensure(m->f32.enc2.dhead, (size_t)Mp * 2 * Dp1 * 4, st));
-        CHK(ensure(m->f32.enc2.dx, (size_t)Mp * Dp0 * 4, st));
-        HIPCHK(hipMemsetAsync(m->f32.dec2.dhead.p, 0, (size_t)Mp * 2 * Dp0 * 4, st));      // (pad columns are read by the weight-gradient GEMMs' strided views: keep them zero)
-        HIPCHK(hipMemsetAsync(m->f32.enc2.dhead.p, 0, (size_t)Mp * 2 * Dp1 * 4, st));
-        GaussBwdArgs g;
-        memset(&g, 0, sizeof(g));
-        g.mode = 0; g.G = ptr<float>(m->gx);
-        g.head = ptr<float>(m->wdec2.head); g.ldH = 2 * Dp0; g.D = D0; g.Dp = Dp0;
-        g.zhead = ptr<float>(m->wenc1.head); g.ldZH = 2 * Dp0; g.Dzp = Dp0;
-        g.dz_direct = ptr<float>(m->dzdir); g.ldDZ = Dp0;
-        g.eps = eps_src(m, 0); g.M = M; g.Mp = Mp; g.k = k;
-        g.DHP = nullptr; g.DHF = ptr<float>(m->f32.dec2.dhead);
-        launch_gauss_bwd(g, st);
-        CHK(f32_block_bwd(m, b_dec2, m->f32.dec2, ptr<float>(m->f32.z[1]), m->D[1], M, Dp0, ptr<float>(m->f32.dec2.dx), Dp1));
-        memset(&g, 0, sizeof(g));
-        g.mode = 1; g.G = ptr<float>(m->gx);
-        g.head = ptr<float>(m->wenc2.head); g.ldH = 2 * Dp1; g.D = m->D[1]; g.Dp = Dp1;
-        g.dz_in = ptr<float>(m->f32.dec2.dx); g.ldDZ = Dp1;
-        g.eps = eps_src(m, 1); g.M = M; g.Mp = Mp; g.k = k;
-        g.DHP = nullptr; g.DHF = ptr<float>(m->f32.enc2.dhead);
-        launch_gauss_bwd(g, st);
-        CHK(f32_block_bwd(m, b_enc2, m->f32.enc2, ptr<float>(m->f32.z[0]), D0, M, Dp1, ptr<float>(m->f32.enc2.dx), Dp0));
-        dz1_b = ptr<float>(m->dzdir); dz1_c = ptr<float>(m->f32.enc2.dx);
-    }
-    {
-        CHK(ensure(m->f32.enc1.dhead, (size_t)m->Bp * 2 * Dp0 * 4, st));
-        HIPCHK(hipMemsetAsync(m->f32.enc1.dhead.p, 0, (size_t)m->Bp * 2 * Dp0 * 4, st));
-        LatentBwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.dz = ptr<float>(m->wdec1.dz); a.dz2 = dz1_b; a.dz3 = dz1_c; a.ldDZ = Dp0;
-        a.head = ptr<float>(m->wenc1.head); a.ldH = 2 * Dp0; a.D = D0; a.Dp = Dp0;
-        a.cf = ptr<float4>(m->cf); a.eps = eps_src(m, 0);
-        a.B = B; a.Bp = m->Bp; a.k = k;
-        a.kmu = a.ksig = (objective == OBJ_VAE_ELBO_KL) ? m->beta / (float)B : 0.f;
-        a.DHP = nullptr; a.DHF = ptr<float>(m->f32.enc1.dhead);
-        if (m->has_prior) {      // gradient of the conditional prior's head, summed over the image's samples (tasks/task04.py:124-130)
-            CHK(ensure(m->f32.prior.dhead, (size_t)m->Bp * 2 * Dp0 * 4, st));
-            HIPCHK(hipMemsetAsync(m->f32.prior.dhead.p, 0, (size_t)m->Bp * 2 * Dp0 * 4, st));
-            a.prior_head = ptr<float>(m->wprior.head); a.DHF2 = ptr<float>(m->f32.prior.dhead);
-        }
-        launch_latent_bwd(a, st);
-    }
-    if (m->has_prior)
-        CHK(f32_block_bwd(m, m->prior[0].sub[0], m->f32.prior, ptr<float>(m->cond) + (size_t)m->call.cond_row0 * m->C, m->C, B, Dp0, nullptr, 0));
-    CHK(f32_block_bwd(m, m->enc1[0].sub[0], m->f32.enc1, m->C > 0 ? ptr<float>(m->f32.xcat) : m->f32_x, X + m->C, B, Dp0, nullptr, 0));
-    m->f32_slab_want = std::max(m->f32_slab_want, m->f32_slab_want_step);
-    // what the step leaves: nothing for a caller's own all-reduce (split_offset = n: the data-parallel step exchanges the whole gradient at once);
-    // with the side stream, the decoder's sums [+ update] there (join_side: whoever reads the decoder's gradient or parameters next)
-    m->left = StepLeft{use_side, false, BlockRange(), m->nparam, ON_SIDE};
-    if (!use_side) {
-        CHK(f32_flush_reductions(m));      // every row-split gradient's slabs -> the flat gradient, one launch
-        if (update) CHK(adam_impl(m, lr, 1.0f));
-        HIPCHK(hipGetLastError());
-        return IWAE_OK;
-    }
-    const int b0 = m->tb.dec1.e;
-    const float alpha = update ? adam_alpha(m, lr) : 0.0f;
-    CHK(f32_flush_reductions(m, 0));       // the slabs of the main stream's gradients (every block but the decoder)
-    if (update) adam_blocks(m, st, 0, b0, alpha, 1.0f);
-    CHK(f32_flush_reductions(m, 1));       // the decoder's, on the side stream
-    if (update) adam_blocks(m, m->side, b0, m->tb.end.e - b0, alpha, 1.0f);
-    HIPCHK(hipEventRecord(m->ev_dec, m->side));
-    HIPCHK(hipGetLastError());
-    return IWAE_OK;
-}
+namespace {      // (internal linkage again)
 
 // Data-parallel step, second half (the gradient of this rank's shard is in m->grad; backward_impl(END_GRAD_SPLIT_HELD) left the decoder's
 // segment to the side stream, its slabs not yet summed): all-reduce + Adam(grad_scale 1/N) of the decoder's layers on the SIDE stream -- they run
@@ -2062,23 +1605,6 @@ int copy_in(iwae_model* m, DevBuf& dst, const void* src, size_t bytes) {
 
 int copy_out(iwae_model* m, void* dst, const void* src, size_t bytes) {
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, m->stream));
-    return IWAE_OK;
-}
-
-// Y = epi(X W + b), W = the Keras kernel [in, out] of layer kl inside the flat float32 parameters
-int f32_fwd(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, int rows, float* Y, long ldy, int epi, bool no_ksplit) {
-    return f32_gemm(m, X, ldx, 1, m->param + kl.offW, kl.Nout, 1, Y, ldy, rows, kl.Nout, kl.Kin, m->param + kl.offb, epi, nullptr, 0, false, nullptr, nullptr, nullptr, no_ksplit);
-}
-// BasicBlock (iwae1.py:36-44) on R rows: X [R][ldx] -> h1, h2 [R][H], head [R][2Dp] (mu at 0.., sigma = exp(.)+1e-6 at Dp..)
-int f32_block_fwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, float* head, int Dp, bool no_ksplit) {
-    const KerasLayer *l1 = &m->klayers[base], *l2 = l1 + 1, *lmu = l1 + 2, *lsd = l1 + 3;
-    const int H = l1->Nout;
-    CHK(ensure(w.h1, (size_t)R * H * 4, m->stream));
-    CHK(ensure(w.h2, (size_t)R * H * 4, m->stream));
-    CHK(f32_fwd(m, *l1, X, ldx, R, ptr<float>(w.h1), H, GEMM_EPI_TANH, no_ksplit));
-    CHK(f32_fwd(m, *l2, ptr<float>(w.h1), H, R, ptr<float>(w.h2), H, GEMM_EPI_TANH, no_ksplit));
-    CHK(f32_fwd(m, *lmu, ptr<float>(w.h2), H, R, head, 2 * Dp, GEMM_EPI_NONE, no_ksplit));
-    CHK(f32_fwd(m, *lsd, ptr<float>(w.h2), H, R, head + Dp, 2 * Dp, GEMM_EPI_EXP, no_ksplit));
     return IWAE_OK;
 }
 

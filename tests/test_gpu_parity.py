@@ -701,6 +701,87 @@ def test_every_end_of_the_step_lands_on_the_same_parameters(gpu, layers, B, k, c
         assert t1 == t0, end
 
 
+def _float32_three_steps(layers, B, k, cond, opts, end, bf16_eval_between=False):
+    """Three float32 training steps on the device's own noise that end the way `end` says; the parameters, the Adam moments and the step
+    count they land on.  bf16_eval_between: a bf16 forward-only pass (eval_llh on 8 images, k = 50) between the steps."""
+    from iwae_amd.native import NativeModel
+    nh, nl = (200, 100) if layers == 1 else ([200, 100], [100, 50])
+    C, lr = (10 if cond else 0), 1e-3
+    x = O.synthetic_binarized(B, 17)
+    y = np.eye(10, dtype=np.float32)[np.random.default_rng(B + k).integers(0, 10, B)]
+    P = O.init_params(layers, nh, nl, 23, x_mean=O.synthetic_pixel_means(), **({"cond_dim": C, "cond_prior": True} if cond else {}))
+    m = NativeModel(layers, nh, nl, seed=123, cond_dim=C, cond_prior=cond, precision="fp32", options=opts)
+    m.set_params(O.flatten_params(P))
+    if end == "dp":
+        m.comm_init(NativeModel.comm_unique_id(), 1, 0)
+    for t in range(3):
+        m.set_step(t, 0)
+        if cond:
+            m.set_condition(y)
+        if end == "fused" or end == "dp":
+            m.train_step(x, k, 1.0, lr, "iwae_elbo", scalars=False)
+        elif end == "tensors":
+            m.train_step(x, k, 1.0, lr, "iwae_elbo", want=("lpxz",), scalars=False)
+        else:
+            m.forward_backward(x, k, 1.0, "iwae_elbo")
+            m.adam_step(lr)
+        if bf16_eval_between and t < 2:
+            m.set_eval_precision("bf16")
+            m.eval_llh(x[:8], k=50)
+            m.set_eval_precision("fp32")
+    out = m.get_params().copy(), m.get_adam_state()
+    if end == "dp":
+        m.comm_destroy()
+    m.close()
+    return out
+
+
+@pytest.mark.parametrize("layers,B,k,cond,opts", [
+    (1, 20, 5, False, {}),                          # 100 rows: one stream (M < 4 096), separate Bernoulli and dl passes, K-split few-row products
+    (1, 82, 50, False, {}),                         # 4 100 rows: the side stream on, s not kept (dl_f32 pass)
+    (1, 190, 50, False, {}),                        # 9 500 rows: the output layer's GEMM epilogue keeps s (gemm_f32_takes_big: 75 x 7 >= 512 tiles, from 9 400 rows on)
+    (2, 82, 50, False, {}),                         # the 2-layer chain behind the decoder
+    (1, 82, 50, True, {}),                          # conditional prior: its block sits behind the decoder in the table, so one stream
+    (1, 190, 50, False, {"f32_wout_last": 1}),      # the output layer's gradient last on the side stream
+    (1, 190, 50, False, {"f32_dw_last": 1}),        # all three behind the dX chain: tiles as picked,
+    (1, 190, 50, False, {"f32_dw_last": 2}),        # ... 4-wave tiles,
+    (1, 190, 50, False, {"f32_dw_last": 3}),        # ... at 3 waves per SIMD
+    (1, 190, 50, False, {"f32_dec_fused_train": 1}),      # the training step's decoder forward as dec_fwd_f32_kernel
+    (1, 190, 50, False, {"no_f32_multi_reduce": 1}),      # a slab reduction per gradient tensor (the host waits between them)
+])
+def test_float32_every_end_of_the_step_lands_on_the_same_parameters(gpu, layers, B, k, cond, opts):
+    """The float32 twin of the test above (plan_step_f32, backward_f32's four enqueue orders of the decoder's weight gradients): the four
+    ends of a step differ in streams, events and launches only, so three steps on the device's own noise land on bit-identical
+    parameters, Adam moments and step count.  Compared within one option set, never across: the tile modes change the order of float32
+    sums.  The row counts are the smallest that reach each branch of the float32 plan.
+
+    The {"f32_wout_last": 1} case is the one that caught a missing order: the side stream's deferred decoder update rewrites W1, which
+    the main stream's dX product of the decoder's first layer reads, and nothing but the side stream's own backlog kept it behind.  While
+    the slab buffer still grows, f32_dw makes the host wait for both streams, under f32_wout_last right in front of that product: the
+    fused end then differed from the others from the second step on in about half the runs, by rounding (max 2.4e-06), in the encoder's
+    parameters only.  backward_f32 now makes the update wait for the main stream's last launch of the step."""
+    p0, (m0, v0, t0) = _float32_three_steps(layers, B, k, cond, opts, "fused")
+    assert t0 == 3
+    for end in ("tensors", "grad_then_adam", "dp"):
+        p1, (m1, v1, t1) = _float32_three_steps(layers, B, k, cond, opts, end)
+        np.testing.assert_array_equal(p0, p1, err_msg="parameters, fused vs " + end)
+        np.testing.assert_array_equal(m0, m1, err_msg="first moments, fused vs " + end)
+        np.testing.assert_array_equal(v0, v1, err_msg="second moments, fused vs " + end)
+        assert t1 == t0, end
+
+
+def test_float32_steps_with_a_bf16_forward_between_them(gpu):
+    """A bf16 forward-only pass between float32 steps (eval_llh in bf16 precision on a float32 handle) shares the side streams and the
+    wait for ev_join with them (bf16_side_used, StepLeft::z_pending, which forward_impl consumes too): at 82 x 50 rows, side stream on,
+    parameters and moments equal the run without it, bitwise."""
+    p0, (m0, v0, t0) = _float32_three_steps(1, 82, 50, False, {}, "fused")
+    p1, (m1, v1, t1) = _float32_three_steps(1, 82, 50, False, {}, "fused", bf16_eval_between=True)
+    np.testing.assert_array_equal(p0, p1)
+    np.testing.assert_array_equal(m0, m1)
+    np.testing.assert_array_equal(v0, v1)
+    assert t0 == t1 == 3
+
+
 @pytest.mark.parametrize("B,k,obj,nh,nl,xd", [(6, 5, "iwae_elbo", 200, 100, 784), (9, 3, "vae_elbo_kl", 64, 20, 48), (170, 50, "iwae_elbo", 200, 100, 784)])
 def test_conditional_model_matches_oracle(gpu, B, k, obj, nh, nl, xd):
     """tasks/task05.py:101-168 (CIWAE): encoder on concat(x, onehot(y)), decoder on concat(z, onehot(y)); the condition
