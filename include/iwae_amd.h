@@ -419,6 +419,58 @@ typedef struct {
 int iwae_local_posterior(iwae_handle h, const float* x, int32_t N,        /* [N, x_dim], host or device, any values in [0,1] */
                          const iwae_local_options* opt, const iwae_local_outputs* out);
 
+/* Masked importance-weighted bound on log p(x_obs) and the self-normalised importance-sampling (SNIS) estimate of E[x | x_obs] (Mattei &
+ * Frellsen 2019, "MIWAE: Deep Generative Modelling and Imputation of Incomplete Data Sets"; the snis_z idea of src/iwae1.py:139 carried
+ * through the decoder; no reference counterpart).  m [N, x_dim] marks the observed pixels (non-zero), NULL = every pixel observed: the call
+ * is then the importance-weighted reconstruction.  The encoder sees xin_nj = m_nj ? x_nj : 0; (mu_n, sigma_n) are its heads
+ * (src/iwae1.py:39-42) of xin_n in the eval precision.  Image n has k draws e_s ~ N(0, I); with z_s = mu + sigma e_s, l_s = decoder(z_s)
+ * (src/iwae1.py:72-75, logits) and c = log(2 pi)/2,
+ *   lpx_s   = sum_{j: m_nj != 0} [x_nj l_sj - softplus(l_sj)]       (src/iwae1.py:105-111 restricted to the observed pixels)
+ *   log_w_s = lpx_s + sum_d (-z_sd^2/2 - c) - sum_d (-e_sd^2/2 - log sigma_d - c)
+ *   al_s    = softmax_s(log_w)              log_px[n] = LSE_s log_w - log k              ess[n] = 1 / sum_s al_s^2
+ *   xhat[n,j] = sum_s al_s sigmoid(l_sj)    for EVERY pixel j, the observed ones too (the caller puts the observed values back)
+ * log_px is the k-sample IWAE bound on log p(x_obs): the unobserved pixels are marginalised by leaving them out of log p(x|z).
+ * Unobserved pixels are SELECTED out, not multiplied out: what x holds at a pixel with m = 0 is never read into any result -- NaN or
+ * garbage there changes nothing, bitwise.  Observed x may be any value in [0,1], as in iwae_ais.
+ * Arithmetic: the row products are float32 (v_mfma_f32_16x16x4_f32) whatever iwae_set_eval_precision says, exactly as iwae_ais and
+ * iwae_local_posterior (only the heads follow it); sigma enters z as exp(log sigma), as in iwae_local_posterior.  float32: a lane's sums
+ * over the pixels of one pass of the output layer (16 ceil(n_hidden/16) pixels) and over its latent features, al_s = exp(log_w_s - max) * (float)(1 / sum), and xhat -- an image's
+ * al_s sigmoid(l_sj) added in sample order within a 64-draw chunk, then the chunks in chunk order, then clamped to 1 (a convex
+ * combination, the clamp takes the rounding of sum_s al_s).  double: a row's log_w -- the passes in pass order per lane, the three terms,
+ * then the row's 16 lanes by a butterfly -- rounded to float32 once; and per image, over its float32 log_w in sample order,
+ * sum_s exp(log_w_s - max) and its squares, hence log_px and ess.
+ * Noise: with eps == NULL the draws are exactly what iwae_debug_eps(N, k, 0) returns at the handle's step and offset (latent stream 0, row
+ * (batch_offset + n) k + s), and the call advances the noise step by one; so with mask == NULL, log_px[n] is iwae_eval_llh's per-image
+ * value at the same k and step (up to the evaluator's other float32 kernels).  With the caller's eps [k, N, D] the step is left alone.
+ * Determinism: an image's outputs depend only on the weights, the image, its mask, k and its draws -- not on N, its position, the other
+ * images or the launch chunking (option impute_rows: rows per launch, whole images) -- and repeat bitwise.  No atomics; every reduction
+ * has a fixed order.
+ * Models: the 1-layer unconditional model with n_hidden <= 208 and n_latent <= 128 (the chain kernel's limits); a 2-layer handle,
+ * cond_dim > 0 or cond_prior: IWAE_ERR_ARG.  N <= 0, k outside 1..65536, N k > 2^27, x / opt / out / log_px NULL or a wrong struct_size:
+ * IWAE_ERR_ARG before any launch, the noise step unchanged.
+ * Workspace: 4 k N bytes of log-weights and 16 N of per-image sums; with a mask 4 N x_dim for the masked input (and N x_dim for the mask's
+ * copy when it arrives on the host); with xhat, for k > 64, 4 ceil(k / 64) x_dim' bytes per image of a launch (x_dim' = x_dim rounded up to
+ * 16; at most impute_rows / 64 chunks: 26 MB at the defaults and 784 pixels); two padded copies of the decoder's weights (as iwae_ais);
+ * per output asked for on the host its own size and, with the caller's eps on the host, its copy (4 k N D bytes).
+ * x, mask, eps: host or device.  Outputs: each host or device, NULL = not wanted and never materialised (xhat == NULL: the second pass
+ * over the decoder does not run). */
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(iwae_impute_options) (24); ABI guard like iwae_local_options' */
+    int32_t k;                 /* draws per image, 1..65536 */
+    const uint8_t* mask;       /* [N, x_dim], non-zero = observed; NULL = every pixel observed */
+    const float* eps;          /* [k, N, D] the caller's N(0,1) draws (reference order), or NULL */
+} iwae_impute_options;
+typedef struct {
+    double* log_px;            /* [N]      required: LSE_s log_w - log k, the k-sample bound on log p(x_obs) */
+    float* xhat;               /* [N, X]   sum_s al_s sigmoid(l_s): every pixel, observed ones too */
+    float* ess;                /* [N]      1 / sum_s al_s^2 */
+    float* log_w;              /* [k, N] */
+    float* q_mu;               /* [N, D]   heads of the masked input */
+    float* q_sigma;            /* [N, D] */
+} iwae_impute_outputs;
+int iwae_impute(iwae_handle h, const float* x, int32_t N,                  /* [N, x_dim], host or device, observed values in [0,1] */
+                const iwae_impute_options* opt, const iwae_impute_outputs* out);
+
 /* Data pipeline on the device (main.py:59-65,117-120 + src/utils.py:26-27): the grey-level training set
  * stays resident in HBM as uint8 [n, x_dim]; every epoch gets a visiting order (tf.data shuffle) and a
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),
@@ -443,7 +495,7 @@ int iwae_train_step_dataset(iwae_handle h, int32_t start, int32_t B, int32_t k, 
  * step (an event record costs a few us of stream bubble, so bench.py samples rather than timing every launch); 0 switches
  * it off.  name: "decoder_fwd" (whole decoder forward + log-likelihood), "out_bwd" (output-layer backward), "decoder_bwd" (the decoder's whole dX chain where it is one launch), "wgrad_out",
  * "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent" (the decoder's other backward kernels), "latent_bwd",
- * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel).  A kernel a configuration does not launch reports 0 launches. */
+ * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel), "impute" (likewise both passes of iwae_impute's impute_rows_kernel).  A kernel a configuration does not launch reports 0 launches. */
 int iwae_enable_timing(iwae_handle h, int32_t enable);
 int iwae_kernel_time(iwae_handle h, const char* name, double* avg_us, int64_t* launches);
 

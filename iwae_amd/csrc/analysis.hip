@@ -1,5 +1,5 @@
-// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior, iwae_ais and iwae_local_posterior: the analyses that start from the
-// encoder heads of N images (host code; kernels in the five *_kernels.hip).  Each reads in five parts: argument checks, eval_begin, its own buffers and launches, its own copy-outs, eval_end.
+// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior, iwae_ais, iwae_local_posterior and iwae_impute: the analyses that start
+// from the encoder heads of N images (host code; kernels in the six *_kernels.hip).  Each reads in five parts: argument checks, eval_begin, its own buffers and launches, its own copy-outs, eval_end.
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -85,6 +85,13 @@ int dump_eps(iwae_model* m, int N, int S, int D, DevBuf& ws) {
 // measurable (0.207 s in the kernel against 0.205 s), so nothing is gained by going lower and nothing by going higher.
 #define LOCAL_T_CHUNK_DEFAULT 32
 #define LOCAL_PASSES_MAX (1 << 24)      // T and E each: T + E and the step-size table stay far inside int and host memory
+
+// Rows (images x draws, whole images) per launch of impute_rows_kernel (option impute_rows).  Measured at the timing workload (reference dims,
+// 50 % mask; profiles/impute_time.txt): a launch of 500 000 rows (N = 10 000, k = 50) takes 8.26 ms, one of 520 000 (104 images at k = 5 000)
+// 6.65 ms, each the mean of passes (a) and (c) -- well under the 50 ms a launch may hold a shared machine -- and the 194 launches
+// (97 per pass) of the N = 10 000, k = 5 000 call cost nothing measurable (1.290 s in the kernel of 1.297 s wall), so nothing is gained by going higher.
+#define IMPUTE_ROWS_DEFAULT (1 << 19)
+#define IMPUTE_K_MAX 65536
 
 // The decoder's weights in both orientations, padded to multiples of 16 (src/iwae1.py:72-75; Keras kernels [in][out]), into m->ais.wpad
 struct DecPad { const float *W1, *W1T, *W2, *W2T, *W3, *W3T, *b1, *b2, *b3; };
@@ -624,6 +631,97 @@ int iwae_local_posterior(iwae_handle m, const float* x, int32_t N, const iwae_lo
     if (logwd) CHK(finish_out(m, out->log_w, logwd, (size_t)E * S * N * 4));
     CHK(eval_end(c));
     if (!o->eps) m->noise_step += (uint32_t)(T + E);
+    return IWAE_OK;
+}
+
+// Masked importance-weighted bound on log p(x_obs) and the SNIS estimate of E[x | x_obs] (Mattei & Frellsen 2019): DESIGN.md section 17
+int iwae_impute(iwae_handle m, const float* x, int32_t N, const iwae_impute_options* o, const iwae_impute_outputs* out) {
+    if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "impute: need x, options and outputs");
+    if (o->struct_size != sizeof(iwae_impute_options)) return fail(IWAE_ERR_ARG, "impute: iwae_impute_options.struct_size must be sizeof(iwae_impute_options) = " + std::to_string(sizeof(iwae_impute_options)));
+    if (!out->log_px) return fail(IWAE_ERR_ARG, "impute: log_px is required");
+    if (N <= 0 || o->k < 1 || o->k > IMPUTE_K_MAX) return fail(IWAE_ERR_ARG, "impute: needs N > 0 and 1 <= k <= " + std::to_string(IMPUTE_K_MAX));
+    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "impute: only the 1-layer model");
+    if (m->C != 0 || m->has_prior) return fail(IWAE_ERR_ARG, "impute: only the unconditional model (cond_dim = 0, no learned prior)");
+    if ((int64_t)N * o->k > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "impute: too large (N * k > 2^27 rows)");
+    const int D = m->D[0], H = m->H[0], X = m->X, Dp = round_up(D, 16), Hp = round_up(H, 16), Xp = round_up(X, 16), Dh = m->Dp[0];
+    if (Hp > 16 * AIS_NT || Dp > 16 * AIS_DT) return fail(IWAE_ERR_ARG, "impute: needs n_hidden <= " + std::to_string(16 * AIS_NT) + " and n_latent <= " + std::to_string(16 * AIS_DT));
+    const int S = o->k;
+    EvalCall c;
+    CHK(eval_begin(m, x, N, c));
+    hipStream_t st = c.st;
+    iwae_model::ImputeWs& w = m->imp;
+    // ---- the masked input xin = m ? x : 0 into the call's own buffer: what the encoder and the rows read from here on
+    const uint8_t* maskd = nullptr;
+    if (o->mask) {
+        CHK(staged_in(m, o->mask, w.mask, (size_t)N * X, &maskd));
+        CHK(ensure(w.xin, (size_t)N * X * 4, st));
+        launch_impute_mask(c.xd, maskd, (long)N * X, ptr<float>(w.xin), st);
+        HIPCHK(hipGetLastError());
+        c.xd = ptr<float>(w.xin);
+    }
+    // ---- encoder heads mu, sigma of the masked input (src/iwae1.py:39-42), in the eval precision
+    CHK(eval_heads(c, N));
+    CHK(eval_copy_heads(c, N, out->q_mu, out->q_sigma));
+    ImputeArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    {
+        DecPad p;
+        CHK(pad_decoder(m, st, Dp, Hp, Xp, p));
+        ia.W1 = p.W1; ia.W2 = p.W2; ia.W3 = p.W3; ia.b1 = p.b1; ia.b2 = p.b2; ia.b3 = p.b3;
+    }
+    const float* epsd = nullptr;
+    if (o->eps) CHK(staged_in(m, o->eps, w.eps, (size_t)S * N * D * 4, &epsd));
+    float *logwd = nullptr, *xhatd = nullptr;
+    CHK(staged_out(m, out->log_w, w.logw, (size_t)S * N * 4, &logwd));      // (always computed: passes (b) and (c) read it)
+    if (out->xhat) CHK(staged_out(m, out->xhat, w.xhat, (size_t)N * X * 4, &xhatd));
+    CHK(ensure(w.wstat, (size_t)N * 8, st));
+    CHK(ensure(w.lpx, (size_t)N * 8, st));
+    if (out->ess) CHK(ensure(w.ess, (size_t)N * 4, st));
+    // ---- launches of whole images, at most `cap` rows each
+    const int cap = m->opt.impute_rows > 0 ? m->opt.impute_rows : IMPUTE_ROWS_DEFAULT;
+    const int nbmax = std::min((int)N, std::max(1, cap / S)), nchunk = S > 64 ? (S + 63) / 64 : 1;
+    if (xhatd && nchunk > 1) CHK(ensure(w.part, (size_t)nbmax * nchunk * Xp * 4, st));
+    ia.D = D; ia.H = H; ia.X = X; ia.Dp = Dp; ia.Hp = Hp; ia.Xp = Xp;
+    ia.x = c.xd; ia.mask = maskd; ia.head = c.head; ia.ldh = c.ldh; ia.soff = Dh;
+    ia.N = N; ia.S = S; ia.ipw = S <= 64 ? 64 / S : 1; ia.nchunk = nchunk;
+    ia.eps = epsd; ia.seed = m->cfg.seed; ia.row_offset = (uint64_t)m->batch_offset * (uint64_t)S; ia.step = m->noise_step;
+    ia.log_w = logwd; ia.wstat = ptr<float2>(w.wstat); ia.xhat = xhatd; ia.part = nchunk > 1 ? ptr<float>(w.part) : nullptr;
+    m->time_this = m->timing > 0;
+    // pass (a): log_w of every row
+    for (int i0 = 0; i0 < N; i0 += nbmax) {
+        ia.img0 = i0; ia.nimg = std::min(nbmax, (int)N - i0);
+        ScopedTimer tm(m, T_IMPUTE, st);
+        launch_impute_rows(ia, false, st);
+        HIPCHK(hipGetLastError());
+    }
+    // pass (b): per image the maximum, the sum, log_px and ess, in sample order
+    ImputeStatsArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.log_w = logwd; sa.N = N; sa.S = S; sa.log_px = ptr<double>(w.lpx); sa.ess = out->ess ? ptr<float>(w.ess) : nullptr; sa.wstat = ptr<float2>(w.wstat);
+    launch_impute_stats(sa, st);
+    HIPCHK(hipGetLastError());
+    // pass (c): the decoder once more with the weights final (only when xhat is wanted)
+    for (int i0 = 0; xhatd && i0 < N; i0 += nbmax) {
+        ia.img0 = i0; ia.nimg = std::min(nbmax, (int)N - i0);
+        {
+            ScopedTimer tm(m, T_IMPUTE, st);
+            launch_impute_rows(ia, true, st);
+        }
+        if (nchunk > 1) {
+            ImputeMergeArgs ma;
+            memset(&ma, 0, sizeof(ma));
+            ma.part = ia.part; ma.nimg = ia.nimg; ma.nchunk = nchunk; ma.X = X; ma.Xp = Xp; ma.img0 = i0; ma.xhat = xhatd;
+            launch_impute_merge(ma, st);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    m->time_this = false;
+    CHK(copy_out(m, out->log_px, w.lpx.p, (size_t)N * 8));
+    if (out->ess) CHK(copy_out(m, out->ess, w.ess.p, (size_t)N * 4));
+    CHK(finish_out(m, out->log_w, logwd, (size_t)S * N * 4));
+    CHK(finish_out(m, out->xhat, xhatd, (size_t)N * X * 4));
+    CHK(eval_end(c));
+    if (!o->eps) m->noise_step += 1;
     return IWAE_OK;
 }
 

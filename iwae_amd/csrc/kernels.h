@@ -608,4 +608,37 @@ void launch_local_init(const LocalInitArgs& a, hipStream_t st);
 void launch_local_q(const LocalArgs& a, hipStream_t st);
 void launch_local_finish(const LocalFinishArgs& a, hipStream_t st);
 
+// ---- masked importance-weighted bound and SNIS imputation (impute_kernels.hip; iwae_impute): S draws per image, float32, local_q_kernel's
+// blocking and the forward half of its row evaluation.  Rows image-major; S <= 64: a workgroup owns ipw = 64 / S whole images (nchunk = 1),
+// S > 64: chunk c of nchunk = ceil(S / 64) of one image.  A launch holds the whole images [img0, img0 + nimg).
+struct ImputeArgs {                   // impute_rows_kernel<false>: pass (a), writes log_w; <true>: pass (c), reads log_w and wstat, writes xhat / part
+    const float *W1, *W2, *W3, *b1, *b2, *b3;      // padded to multiples of 16 (ais_pad_kernel): W [in][out]
+    int D, H, X, Dp, Hp, Xp;
+    const float* x;                   // [N][X]: the masked input m ? x : 0 (the caller's x where mask is null)
+    const uint8_t* mask;              // [N][X], non-zero = observed, or null: every pixel observed
+    const float* head; int ldh, soff; // mu at head[n ldh + d], sigma soff further
+    int N, S, ipw, nchunk;            // N: the call's images (the stride of eps and log_w)
+    int img0, nimg;                   // this launch's images
+    const float* eps;                 // the caller's draws [S][N][D] or null: Philox stream 0 at `step`, row row_offset + n S + s
+    uint64_t seed, row_offset; uint32_t step;
+    float* log_w;                     // [S][N]
+    const float2* wstat;              // [N]: (max_s log_w, 1 / sum_s exp(log_w - max)) of impute_stats_kernel
+    float* xhat;                      // [N][X] (nchunk == 1)
+    float* part;                      // [nimg][nchunk][Xp] (nchunk > 1): the chunks' sums, for impute_merge_kernel
+};
+struct ImputeStatsArgs {              // impute_stats_kernel: per image, in sample order: log_px = LSE_s log_w - log S and ess (double), wstat
+    const float* log_w; int N, S;
+    double* log_px; float* ess;       // ess: null = not wanted
+    float2* wstat;
+};
+struct ImputeMergeArgs {              // impute_merge_kernel: xhat[img0 + i] = min(1, sum_c part[i][c]) in chunk order
+    const float* part; int nimg, nchunk, X, Xp, img0;
+    float* xhat;
+};
+size_t impute_lds_bytes(int Dp, int Hp);
+void launch_impute_mask(const float* x, const uint8_t* mask, long n, float* xin, hipStream_t st);      // xin = mask ? x : 0
+void launch_impute_rows(const ImputeArgs& a, bool xhat, hipStream_t st);
+void launch_impute_stats(const ImputeStatsArgs& a, hipStream_t st);
+void launch_impute_merge(const ImputeMergeArgs& a, hipStream_t st);
+
 }  // namespace iwae

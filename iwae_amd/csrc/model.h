@@ -54,7 +54,7 @@ template <class Ws> void free_all(Ws& ws) {
 }
 
 // kernels iwae_enable_timing brackets with HIP events (on the stream each is launched on); names: iwae_kernel_time
-enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_COUNT };
+enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_IMPUTE, T_COUNT };
 
 // What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
 // images and samples in chunks and needs log_w only.
@@ -144,6 +144,7 @@ struct StepOptions {
     int grid_chunk = 0;                       // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT)
     int ais_t_chunk = 0;                      // iwae_ais: transitions per launch of ais_chain_kernel (option ais_t_chunk; 0 = AIS_T_CHUNK_DEFAULT)
     int local_t_chunk = 0;                    // iwae_local_posterior: passes per launch of local_q_kernel (option local_t_chunk; 0 = LOCAL_T_CHUNK_DEFAULT)
+    int impute_rows = 0;                      // iwae_impute: rows (images x draws, whole images) per launch of impute_rows_kernel (option impute_rows; 0 = IMPUTE_ROWS_DEFAULT)
 };
 
 // The kernels and streams of one bf16 step.  plan_step decides all of it from shapes and options before forward_impl launches or allocates
@@ -311,6 +312,9 @@ struct iwae_model {
     // iwae_local_posterior's buffers (the padded weights are ais.wpad): the per-image state and double sums, Adam's step sizes, the
     // caller's start and noise when they arrive on the host, and the outputs
     struct LocalWs { DevBuf st, acc, alpha, mu0, sg0, eps, qmu, qsg, mu, sg, elbo, iwae, bound, grad, logw; } loc;
+    // iwae_impute's buffers (the padded weights are ais.wpad): the masked input, the caller's mask and noise when they arrive on the host,
+    // the log-weights, per image (max, 1 / sum), the chunk sums of xhat (more than 64 draws per image) and the outputs
+    struct ImputeWs { DevBuf xin, mask, eps, logw, wstat, part, lpx, ess, xhat; } imp;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
     ncclComm_t comm_main = nullptr, comm_side = nullptr;

@@ -22,6 +22,8 @@ static_assert(sizeof(iwae_ais_options) == 72 && offsetof(iwae_ais_options, betas
               offsetof(iwae_ais_options, unif) == 64 && sizeof(iwae_ais_outputs) == 10 * sizeof(void*), "iwae_ais_options / iwae_ais_outputs layout is part of the ABI (iwae_amd/_capi.py)");
 static_assert(sizeof(iwae_local_options) == 64 && offsetof(iwae_local_options, objective) == 16 && offsetof(iwae_local_options, lr) == 20 && offsetof(iwae_local_options, epsilon) == 32 &&
               offsetof(iwae_local_options, mu0) == 40 && offsetof(iwae_local_options, eps) == 56 && sizeof(iwae_local_outputs) == 9 * sizeof(void*), "iwae_local_options / iwae_local_outputs layout is part of the ABI (iwae_amd/_capi.py)");
+static_assert(sizeof(iwae_impute_options) == 24 && offsetof(iwae_impute_options, k) == 4 && offsetof(iwae_impute_options, mask) == 8 && offsetof(iwae_impute_options, eps) == 16 &&
+              sizeof(iwae_impute_outputs) == 6 * sizeof(void*), "iwae_impute_options / iwae_impute_outputs layout is part of the ABI (iwae_amd/_capi.py)");
 
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -68,7 +70,8 @@ static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgra
                                                  "latent_bwd", "encoder_fwd", "reduce_adam", "decoder_bwd",
                                                  "allreduce_enc", "allreduce_dec",       // (the data-parallel step's two ncclAllReduce calls, each on its own stream)
                                                  "ais_chain",                            // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
-                                                 "local_q"};                             // (iwae_local_posterior: likewise local_q_kernel)
+                                                 "local_q",                              // (iwae_local_posterior: likewise local_q_kernel)
+                                                 "impute"};                              // (iwae_impute: likewise both passes of impute_rows_kernel)
 
 namespace {      // (closed and reopened around each helper that model.h declares for step_f32.hip; what is added in between stays internal)
 
@@ -1744,6 +1747,7 @@ void iwae_destroy(iwae_handle m) {
     free_all(m->agg);
     free_all(m->ais);
     free_all(m->loc);
+    free_all(m->imp);
     for (BlockWs* w : {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior}) free_all(*w);
     free_all(m->wdec1);
     free_all(m->f32);
@@ -1990,6 +1994,7 @@ int iwae_set_option(iwae_handle m, const char* name, int64_t value) {
     else if (n == "grid_chunk") m->opt.grid_chunk = iv > 0 ? std::max(16, iv) : 0;      // iwae_grid_posterior: grid points per chunk (0: the default)
     else if (n == "ais_t_chunk") m->opt.ais_t_chunk = iv > 0 ? iv : 0;                 // iwae_ais: transitions per launch (0: the default)
     else if (n == "local_t_chunk") m->opt.local_t_chunk = iv > 0 ? iv : 0;             // iwae_local_posterior: passes per launch (0: the default)
+    else if (n == "impute_rows") m->opt.impute_rows = iv > 0 ? iv : 0;                 // iwae_impute: rows per launch, whole images (0: the default)
     else if (n == "eval_rows") m->opt.eval_rows = iv > 0 ? std::max(64, iv) : 0;       // data rows per evaluator launch
     else if (n == "no_bern_pipe") m->opt.allow_bern_pipe = !on;           // the Bernoulli forward on dense_kernel<EPI_BERN>
     else if (n == "no_block_fused") m->opt.allow_block_fused = !on;       // a BasicBlock on few rows as three dense_kernel launches

@@ -138,3 +138,23 @@ class IWAE(BaseIWAE):
         out["log_px_se"] = utils.log_mean_exp_se(a["log_w"])
         out.update(ais=a, amortized=amort, local=local)
         return out
+
+    # ---- missing-pixel imputation and importance-weighted reconstruction (Mattei & Frellsen 2019, MIWAE)
+    def impute(self, X, mask, n_samples=50, **kwargs):
+        """Given the pixels of X that mask marks as observed (non-zero; None: all of them): the n_samples-draw bound log_px on
+        log p(x_obs) per image and the self-normalised importance-sampling estimate of E[x | x_obs] (iwae_impute; kwargs: noise).  Returns
+        {"xhat": the estimate with the observed pixels put back exactly as given, "xhat_raw": the estimate at every pixel, "log_px"
+        (float64), "ess"} -- what X holds at an unobserved pixel is never read."""
+        if self._net.cond_dim:
+            raise NotImplementedError("imputation covers the unconditional 1-layer model only")
+        X = np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim)
+        r = self._net.impute(X, mask=mask, n_samples=n_samples, outputs=("log_px", "xhat", "ess"), **kwargs)
+        filled = X.copy() if mask is None else np.where(np.asarray(mask).reshape(X.shape) != 0, X, r["xhat"])
+        return {"xhat": filled, "xhat_raw": r["xhat"], "log_px": r["log_px"], "ess": r["ess"]}
+
+    def reconstruct(self, X, n_samples=50, **kwargs):
+        """The importance-weighted reconstruction of X: impute() with every pixel observed, whose xhat_raw is sum_s al_s sigmoid(l_s).
+        Returns impute()'s dict with "xhat" = that reconstruction."""
+        r = self.impute(X, None, n_samples=n_samples, **kwargs)
+        r["xhat"] = r["xhat_raw"]
+        return r

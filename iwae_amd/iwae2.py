@@ -53,3 +53,9 @@ class IWAE(BaseIWAE):
 
     def inference_gaps(self, X, **kwargs):
         self.local_posterior(None)
+
+    def impute(self, X, mask, n_samples=50, **kwargs):
+        raise ValueError("imputation covers the 1-layer model only: the 2-layer proposal q(z2|z1) q(z1|x) needs its own weights")
+
+    def reconstruct(self, X, n_samples=50, **kwargs):
+        self.impute(None, None)

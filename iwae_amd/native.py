@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import AIS_INITS, LOCAL_OBJECTIVES, OBJECTIVES, PRECISIONS, AisOptions, AisOutputs, Config, LocalOptions, LocalOutputs, Scalars, Tensors, check
+from ._capi import (AIS_INITS, IMPUTE_OUTPUT_FIELDS, LOCAL_OBJECTIVES, OBJECTIVES, PRECISIONS, AisOptions, AisOutputs, Config, ImputeOptions, ImputeOutputs,
+                    LocalOptions, LocalOutputs, Scalars, Tensors, check)
 
 _SCALAR_NAMES = ("vae_elbo", "vae_elbo_kl", "iwae_elbo", "iwae_eq14", "inference_loss",
                  "mean_lpxz", "mean_lpz", "mean_lqzx", "mean_kl")
@@ -454,6 +455,42 @@ class NativeModel:
         for name, arr in res.items():
             setattr(outs, name, arr.ctypes.data)
         check(self.lib.iwae_local_posterior(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
+        return res
+
+    def impute(self, x, mask=None, n_samples=50, noise=None, outputs=IMPUTE_OUTPUT_FIELDS):
+        """iwae_impute: the n_samples-draw importance-weighted bound on log p(x_obs) of the images x [N, x_dim] whose observed pixels mask
+        [N, x_dim] marks (non-zero; None: every pixel observed), and the self-normalised estimate xhat = sum_s al_s sigmoid(l_s) of
+        E[x | x_obs] at every pixel.  What x holds at an unobserved pixel is never read.  noise [n_samples, N, D] replaces the device
+        generator (and leaves the noise step alone).  outputs: which of log_px [N] (float64; always), xhat [N, x_dim], ess [N], log_w
+        [n_samples, N], q_mu, q_sigma [N, D] to return (xhat left out: the second decoder pass does not run).  Returns a dict."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        N, D, S = x.shape[0], self.n_latent[0], int(n_samples)
+        unknown = set(outputs) - set(IMPUTE_OUTPUT_FIELDS)
+        if unknown:
+            raise ValueError("impute: unknown outputs %s (known: %s)" % (sorted(unknown), ", ".join(IMPUTE_OUTPUT_FIELDS)))
+        o = ImputeOptions()
+        o.k = S
+        keep = []
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1, self.x_dim)
+            if mk.shape != x.shape:
+                raise ValueError("impute: mask must be [N, x_dim] = %s, got %s" % (x.shape, mk.shape))
+            o.mask = mk.ctypes.data
+            keep.append(mk)
+        n0, s0 = max(N, 0), max(S, 0)      # (bad counts: the library rejects them; nothing is written)
+        if noise is not None:
+            e = _f32(noise)
+            if e.shape != (s0, n0, D):
+                raise ValueError("impute: noise must be [n_samples, N, %d] = %s, got %s" % (D, (s0, n0, D), e.shape))
+            o.eps = e.ctypes.data
+            keep.append(e)
+        shapes = {"log_px": ((n0,), np.float64), "xhat": ((n0, self.x_dim), np.float32), "ess": ((n0,), np.float32),
+                  "log_w": ((s0, n0), np.float32), "q_mu": ((n0, D), np.float32), "q_sigma": ((n0, D), np.float32)}
+        res = {name: np.empty(*shapes[name]) for name in IMPUTE_OUTPUT_FIELDS if name == "log_px" or name in outputs}
+        outs = ImputeOutputs()
+        for name, arr in res.items():
+            setattr(outs, name, arr.ctypes.data)
+        check(self.lib.iwae_impute(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
         return res
 
     def grad_moments(self, x, k, draws, beta=1.0, objective="iwae_elbo"):

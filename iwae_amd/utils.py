@@ -173,3 +173,11 @@ def inference_gap_split(log_px, elbo_amortized, elbo_local):
     """Cremer, Li & Duvenaud (2018): log p(x) - ELBO[q_enc] = (log p(x) - ELBO[q*]) + (ELBO[q*] - ELBO[q_enc]), per image in float64."""
     lp, ea, el = (np.asarray(v, dtype=np.float64) for v in (log_px, elbo_amortized, elbo_local))
     return {"log_px": lp, "elbo_amortized": ea, "elbo_local": el, "approximation_gap": lp - el, "amortization_gap": el - ea}
+
+
+def mcar_mask(shape, rate, seed=0):
+    """A missing-completely-at-random mask for iwae_impute: uint8 array of `shape`, 1 = observed, each entry unobserved with probability
+    `rate` independently (seeded host generator)."""
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError("mcar_mask: rate must lie in [0, 1], got %r" % (rate,))
+    return (np.random.default_rng(seed).random(shape) >= rate).astype(np.uint8)
