@@ -11,63 +11,11 @@
 #include <type_traits>
 #include "kernels.h"
 #include "layout.h"
+#include "device_helpers.h"
 
 namespace iwae {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 abf16x8_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 abf16x2_t;
-typedef __attribute__((ext_vector_type(4))) float af32x4;
-
-// ---- the device helpers chain2_fwd_kernel's arithmetic rests on (kernels.hip), restated here so the rounding points match it
-#define ALOG2E_F 1.4426950408889634f
-__device__ __forceinline__ uint32_t apack2(float a, float b) {
-    abf16x2_t v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;   // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ af32x4 amfma(const uint4& a, const uint4& b, af32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(abf16x8_t, a), __builtin_bit_cast(abf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ float atanh_fast(float x) {
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x * (2.0f * ALOG2E_F)) + 1.0f);
-}
-__device__ __forceinline__ uint32_t alds_addr_of(const char* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
-// async global -> LDS copy, 16 B per lane at M0 + lane*16 (kernels.hip, glds16: inline asm so the DMA is not drained per k-step)
-__device__ __forceinline__ void aglds16(const char* g, uint32_t lds_wave_base) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(lds_wave_base) : "memory");
-}
-__device__ __forceinline__ void await_all_vmem() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-// Philox4x32-10 + Box-Muller, counter = (row_lo, row_hi, (stream<<24)|d4, step), key = seed: kernels.hip's normal4, bit for bit
-__device__ __forceinline__ void anormal4(uint64_t grow, uint32_t d4, uint32_t stream, uint32_t step, uint64_t seed, float n[4]) {
-    uint32_t c0 = (uint32_t)grow, c1 = (uint32_t)(grow >> 32), c2 = (stream << 24) | d4, c3 = step;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        unsigned long long p0, p1;
-        asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p0) : "v"(c0), "v"(0xD2511F53u) : "vcc");
-        asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p1) : "v"(c2), "v"(0xCD9E8D57u) : "vcc");
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const float s24 = 5.9604644775390625e-08f;   // 2^-24
-    const float u0 = ((float)(c0 >> 8) + 0.5f) * s24, u1 = ((float)(c1 >> 8) + 0.5f) * s24;
-    const float u2 = ((float)(c2 >> 8) + 0.5f) * s24, u3 = ((float)(c3 >> 8) + 0.5f) * s24;
-    const float ra = __builtin_amdgcn_sqrtf(-2.0f * __logf(u0)), rb = __builtin_amdgcn_sqrtf(-2.0f * __logf(u2));
-    n[0] = ra * __builtin_amdgcn_cosf(u1); n[1] = ra * __builtin_amdgcn_sinf(u1);
-    n[2] = rb * __builtin_amdgcn_cosf(u3); n[3] = rb * __builtin_amdgcn_sinf(u3);
-}
 // 4 draws for features 4*d4 .. +3 of sample s of image b: the user's [k][B][D] draws or Philox keyed as iwae_eval_llh keys them
 // (k_total set: row = row_offset + b * k_total + s_off + s)
 __device__ __forceinline__ void aeps4(const EpsSrc& e, int b, int s, int d4, int D, float n[4]) {
@@ -76,7 +24,7 @@ __device__ __forceinline__ void aeps4(const EpsSrc& e, int b, int s, int d4, int
 #pragma unroll
         for (int i = 0; i < 4; ++i) n[i] = (4 * d4 + i < D) ? p[i] : 0.0f;
     } else {
-        anormal4(e.row_offset + (uint64_t)b * (uint64_t)e.k_total + (uint64_t)(e.s_off + s), (uint32_t)d4, e.stream, e.step, e.seed, n);
+        normal4(e.row_offset + (uint64_t)b * (uint64_t)e.k_total + (uint64_t)(e.s_off + s), (uint32_t)d4, e.stream, e.step, e.seed, n);
     }
 }
 
@@ -118,7 +66,7 @@ __global__ __launch_bounds__(512, 4) void act_chain_kernel(ActChainArgs a) {
         for (int idx = 0; idx < NIDX; ++idx) {
             const int p = wave + NWV * idx;
             if (p < npc)
-                aglds16(src + (size_t)p * 1024 + lane * 16, (uint32_t)__builtin_amdgcn_readfirstlane((int)(alds_addr_of(smem + buf * UNIT) + (uint32_t)p * 1024u)));
+                glds16(src + (size_t)p * 1024 + lane * 16, (uint32_t)__builtin_amdgcn_readfirstlane((int)(lds_addr_of(smem + buf * UNIT) + (uint32_t)p * 1024u)));
         }
     };
     dma_unit(0, 0);
@@ -142,14 +90,14 @@ __global__ __launch_bounds__(512, 4) void act_chain_kernel(ActChainArgs a) {
                     z8[4 * h + i] = in ? fmaf(sgv[i], e[i], muv[i]) : 0.0f;
                 }
             }
-            zf[ks] = make_uint4(apack2(z8[0], z8[1]), apack2(z8[2], z8[3]), apack2(z8[4], z8[5]), apack2(z8[6], z8[7]));
+            zf[ks] = make_uint4(pack2(z8[0], z8[1]), pack2(z8[2], z8[3]), pack2(z8[4], z8[5]), pack2(z8[6], z8[7]));
         }
     }
     int u = 0;
-    auto unit_mfma = [&](auto kt_tag, const uint4* bin, af32x4 (&acc)[4]) {
+    auto unit_mfma = [&](auto kt_tag, const uint4* bin, f32x4 (&acc)[4]) {
         constexpr int KTin = decltype(kt_tag)::value;
         const int buf = u & 1;
-        await_all_vmem();
+        wait_all_vmem();
         __syncthreads();
         if (u + 1 < NUNITS) dma_unit(u + 1, buf ^ 1);
         const char* lb = smem + buf * UNIT + a_off;
@@ -157,14 +105,14 @@ __global__ __launch_bounds__(512, 4) void act_chain_kernel(ActChainArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const float4 c = *(const float4*)(lbias + 64 * t);
-            acc[t] = (af32x4){c.x, c.y, c.z, c.w};
+            acc[t] = (f32x4){c.x, c.y, c.z, c.w};
         }
         uint4 av[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) av[i] = *(const uint4*)(lb + i * 1024);
 #pragma unroll
         for (int i = 0; i < KTin * 4; ++i) {
-            acc[i & 3] = amfma(av[i & 3], bin[i >> 2], acc[i & 3]);
+            acc[i & 3] = mfma16(av[i & 3], bin[i >> 2], acc[i & 3]);
             if (i + 4 < KTin * 4) av[i & 3] = *(const uint4*)(lb + (i + 4) * 1024);
         }
         ++u;
@@ -172,7 +120,7 @@ __global__ __launch_bounds__(512, 4) void act_chain_kernel(ActChainArgs a) {
     auto tanh_layer = [&](auto kt_tag, const uint4* bin, uint4 (&bout)[KTH]) {
 #pragma unroll
         for (int mg = 0; mg < MGH; ++mg) {
-            af32x4 acc[4];
+            f32x4 acc[4];
             unit_mfma(kt_tag, bin, acc);
 #pragma unroll
             for (int p2 = 0; p2 < 2; ++p2) {
@@ -180,8 +128,8 @@ __global__ __launch_bounds__(512, 4) void act_chain_kernel(ActChainArgs a) {
                 if (kso < KTH) {
                     float v[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = atanh_fast(acc[2 * p2 + (j >> 2)][j & 3]);
-                    bout[kso] = make_uint4(apack2(v[0], v[1]), apack2(v[2], v[3]), apack2(v[4], v[5]), apack2(v[6], v[7]));
+                    for (int j = 0; j < 8; ++j) v[j] = tanh_fast(acc[2 * p2 + (j >> 2)][j & 3]);
+                    bout[kso] = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
                 }
             }
         }
@@ -191,7 +139,7 @@ __global__ __launch_bounds__(512, 4) void act_chain_kernel(ActChainArgs a) {
     tanh_layer(std::integral_constant<int, KTH>{}, h1f, h2f);
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        af32x4 mu2[4];
+        f32x4 mu2[4];
         unit_mfma(std::integral_constant<int, KTH>{}, h2f, mu2);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -232,18 +180,6 @@ __global__ __launch_bounds__(256) void act_partial_kernel(ActPartialArgs a) {
 // fixed pairwise tree.  Pass 1: the per-image means (block partials folded in order, in double, / kdiv) -> post_mean and their sum;
 // pass 2: the centred second moment about the data mean.  Both orders depend on N only.
 constexpr int ACT_STAT_THREADS = 256;
-__device__ __forceinline__ double act_tree(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = ACT_STAT_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 __global__ __launch_bounds__(ACT_STAT_THREADS) void act_stats_kernel(ActStatsArgs a) {
     __shared__ double sh[ACT_STAT_THREADS];
     const int uu = blockIdx.x;
@@ -259,13 +195,13 @@ __global__ __launch_bounds__(ACT_STAT_THREADS) void act_stats_kernel(ActStatsArg
         a.post_mean[(size_t)i * a.ldpm + a.col + uu] = (float)v;
         s1 += v;
     }
-    const double mean = act_tree(s1, sh) / (double)a.N;
+    const double mean = tree_sum_256(s1, sh) / (double)a.N;
     double s2 = 0.0;
     for (int i = threadIdx.x; i < a.N; i += ACT_STAT_THREADS) {
         const double d = image_mean(i) - mean;
         s2 += d * d;
     }
-    const double var = act_tree(s2, sh) / (double)a.N;
+    const double var = tree_sum_256(s2, sh) / (double)a.N;
     if (threadIdx.x == 0) { a.data_mean[a.col + uu] = mean; a.activity[a.col + uu] = var; }
 }
 

@@ -14,6 +14,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "device_helpers.h"
 
 namespace iwae {
 namespace {
@@ -172,19 +173,6 @@ __global__ __launch_bounds__(AGG_THREADS) void agg_untranspose_kernel(const floa
     dst[idx] = src[(size_t)d * SN + i];
 }
 
-__device__ __forceinline__ double agg_tree(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = AGG_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // agg_reduce_kernel: block d < D sums over the samples of unit d, in double: lq_own - log_qzd, log_qzd - lp, lq_own - lp, lq_own, log_qzd
 // (lq_own = -eps^2/2 - log sigma - c and lp = -z^2/2 - c, z = mu + sigma eps, evaluated in double from the float32 heads and draws);
 // block D sums log_qz.  Thread t takes samples t, t + 256, ...; the 256 thread sums are folded by a fixed tree: the order depends on (N, S).
@@ -208,7 +196,7 @@ __global__ __launch_bounds__(AGG_THREADS) void agg_reduce_kernel(AggReduceArgs a
     }
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
-        const double r = agg_tree(s[q], sh);
+        const double r = tree_sum_256(s[q], sh);
         if (threadIdx.x == 0) a.part[(size_t)d * 5 + q] = r;
     }
 }

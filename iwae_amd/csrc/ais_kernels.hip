@@ -15,55 +15,20 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "device_helpers.h"
 
 namespace iwae {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-#define AIS_LOG2E 1.4426950408889634f
-#define AIS_LN2 0.6931471805599453f
-#define AIS_HALF_LOG_2PI 0.9189385332046727f
 constexpr int AIS_THREADS = 256;
 
 __host__ __device__ inline int ais_pz(int Dp) { return (Dp > 16 * AIS_TPO ? Dp : 16 * AIS_TPO) + 4; }      // pitch of the z strip (also holds a residual tile)
 
-// tanh through one hardware exp2 (fp32_kernels.hip's tanh_f32): absolute error <= ~1.5e-7
-__device__ __forceinline__ float ais_tanh(float x) {
-    const float t = __expf(2.0f * fabsf(x));
-    return __builtin_copysignf(1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f), x);
-}
-
-// Philox4x32-10 + Box-Muller exactly as kernels.hip draws them: counter = (row_lo, row_hi, (stream << 24) | d4, step), key = seed
-__device__ __forceinline__ void ais_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)c0 * 0xD2511F53ull, p1 = (unsigned long long)c2 * 0xCD9E8D57ull;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ void ais_normal4(uint64_t grow, uint32_t d4, uint32_t stream, uint32_t step, uint64_t seed, float n[4]) {
-    uint32_t r[4];
-    ais_philox((uint32_t)grow, (uint32_t)(grow >> 32), (stream << 24) | d4, step, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const float s24 = 5.9604644775390625e-08f;   // 2^-24
-    const float u0 = ((float)(r[0] >> 8) + 0.5f) * s24, u1 = ((float)(r[1] >> 8) + 0.5f) * s24;
-    const float u2 = ((float)(r[2] >> 8) + 0.5f) * s24, u3 = ((float)(r[3] >> 8) + 0.5f) * s24;
-    const float ra = __builtin_amdgcn_sqrtf(-2.0f * __logf(u0)), rb = __builtin_amdgcn_sqrtf(-2.0f * __logf(u2));
-    n[0] = ra * __builtin_amdgcn_cosf(u1); n[1] = ra * __builtin_amdgcn_sinf(u1);
-    n[2] = rb * __builtin_amdgcn_cosf(u3); n[3] = rb * __builtin_amdgcn_sinf(u3);
-}
+// one accept uniform per chain row and transition: Philox stream 4, the first word of the draw
 __device__ __forceinline__ float ais_uniform(uint64_t grow, uint32_t step, uint64_t seed) {
     uint32_t r[4];
-    ais_philox((uint32_t)grow, (uint32_t)(grow >> 32), 4u << 24, step, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    philox4x32_10_mul((uint32_t)grow, (uint32_t)(grow >> 32), 4u << 24, step, (uint32_t)seed, (uint32_t)(seed >> 32), r);
     return ((float)(r[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
-}
-
-__device__ __forceinline__ float ais_rowsum(float v) {      // over the 16 lanes n16 of a quad group: every lane gets the same bits
-    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-    return v;
 }
 
 __global__ __launch_bounds__(AIS_THREADS) void ais_pad_kernel(AisPrepArgs a) {
@@ -87,45 +52,6 @@ __global__ __launch_bounds__(AIS_THREADS) void ais_init_kernel(AisInitArgs a) {
             const float z = a.z0[(size_t)r * a.D + d];
             a.e[(size_t)r * a.D + d] = a.head ? (z - a.head[(size_t)n * a.ldh + d]) / a.head[(size_t)n * a.ldh + a.soff + d] : z;
         }
-    }
-}
-
-// acc[t] += strip[16 rows][16 nkb] * W[16 nkb rows][16 cnt columns], t < cnt: W row-major with ldw floats per row, already at its first row and
-// column.  Whole workgroup: the slab of 16 weight rows goes global -> registers (one slab ahead) -> LDS between two barriers.
-__device__ __forceinline__ void ais_wg_gemm(const float* strip, int pa, int nkb, const float* W, int ldw, int cnt, float* slab,
-                                            f32x4v (&acc)[AIS_NT], int tid, int n16, int q) {
-    const int gpr = 4 * cnt;                     // 16-byte granules per slab row
-    int goff[4], soff[4];
-    bool ok[4];
-    float4 pre[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int g = tid + AIS_THREADS * u, r = g / gpr, cq = g - r * gpr;
-        ok[u] = r < 16;
-        goff[u] = r * ldw + 4 * cq;
-        soff[u] = r * AIS_SLABP + 4 * cq;
-        pre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok[u]) pre[u] = *(const float4*)(W + goff[u]);
-    }
-    for (int kb = 0; kb < nkb; ++kb) {
-        __syncthreads();          // every wave has left the previous slab (and the strips of the layer before are written)
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (ok[u]) *(float4*)(slab + soff[u]) = pre[u];
-        __syncthreads();
-        if (kb + 1 < nkb) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (ok[u]) pre[u] = *(const float4*)(W + (size_t)(kb + 1) * 16 * ldw + goff[u]);
-        }
-        const float4 av = *(const float4*)(strip + n16 * pa + 16 * kb + 4 * q);      // row n16, k = 16 kb + 4 q + j at .j
-        const float a4[4] = {av.x, av.y, av.z, av.w};
-        const float* sl = slab + 4 * q * AIS_SLABP + n16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int t = 0; t < AIS_NT; ++t)
-                if (t < cnt) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], sl[j * AIS_SLABP + 16 * t], acc[t], 0, 0, 0);
     }
 }
 
@@ -166,16 +92,16 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
             p[t][r] = 0.0f;
             if (in) ls += __logf(sg_at(r, col));
         }
-        lsum[r] = ais_rowsum(ls);                 // sum_d log sigma_d
+        lsum[r] = rowsum16(ls);                 // sum_d log sigma_d
         hstep[r] = a.h[row[r]];
         nacc[r] = a.nacc[row[r]];
     }
-    const float dc = (float)a.D * AIS_HALF_LOG_2PI;
+    const float dc = (float)a.D * HALF_LOG_2PI_F;
 
     // lj = log p(x|z) + log p(z) and l0 = log N(e; 0, I) - sum log sigma at z = mu + sigma e, then the kick p -= hh grad U_t with
     // grad U_t = (1 - bt) e - bt sigma (grad_z log p(x|z) - z)
     auto eval_kick = [&](float (&lj)[4], float (&l0)[4], const float bt, const float (&hh)[4]) {
-        f32x4v acc[AIS_NT], dg2[AIS_NT];
+        f32x4 acc[AIS_NT], dg2[AIS_NT];
         float sz[4] = {0.f, 0.f, 0.f, 0.f}, se[4] = {0.f, 0.f, 0.f, 0.f}, lp[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < AIS_DT; ++t) {
@@ -193,33 +119,33 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
         }
         // ---- g1 = tanh(z W1 + b1), g2 = tanh(g1 W2 + b2)
 #pragma unroll
-        for (int t = 0; t < AIS_NT; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-        ais_wg_gemm(zs, PZ, dt, a.W1, a.Hp, ht, slab, acc, tid, n16, q);
+        for (int t = 0; t < AIS_NT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        wg_gemm_f32(zs, PZ, dt, a.W1, a.Hp, ht, slab, acc, tid, n16, q);
 #pragma unroll
         for (int t = 0; t < AIS_NT; ++t) {
             if (t < ht) {
                 const float b = a.b1[16 * t + n16];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) g1s[(4 * q + r) * PH + 16 * t + n16] = ais_tanh(acc[t][r] + b);
-                acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+                for (int r = 0; r < 4; ++r) g1s[(4 * q + r) * PH + 16 * t + n16] = tanh_f32(acc[t][r] + b);
+                acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
         }
-        ais_wg_gemm(g1s, PH, ht, a.W2, a.Hp, ht, slab, acc, tid, n16, q);
+        wg_gemm_f32(g1s, PH, ht, a.W2, a.Hp, ht, slab, acc, tid, n16, q);
 #pragma unroll
         for (int t = 0; t < AIS_NT; ++t) {
             if (t < ht) {
                 const float b = a.b2[16 * t + n16];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) g2s[(4 * q + r) * PH + 16 * t + n16] = ais_tanh(acc[t][r] + b);
+                for (int r = 0; r < 4; ++r) g2s[(4 * q + r) * PH + 16 * t + n16] = tanh_f32(acc[t][r] + b);
             }
-            dg2[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            dg2[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
         // ---- output layer, 64 pixels at a time: logits -> log p(x|z) and s = x - sigmoid(l) -> dg2 += s W3^T (s never leaves the workgroup)
         for (int pass = 0; pass < npass; ++pass) {
             const int c0 = 16 * AIS_TPO * pass, cnt = min(AIS_TPO, xt - AIS_TPO * pass);
 #pragma unroll
-            for (int t = 0; t < AIS_TPO; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
-            ais_wg_gemm(g2s, PH, ht, a.W3 + c0, a.Xp, cnt, slab, acc, tid, n16, q);
+            for (int t = 0; t < AIS_TPO; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            wg_gemm_f32(g2s, PH, ht, a.W3 + c0, a.Xp, cnt, slab, acc, tid, n16, q);
             // sum_n x l - softplus(l) = sum_n (x - 1/2) l - |l| / 2 - log(1 + e^-|l|), the logarithms as one log2 of the product (dec_fwd_f32_kernel's form)
             float s_xl[4] = {0.f, 0.f, 0.f, 0.f}, s_al[4] = {0.f, 0.f, 0.f, 0.f}, prod[4] = {1.f, 1.f, 1.f, 1.f};
 #pragma unroll
@@ -232,7 +158,7 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
                     for (int r = 0; r < 4; ++r) {
                         const float x1 = in ? xrow[r][col] : 0.0f;
                         const float l = in ? acc[t][r] + b : 0.0f, xm = in ? x1 - 0.5f : 0.0f;
-                        const float ex = __builtin_amdgcn_exp2f(-fabsf(l) * AIS_LOG2E);      // exp(-|l|)
+                        const float ex = __builtin_amdgcn_exp2f(-fabsf(l) * LOG2E_F);      // exp(-|l|)
                         s_xl[r] = fmaf(xm, l, s_xl[r]);
                         s_al[r] += fabsf(l);
                         prod[r] = in ? fmaf(prod[r], ex, prod[r]) : prod[r];
@@ -241,8 +167,8 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) lp[r] += s_xl[r] - 0.5f * s_al[r] - AIS_LN2 * __builtin_amdgcn_logf(prod[r]);
-            ais_wg_gemm(zs, PZ, cnt, a.W3T + (size_t)c0 * a.Hp, a.Hp, ht, slab, dg2, tid, n16, q);
+            for (int r = 0; r < 4; ++r) lp[r] += s_xl[r] - 0.5f * s_al[r] - LN2_F * __builtin_amdgcn_logf(prod[r]);
+            wg_gemm_f32(zs, PZ, cnt, a.W3T + (size_t)c0 * a.Hp, a.Hp, ht, slab, dg2, tid, n16, q);
         }
         // ---- dpre2 = dg2 (1 - g2^2) over g2; dpre1 = (dpre2 W2^T)(1 - g1^2) over g1; dz = dpre1 W1^T
 #pragma unroll
@@ -255,9 +181,9 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
                     *at = dg2[t][r] * (1.0f - y * y);
                 }
             }
-            acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
-        ais_wg_gemm(g2s, PH, ht, a.W2T, a.Hp, ht, slab, acc, tid, n16, q);
+        wg_gemm_f32(g2s, PH, ht, a.W2T, a.Hp, ht, slab, acc, tid, n16, q);
 #pragma unroll
         for (int t = 0; t < AIS_NT; ++t) {
             if (t < ht) {
@@ -267,10 +193,10 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
                     const float y = *at;
                     *at = acc[t][r] * (1.0f - y * y);
                 }
-                acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+                acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
         }
-        ais_wg_gemm(g1s, PH, ht, a.W1T, a.Dp, dt, slab, acc, tid, n16, q);
+        wg_gemm_f32(g1s, PH, ht, a.W1T, a.Dp, dt, slab, acc, tid, n16, q);
 #pragma unroll
         for (int t = 0; t < AIS_DT; ++t) {
             if (t < dt) {
@@ -286,8 +212,8 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            lj[r] = ais_rowsum(lp[r]) + (-0.5f * ais_rowsum(sz[r]) - dc);
-            l0[r] = -0.5f * ais_rowsum(se[r]) - lsum[r] - dc;
+            lj[r] = rowsum16(lp[r]) + (-0.5f * rowsum16(sz[r]) - dc);
+            l0[r] = -0.5f * rowsum16(se[r]) - lsum[r] - dc;
         }
     };
     auto kinetic = [&](float (&kin)[4]) {
@@ -296,7 +222,7 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
             float s = 0.0f;
 #pragma unroll
             for (int t = 0; t < AIS_DT; ++t) s = fmaf(p[t][r], p[t][r], s);
-            kin[r] = 0.5f * ais_rowsum(s);
+            kin[r] = 0.5f * rowsum16(s);
         }
     };
 
@@ -312,7 +238,7 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
                 const int rr = idx / dq, d4 = idx - rr * dq;
                 const long rw = min(m0 + rr, a.R - 1);
                 float nrm[4];
-                ais_normal4(a.row_offset + (uint64_t)(rw % a.N) * (uint64_t)a.C + (uint64_t)(rw / a.N), (uint32_t)d4, 3u, a.step0 + (uint32_t)tt + 1u, a.seed, nrm);
+                normal4_mul(a.row_offset + (uint64_t)(rw % a.N) * (uint64_t)a.C + (uint64_t)(rw / a.N), (uint32_t)d4, 3u, a.step0 + (uint32_t)tt + 1u, a.seed, nrm);
                 *(float4*)(zs + rr * PZ + 4 * d4) = make_float4(nrm[0], nrm[1], nrm[2], nrm[3]);
             }
         }

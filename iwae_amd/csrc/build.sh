@@ -11,7 +11,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -fn
 # Build id = sha256 over the sources this library is made of (the same list, order and framing as iwae_amd/_capi.py::source_build_id):
 # iwae_build_id() returns it, tests/conftest.py rebuilds when the binary under test does not match the tree, bench.py stamps its line and
 # refuses profile artefacts taken on another build.
-BUILD_ID=$(for f in activity_kernels.hip aggregate_kernels.hip ais_kernels.hip analysis.hip build.sh fp32_kernels.hip grid_kernels.hip impute_kernels.hip kernels.h kernels.hip layout.h local_kernels.hip model.h model.hip moments_kernels.hip step_f32.hip ../../include/iwae_amd.h; do echo "== $(basename $f)"; cat "$f"; done | sha256sum | cut -c1-16)
+BUILD_ID=$(for f in activity_kernels.hip aggregate_kernels.hip ais_kernels.hip analysis.hip build.sh device_helpers.h fp32_kernels.hip grid_kernels.hip impute_kernels.hip kernels.h kernels.hip layout.h local_kernels.hip model.h model.hip moments_kernels.hip step_f32.hip ../../include/iwae_amd.h; do echo "== $(basename $f)"; cat "$f"; done | sha256sum | cut -c1-16)
 if [ -n "${DIAG:-}${STAMPS:-}" ]; then BUILD_ID="${BUILD_ID}-diag"; fi
 if [ -n "${DIAG:-}${STAMPS:-}" ]; then FLAGS="$FLAGS -DIWAE_DIAG"; fi
 if [ -n "${STAMPS:-}" ]; then FLAGS="$FLAGS -DIWAE_DENSE_STAMPS"; fi

@@ -8,17 +8,9 @@
 #include <type_traits>
 #include <algorithm>
 #include "kernels.h"
+#include "device_helpers.h"
 
 namespace iwae {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
-
-// tanh through one hardware exp2: 1 - 2/(1 + e^{2|x|}), sign restored.  Absolute error <= ~1.5e-7 (one ulp of 1.0; saturates cleanly: e^{2|x|} = inf
-// gives exactly 1) -- the library tanhf is ~50 instructions per value, 20 million values per tanh layer of the full-size step.
-__device__ __forceinline__ float tanh_f32(float x) {
-    const float t = __expf(2.0f * fabsf(x));
-    return __builtin_copysignf(1.0f - 2.0f * __builtin_amdgcn_rcpf(t + 1.0f), x);
-}
 
 // a fetched quad of op(B) times the row weights of its k index / indices (GemmF32Args.brow_scale)
 __device__ __forceinline__ float4 scale_b_quad(const GemmF32Args& a, float4 t, int gk, bool b_nfast) {
@@ -44,11 +36,11 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmF32Args a) {
     const int k_beg = blockIdx.z * a.kchunk, k_end = min(a.K, k_beg + a.kchunk);
     const int wm = wave >> 1, wn = wave & 1;
     const int r16 = lane & 15, q = lane >> 4;
-    f32x4v acc[2][2];
+    f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // Each thread fetches KB quads (4 consecutive elements along the unit-stride index) of the A tile and of the B tile per iteration, as
     // float4 where the host found the operand 16-byte aligned (a.avec / a.bvec), and the NEXT iteration's quads are requested before
     // this one's MFMAs: the global latency hides under them.
@@ -172,11 +164,11 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_big_kernel(GemmF32Args a) {  
     const int k_beg = blockIdx.z * a.kchunk, k_end = min(a.K, k_beg + a.kchunk);
     const int wm = wave >> 1, wn = wave & 1;
     const int r16 = lane & 15, q = lane >> 4;
-    f32x4v acc[TM][TN];
+    f32x4 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // quad u of a thread: number qq = tid + 256 u of the tile's quads; k-fast: 4 quads per row (m = qq >> 2, k = 4 (qq & 3)); m-fast: QM quads per k
     // (k = qq / QM, m = 4 (qq % QM)); the B tile likewise
     auto a_pos = [&](int u, int& lm, int& lk) { const int qq = tid + 256 * u; if (a_kfast) { lm = qq >> 2; lk = (qq & 3) * 4; } else { lk = qq / QM; lm = (qq % QM) * 4; } return qq < BM * 4; };
@@ -430,11 +422,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void gemm_f32_v2_kernel(GemmF3
     const int k_beg = bz * a.kchunk, k_end = min(a.K, k_beg + a.kchunk);
     const int wm = wave / WGN, wn = wave % WGN;
     const int r16 = lane & 15, q = lane >> 4;
-    f32x4v acc[TM][TN];
+    f32x4 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // ---- the thread's quads.  Quad u of an operand tile [E = BM | BN][16 k]:
     //   k index unit-stride: row e = (tid >> 2) + 64 u, k = 4 (tid & 3) .. + 3            (E / 64 quads per thread, rounded up)
     //   otherwise:          k row = (256 / TPR) u + tid / TPR, e = 4 (tid % TPR) .. + 3    (TPR = threads per k row: the power of two >= E / 4)
@@ -782,11 +774,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void gemm_f32_v2_kernel(GemmF3
 #define DF_TP 13                    // out-feature tiles (16 each) a wave accumulates per pass
 #define DF_PA 212                   // activation strip pitch in floats (= 4 * 53: rows fall into different bank quads for ds_read_b128)
 #define DF_SLAB (16 * 16 * DF_TP)   // floats per weight slab: 16 in-features x 208 out-features
-__device__ __forceinline__ void df_glds16(const char* g, uint32_t lds_wave_base) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(lds_wave_base) : "memory");
-}
 __global__ __launch_bounds__(256, 2) void dec_fwd_f32_kernel(DecFwdF32Args a) {
     extern __shared__ __attribute__((aligned(1024))) char smem_df[];
 #ifdef IWAE_DENSE_STAMPS
@@ -872,14 +859,14 @@ __global__ __launch_bounds__(256, 2) void dec_fwd_f32_kernel(DecFwdF32Args a) {
                 for (int u = 0; u < 4; ++u) {
                     if (256 * u + 64 * wave < 16 * 4 * DF_TP) {          // (wave-uniform: pieces past the slab's 832 granules are never issued)
                         const char* src = (last_ragged && 16 * kb + grow[u] >= K) ? zsrc : gcur[u];
-                        df_glds16(src, (uint32_t)__builtin_amdgcn_readfirstlane((int)(slab_lds + (uint32_t)buf * (DF_SLAB * 4) + (uint32_t)(256 * u + 64 * wave) * 16u)));
+                        glds16(src, (uint32_t)__builtin_amdgcn_readfirstlane((int)(slab_lds + (uint32_t)buf * (DF_SLAB * 4) + (uint32_t)(256 * u + 64 * wave) * 16u)));
                         gcur[u] += gstep[u];
                     }
                 }
             };
-            f32x4v acc[DF_TP];
+            f32x4 acc[DF_TP];
 #pragma unroll
-            for (int t = 0; t < DF_TP; ++t) acc[t] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+            for (int t = 0; t < DF_TP; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
             DF_STAMP(1)      // pass set-up
             __syncthreads();              // every wave is done with both slabs of the pass / layer before (and the strip is written)
             DF_STAMP(2)      // barrier between passes

@@ -12,26 +12,12 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "layout.h"
+#include "device_helpers.h"
 
 namespace iwae {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 gbf16x8_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 gbf16x2_t;
-typedef __attribute__((ext_vector_type(4))) float gf32x4;
-
 #define GRID_LOG2PI 1.8378770664093453
-
-__device__ __forceinline__ uint32_t gpack2(float a, float b) {
-    gbf16x2_t v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;   // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float gbf(uint32_t u, int hi) { return __uint_as_float(hi ? (u & 0xffff0000u) : (u << 16)); }
-__device__ __forceinline__ gf32x4 gmfma(const uint4& a, const uint4& b, gf32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gbf16x8_t, a), __builtin_bit_cast(gbf16x8_t, b), c, 0, 0, 0);
-}
 
 // x [N][X] fp32 -> XB [Np][Xp] bf16 (pad rows / pixels zero); *nonbinary = 1 if any x is not 0 or 1
 __global__ __launch_bounds__(256) void grid_prep_x_kernel(const float* x, int N, int X, int Np, int Xp, uint16_t* XB, int* nonbinary) {
@@ -47,7 +33,7 @@ __global__ __launch_bounds__(256) void grid_prep_x_kernel(const float* x, int N,
         v[j] = (row < N && col < X) ? x[(size_t)row * X + col] : 0.0f;
         bad |= !(v[j] == 0.0f || v[j] == 1.0f);
     }
-    *(uint4*)(XB + (size_t)row * Xp + c8) = make_uint4(gpack2(v[0], v[1]), gpack2(v[2], v[3]), gpack2(v[4], v[5]), gpack2(v[6], v[7]));
+    *(uint4*)(XB + (size_t)row * Xp + c8) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
     if (bad) atomicOr(nonbinary, 1);
 }
 
@@ -69,12 +55,12 @@ __global__ __launch_bounds__(256) void grid_prep_kernel(GridPrepArgs a) {
         uint32_t h[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            h[j] = gpack2(l[2 * j], l[2 * j + 1]);
-            lo[2 * j] = l[2 * j] - gbf(h[j], 0);
-            lo[2 * j + 1] = l[2 * j + 1] - gbf(h[j], 1);
+            h[j] = pack2(l[2 * j], l[2 * j + 1]);
+            lo[2 * j] = l[2 * j] - bflo(h[j]);
+            lo[2 * j + 1] = l[2 * j + 1] - bfhi(h[j]);
         }
         *(uint4*)(a.Lhi + (size_t)g * a.Xp + c8) = make_uint4(h[0], h[1], h[2], h[3]);
-        *(uint4*)(a.Llo + (size_t)g * a.Xp + c8) = make_uint4(gpack2(lo[0], lo[1]), gpack2(lo[2], lo[3]), gpack2(lo[4], lo[5]), gpack2(lo[6], lo[7]));
+        *(uint4*)(a.Llo + (size_t)g * a.Xp + c8) = make_uint4(pack2(lo[0], lo[1]), pack2(lo[2], lo[3]), pack2(lo[4], lo[5]), pack2(lo[6], lo[7]));
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) sp += __shfl_xor(sp, off);      // butterfly: every lane holds the same sum
@@ -157,12 +143,12 @@ __global__ __launch_bounds__(256) void grid_score_kernel(GridScoreArgs a) {
             lfrag[f] = *(const uint4*)src;
         }
         __syncthreads();
-        gf32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int s = 0; s < KTM; ++s) {
             if (s < KT) {
-                acc = gmfma(lfrag[s * 64 + lane], xf[s], acc);
-                acc = gmfma(lfrag[(KT + s) * 64 + lane], xf[s], acc);
+                acc = mfma16(lfrag[s * 64 + lane], xf[s], acc);
+                acc = mfma16(lfrag[(KT + s) * 64 + lane], xf[s], acc);
             }
         }
 #pragma unroll

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include "kernels.h"
 #include "layout.h"
+#include "device_helpers.h"
 
 #ifdef IWAE_DIAG
 #define WG_DBG(a, bit) (((a).dbg & (bit)) != 0)
@@ -23,124 +24,6 @@
 #endif
 namespace iwae {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define LOG2PI_F 1.8378770664093453f
-
-// ---------------------------------------------------------------------------------
-// small device helpers
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-    bf16x2_t v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;   // hipcc emits v_cvt_pk_bf16_f32 (round-to-nearest-even, NaN-safe)
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float bflo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bfhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ float bf_at(const uint4& u, int j) {
-    const uint32_t w = (j < 2) ? u.x : (j < 4) ? u.y : (j < 6) ? u.z : u.w;
-    return (j & 1) ? bfhi(w) : bflo(w);
-}
-__device__ __forceinline__ f32x4 mfma16(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ float rcp_fast(float x) { return __builtin_amdgcn_rcpf(x); }
-#define LOG2E_F 1.4426950408889634f
-#define LN2_F 0.6931471805599453f
-// raw v_exp_f32 / v_log_f32 (base 2, ~1 ulp, no denormal fix-up code: arguments here never need it)
-__device__ __forceinline__ float exp2_raw(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float log2_raw(float x) { return __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float tanh_fast(float x) {
-    // 1 - 2/(e^{2x}+1): exact limits at +-inf, abs error ~1e-7 (the result is rounded to bf16 anyway)
-    return 1.0f - 2.0f * rcp_fast(exp2_raw(x * (2.0f * LOG2E_F)) + 1.0f);
-}
-__device__ __forceinline__ float sigmoid_fast(float l) { return rcp_fast(1.0f + exp2_raw(-l * LOG2E_F)); }
-
-// async global -> LDS copy (LDS-DMA), 16 B per lane; LDS destination = M0 (wave-uniform byte address)
-// + lane*16.  Issued through inline asm on purpose: with the builtin, hipcc cannot prove that the
-// DMA does not alias later ds_reads and drains it (s_waitcnt vmcnt(0)) before every k-step, which
-// serialises the weight prefetch with the MFMAs.  Completion is ordered by the explicit
-// "s_waitcnt vmcnt(0)" + barrier at the top of each group (cdna_hip_programming.md 5.7).
-__device__ __forceinline__ uint32_t lds_addr_of(const char* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
-__device__ __forceinline__ void glds16(const char* g, uint32_t lds_wave_base) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(lds_wave_base) : "memory");
-}
-
-// stream `bytes` (multiple of 1 KiB) of an A-image into LDS with the whole workgroup (wave must be
-// wave-uniform, e.g. readfirstlane(threadIdx.x >> 6))
-template <int NWAVES>
-__device__ __forceinline__ void stage_image(const char* src, char* lds, int bytes, int wave, int lane) {
-    const uint32_t base = lds_addr_of(lds);
-    for (int off = wave * 1024; off < bytes; off += NWAVES * 1024)
-        glds16(src + off + lane * 16, (uint32_t)__builtin_amdgcn_readfirstlane((int)(base + (uint32_t)off)));
-}
-
-// Group boundary wait.  The builtin tells hipcc's waitcnt pass that every vector-memory op it knows
-// about has retired (otherwise it re-waits vmcnt(0) in front of the first MFMA of the group, which
-// also drains the LDS-DMA just issued for the NEXT group); the asm form is the one that must stay:
-// it also covers the asm-issued LDS-DMA, which the pass cannot see.
-__device__ __forceinline__ void wait_all_vmem() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt/lgkmcnt untouched
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// A-fragment stream with P ds_read_b128 in flight: rd(i) -> uint4, use(i, frag).  Without this the
-// compiler emits read -> lgkmcnt(0) -> 2 MFMA per fragment and a lone wave pays the LDS latency
-// (~64-128 cycles) for every 32 cycles of MFMA.
-template <int N, int P, class RD, class USE, class SIDE>
-__device__ __forceinline__ void lds_pipeline(RD rd, USE use, SIDE side) {
-    uint4 av[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-        if (i < N) av[i] = rd(i);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        use(i, av[i % P]);
-        if (i + P < N) av[i % P] = rd(i + P);
-        side(i);       // e.g. one LDS-DMA piece of the NEXT group: drains under the MFMAs instead of in front of them
-    }
-}
-template <int N, int P, class RD, class USE>
-__device__ __forceinline__ void lds_pipeline(RD rd, USE use) {
-    lds_pipeline<N, P>(rd, use, [](int) {});
-}
-
-// ---------------------------------------------------------------------------------
-// Philox4x32-10 + Box-Muller.  counter = (row_lo, row_hi, (stream<<24)|d4, step), key = seed
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // both halves of a 32 x 32 product from ONE v_mad_u64_u32 (as __umulhi + a 32-bit multiply the compiler issued two quarter-rate multiplies each)
-        unsigned long long p0, p1;
-        asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p0) : "v"(c0), "v"(0xD2511F53u) : "vcc");
-        asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p1) : "v"(c2), "v"(0xCD9E8D57u) : "vcc");
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ void normal4(uint64_t grow, uint32_t d4, uint32_t stream, uint32_t step, uint64_t seed, float n[4]) {
-    uint32_t r[4];
-    philox4x32_10((uint32_t)grow, (uint32_t)(grow >> 32), (stream << 24) | d4, step, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const float s24 = 5.9604644775390625e-08f;   // 2^-24
-    const float u0 = ((float)(r[0] >> 8) + 0.5f) * s24, u1 = ((float)(r[1] >> 8) + 0.5f) * s24;
-    const float u2 = ((float)(r[2] >> 8) + 0.5f) * s24, u3 = ((float)(r[3] >> 8) + 0.5f) * s24;
-    // v_log/v_sqrt/v_sin/v_cos (v_sin/v_cos take revolutions: sin(2*pi*u) = v_sin(u)); abs error ~1e-6
-    const float ra = __builtin_amdgcn_sqrtf(-2.0f * __logf(u0)), rb = __builtin_amdgcn_sqrtf(-2.0f * __logf(u2));
-    n[0] = ra * __builtin_amdgcn_cosf(u1); n[1] = ra * __builtin_amdgcn_sinf(u1);
-    n[2] = rb * __builtin_amdgcn_cosf(u3); n[3] = rb * __builtin_amdgcn_sinf(u3);
-}
 // 4 consecutive eps values for features 4*d4 .. 4*d4+3 of data row (b,s)
 __device__ __forceinline__ void eps4(const EpsSrc& e, int b, int s, int row, int d4, int D, float n[4]) {
     if (e.cache) {

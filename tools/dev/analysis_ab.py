@@ -6,7 +6,9 @@ two builds and compare the files array by array (numpy.array_equal) to show that
 
 Calls (both precisions; the images once as a host array, once as a device pointer): grid_posterior 64/2/48 N=5 G=1500 in two chunks with
 log_joint; latent_activity N=3 k=200 on the small and the reference 2-layer models; aggregate_posterior 64/8/48 N=37 S=3 with the
-per-sample outputs; ais 64/8/48 N=3 C=7 T=6 L=2 with trace from both inits; grad_moments B=20 k=5 M=4; eval_llh N=7 k=50; decode n=5.
+per-sample outputs; ais 64/8/48 N=3 C=7 T=6 L=2 with trace from both inits; local_posterior 64/8/48 N=3 S=5 T=4 E=2 with trace, once on
+the caller's draws and once on Philox; impute 64/8/48 under a 50 % mask at N=5 S=3 (several images per workgroup, a dead row), N=2 S=70 (two
+chunks per image and impute_merge_kernel) and N=5 S=3 without a mask; grad_moments B=20 k=5 M=4; eval_llh N=7 k=50; decode n=5.
 """
 import argparse
 import os
@@ -82,6 +84,8 @@ def model(layers, nh, nl, xd, N, seed, prec, **kw):
 rng = np.random.default_rng(5)
 z = rng.uniform(-3.0, 3.0, (1500, 2)).astype(np.float32)
 lw = rng.uniform(-1.0, 0.0, 1500).astype(np.float32)
+lq_noise = rng.standard_normal((4 + 2, 5, 3, 8)).astype(np.float32)
+im_mask = rng.random((5, 48)) < 0.5
 for prec in ("fp32", "bf16"):
     for where in ("host", "dev"):
         put = (lambda a: a) if where == "host" else DevArray
@@ -101,6 +105,13 @@ for prec in ("fp32", "bf16"):
         for init in ("encoder", "prior"):
             m.set_step(6, 4)
             keep(tag + "ais." + init, m.ais(put(x[:3]), n_chains=7, n_temps=6, leapfrog=2, init=init, trace=True))
+        m.set_step(9, 6)
+        keep(tag + "local_q.noise", m.local_posterior(put(x[:3]), n_samples=5, n_iters=4, n_eval=2, noise=lq_noise, trace=True))
+        keep(tag + "local_q.philox", m.local_posterior(put(x[:3]), n_samples=5, n_iters=4, n_eval=2, trace=True))
+        m.set_step(10, 7)
+        keep(tag + "impute.s3", m.impute(put(x[:5]), mask=im_mask, n_samples=3))
+        keep(tag + "impute.s70", m.impute(put(x[:2]), mask=im_mask[:2], n_samples=70))
+        keep(tag + "impute.nomask", m.impute(put(x[:5]), n_samples=3))
         m.set_step(7, 0)
         keep(tag + "grad_moments", m.grad_moments(put(x[:20]), 5, 4))
         m.set_step(8, 5)
