@@ -471,6 +471,65 @@ typedef struct {
 int iwae_impute(iwae_handle h, const float* x, int32_t N,                  /* [N, x_dim], host or device, observed values in [0,1] */
                 const iwae_impute_options* opt, const iwae_impute_outputs* out);
 
+/* The two uses of the self-normalised importance weights beyond a pixel mean, on the device at scale: the SNIS estimate of the posterior's
+ * mean and covariance in latent space, and sampling importance resampling (SIR) of R latent vectors per image from p(z | x_obs)
+ * (the reference's tasks/task01.py:52-58 and tasks/plot_task01.py:74-88 do both on the host per image; the covariance is what the
+ * approximation gap of iwae_local_posterior is made of, Cremer et al. 2018; the SIR draws are Mattei & Frellsen's multiple imputation).
+ * The proposal, the mask semantics, log_w_s and al_s are iwae_impute's: image n has k draws e_s ~ N(0, I), z_s = mu + sigma e_s.
+ * (1) Shared outputs.  log_w [k, N], log_px, ess, q_mu, q_sigma are bit for bit what iwae_impute returns on the same x, mask, k and noise:
+ * both calls run the same heads step, pass (a) and pass (b) (and honour the same launch cap, option impute_rows).
+ * (2) Moments, taken in the standardised variable e (q's own mean is the pilot, so one pass suffices):
+ *   ebar_d = sum_s al_s e_sd        M2_dd' = sum_s (al_s e_sd) e_sd'        Ce = M2 - ebar ebar^T
+ *   mean[n,d] = mu_d + sigma_d ebar_d        cov[n,d,d'] = sigma_d sigma_d' Ce_dd'
+ * float32: al_s = exp(log_w_s - max) * (float)(1 / sum), and the sums over each 64-draw chunk of an image in sample order (M2 on
+ * v_mfma_f32_16x16x4_f32, four draws per instruction).  double: the chunks in chunk order, Ce, and the products with mu and sigma, each
+ * output rounded to float32 once.  cov is bitwise symmetric (one triangle is computed, the other mirrors it) and its diagonal is clamped
+ * at 0.  With cov == NULL the second-moment product does not run; with mean == NULL too, no moment kernel runs.
+ * (3) Resampling with replacement by the inverse CDF.  w_s = exp((double)(log_w_s - max)) (pass (b)'s exponential), c_s = sum_{j <= s} w_j
+ * in double in sample order (c_{k-1} is pass (b)'s sum); draw r takes
+ *   idx[r,n] = the smallest s with c_s > (double)u_{r,n} c_{k-1}          z[r,n,:] = mu + exp(log sigma) e_idx  (fmaf, pass (a)'s arithmetic)
+ * and u = 1 (no such s) takes the first s whose c_s reaches c_{k-1}: the last draw of non-zero weight.  Passing unif with
+ * u_{r,n} = (r + u0_n) / R, u0_n in [0,1), gives systematic resampling.  e_idx is regenerated from the index at the proposal's own Philox
+ * row (batch_offset + n) k + idx (with the caller's eps: gathered from there): no [k, N, D] array of z ever exists.  u [R, N] returns the
+ * uniforms used.  R = 0: no resampling; asking for idx, z or u then is IWAE_ERR_ARG.  R > 0 with none of the three asked for draws nothing.
+ * (4) Noise.  eps == NULL: iwae_impute's draws (latent stream 0 at the handle's step).  unif == NULL: Philox stream 5 at the same step,
+ * counter (row lo, row hi, 5 << 24, step) with row = (batch_offset + n) R + r, the uniform ((word 0 >> 8) + 0.5) 2^-24 as iwae_ais forms
+ * its accept uniforms.  The call advances the noise step by one if and only if it drew anything on the device (eps, or uniforms that a
+ * wanted idx, z or u needed); with both the caller's it is left alone.
+ * Determinism: iwae_impute's contract.  An image's outputs depend only on the weights, the image, its mask, k, R and its own draws and
+ * uniforms -- not on N, its position, the other images or the launch chunking -- and repeat bitwise.  No atomics; every reduction has a
+ * fixed order and every trip count is known on the host; workgroups never communicate.  What x holds at an unobserved pixel reaches nothing.
+ * Models and limits: iwae_impute's (1-layer, unconditional, n_hidden <= 208, n_latent <= 128).  IWAE_ERR_ARG before any launch, the noise
+ * step unchanged: k outside 1..65536, R outside 0..65536, N <= 0, N k > 2^27, N R > 2^27, a wrong struct_size, reserved != 0, x / opt /
+ * out / log_px NULL, idx / z / u with R = 0.
+ * Workspace: iwae_impute's without xhat; for the moments 4 ceil(k / 64) (D'^2 + D') bytes per image of a launch (D' = n_latent rounded up
+ * to 16; launches are cut so that this stays under 256 MB); for the resampling 8 k bytes per image of a launch (never 8 k N) and 4 R N of
+ * indices; per output asked for on the host its own size.
+ * x, mask, eps, unif: host or device.  Outputs: each host or device, NULL = not wanted and never materialised. */
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(iwae_posterior_options) (40) */
+    int32_t k;                 /* importance draws per image, 1..65536 */
+    int32_t R;                 /* resampled draws per image, 0..65536 */
+    int32_t reserved;          /* 0 */
+    const uint8_t* mask;       /* [N, x_dim], non-zero = observed; NULL = every pixel observed */
+    const float* eps;          /* [k, N, D] the caller's N(0,1) draws, or NULL */
+    const float* unif;         /* [R, N] the caller's uniforms in [0,1], or NULL */
+} iwae_posterior_options;
+typedef struct {
+    double* log_px;            /* [N]        required: as iwae_impute */
+    float* ess;                /* [N] */
+    float* mean;               /* [N, D]     SNIS estimate of E[z | x_obs] */
+    float* cov;                /* [N, D, D]  SNIS estimate of Cov[z | x_obs] */
+    int32_t* idx;              /* [R, N]     the resampled draws' indices into the k proposals */
+    float* z;                  /* [R, N, D]  the resampled latent vectors */
+    float* u;                  /* [R, N]     the uniforms used */
+    float* log_w;              /* [k, N] */
+    float* q_mu;               /* [N, D]     heads of the masked input */
+    float* q_sigma;            /* [N, D] */
+} iwae_posterior_outputs;
+int iwae_posterior(iwae_handle h, const float* x, int32_t N,               /* [N, x_dim], host or device, observed values in [0,1] */
+                   const iwae_posterior_options* opt, const iwae_posterior_outputs* out);
+
 /* Data pipeline on the device (main.py:59-65,117-120 + src/utils.py:26-27): the grey-level training set
  * stays resident in HBM as uint8 [n, x_dim]; every epoch gets a visiting order (tf.data shuffle) and a
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),
@@ -495,7 +554,7 @@ int iwae_train_step_dataset(iwae_handle h, int32_t start, int32_t B, int32_t k, 
  * step (an event record costs a few us of stream bubble, so bench.py samples rather than timing every launch); 0 switches
  * it off.  name: "decoder_fwd" (whole decoder forward + log-likelihood), "out_bwd" (output-layer backward), "decoder_bwd" (the decoder's whole dX chain where it is one launch), "wgrad_out",
  * "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent" (the decoder's other backward kernels), "latent_bwd",
- * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel), "impute" (likewise both passes of iwae_impute's impute_rows_kernel).  A kernel a configuration does not launch reports 0 launches. */
+ * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel), "impute" (likewise both passes of iwae_impute's impute_rows_kernel, and pass (a) of iwae_posterior), "posterior" (likewise iwae_posterior's moments and merge launches).  A kernel a configuration does not launch reports 0 launches. */
 int iwae_enable_timing(iwae_handle h, int32_t enable);
 int iwae_kernel_time(iwae_handle h, const char* name, double* avg_us, int64_t* launches);
 

@@ -86,6 +86,22 @@ class ImputeOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in IMPUTE_OUTPUT_FIELDS]
 
 
+class PosteriorOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_int32), ("R", C.c_int32), ("reserved", C.c_int32), ("mask", C.c_void_p),
+                ("eps", C.c_void_p), ("unif", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(PosteriorOptions)   # the ABI guard iwae_posterior checks
+
+
+POSTERIOR_OUTPUT_FIELDS = ("log_px", "ess", "mean", "cov", "idx", "z", "u", "log_w", "q_mu", "q_sigma")
+
+
+class PosteriorOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in POSTERIOR_OUTPUT_FIELDS]
+
+
 # every symbol include/iwae_amd.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -128,6 +144,7 @@ SYMBOLS = {
     "iwae_ais": (C.c_int, [_P, _P, C.c_int32, C.POINTER(AisOptions), C.POINTER(AisOutputs)]),
     "iwae_local_posterior": (C.c_int, [_P, _P, C.c_int32, C.POINTER(LocalOptions), C.POINTER(LocalOutputs)]),
     "iwae_impute": (C.c_int, [_P, _P, C.c_int32, C.POINTER(ImputeOptions), C.POINTER(ImputeOutputs)]),
+    "iwae_posterior": (C.c_int, [_P, _P, C.c_int32, C.POINTER(PosteriorOptions), C.POINTER(PosteriorOutputs)]),
     "iwae_grad_moments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "iwae_dataset_upload": (C.c_int, [_P, _P, C.c_int32]),
     "iwae_dataset_begin_epoch": (C.c_int, [_P, C.c_uint32, _P, C.c_int32]),
@@ -144,7 +161,7 @@ SYMBOLS = {
 
 _lib = None
 
-_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "device_helpers.h", "fp32_kernels.hip", "grid_kernels.hip", "impute_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "local_kernels.hip", "model.h", "model.hip", "moments_kernels.hip", "step_f32.hip",
+_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "device_helpers.h", "fp32_kernels.hip", "grid_kernels.hip", "impute_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "local_kernels.hip", "model.h", "model.hip", "moments_kernels.hip", "posterior_kernels.hip", "step_f32.hip",
                os.path.join("..", "..", "include", "iwae_amd.h"))
 
 

@@ -1,5 +1,5 @@
-// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior, iwae_ais, iwae_local_posterior and iwae_impute: the analyses that start
-// from the encoder heads of N images (host code; kernels in the six *_kernels.hip).  Each reads in five parts: argument checks, eval_begin, its own buffers and launches, its own copy-outs, eval_end.
+// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior, iwae_ais, iwae_local_posterior, iwae_impute and iwae_posterior: the analyses that start
+// from the encoder heads of N images (host code; kernels in the seven *_kernels.hip).  Each reads in five parts: argument checks, eval_begin, its own buffers and launches, its own copy-outs, eval_end.
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -92,6 +92,10 @@ int dump_eps(iwae_model* m, int N, int S, int D, DevBuf& ws) {
 // (97 per pass) of the N = 10 000, k = 5 000 call cost nothing measurable (1.290 s in the kernel of 1.297 s wall), so nothing is gained by going higher.
 #define IMPUTE_ROWS_DEFAULT (1 << 19)
 #define IMPUTE_K_MAX 65536
+#define POSTERIOR_R_MAX 65536
+// iwae_posterior: floats of chunk moments per launch of posterior_moments_kernel (256 MB): at the reference dims (D' = 112, k = 5 000) an image
+// takes 79 x 12 656 floats, so a launch holds 67 images; the sums do not depend on where the launches are cut.
+#define POSTERIOR_PART_FLOATS ((size_t)1 << 26)
 
 // The decoder's weights in both orientations, padded to multiples of 16 (src/iwae1.py:72-75; Keras kernels [in][out]), into m->ais.wpad
 struct DecPad { const float *W1, *W1T, *W2, *W2T, *W3, *W3T, *b1, *b2, *b3; };
@@ -108,6 +112,79 @@ int pad_decoder(iwae_model* m, hipStream_t st, int Dp, int Hp, int Xp, DecPad& p
     for (const AisPrepArgs& j : jobs) launch_ais_pad(j, st);
     HIPCHK(hipGetLastError());
     p = DecPad{W1, W1T, W2, W2T, W3, W3T, b1, b2, b3};
+    return IWAE_OK;
+}
+
+// What iwae_impute and iwae_posterior share.  First the models and sizes both accept (who: the caller's name, for the message) ...
+int impute_scope(iwae_model* m, const char* who, int N, int k) {
+    const std::string w(who);
+    if (N <= 0 || k < 1 || k > IMPUTE_K_MAX) return fail(IWAE_ERR_ARG, w + ": needs N > 0 and 1 <= k <= " + std::to_string(IMPUTE_K_MAX));
+    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, w + ": only the 1-layer model");
+    if (m->C != 0 || m->has_prior) return fail(IWAE_ERR_ARG, w + ": only the unconditional model (cond_dim = 0, no learned prior)");
+    if ((int64_t)N * k > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, w + ": too large (N * k > 2^27 rows)");
+    if (round_up(m->H[0], 16) > 16 * AIS_NT || round_up(m->D[0], 16) > 16 * AIS_DT) return fail(IWAE_ERR_ARG, w + ": needs n_hidden <= " + std::to_string(16 * AIS_NT) + " and n_latent <= " + std::to_string(16 * AIS_DT));
+    return IWAE_OK;
+}
+
+// ... and the weights: the masked input, the encoder heads (copied to q_mu / q_sigma), pass (a) in launches of whole images of at most
+// `impute_rows` rows, and pass (b).  Leaves in m->imp log_w (or in the caller's device array: iw.logwd), wstat, lpx and (want_ess) ess; iw.ia
+// is ready for further launches of impute_rows_kernel (xhat and part unset) and carries the call's noise keys.  Switches the kernel
+// timing on for the call: the caller switches it off after its own timed launches.
+struct ImputeWeights { ImputeArgs ia; float* logwd; int nbmax, nchunk; };
+int impute_weights(EvalCall& c, int N, int S, const uint8_t* mask, const float* eps, float* log_w, bool want_ess, float* q_mu, float* q_sigma, ImputeWeights& iw) {
+    iwae_model* m = c.m;
+    hipStream_t st = c.st;
+    iwae_model::ImputeWs& w = m->imp;
+    const int D = m->D[0], H = m->H[0], X = m->X, Dp = round_up(D, 16), Hp = round_up(H, 16), Xp = round_up(X, 16), Dh = m->Dp[0];
+    // ---- the masked input xin = m ? x : 0 into the call's own buffer: what the encoder and the rows read from here on
+    const uint8_t* maskd = nullptr;
+    if (mask) {
+        CHK(staged_in(m, mask, w.mask, (size_t)N * X, &maskd));
+        CHK(ensure(w.xin, (size_t)N * X * 4, st));
+        launch_impute_mask(c.xd, maskd, (long)N * X, ptr<float>(w.xin), st);
+        HIPCHK(hipGetLastError());
+        c.xd = ptr<float>(w.xin);
+    }
+    // ---- encoder heads mu, sigma of the masked input (src/iwae1.py:39-42), in the eval precision
+    CHK(eval_heads(c, N));
+    CHK(eval_copy_heads(c, N, q_mu, q_sigma));
+    ImputeArgs& ia = iw.ia;
+    memset(&ia, 0, sizeof(ia));
+    {
+        DecPad p;
+        CHK(pad_decoder(m, st, Dp, Hp, Xp, p));
+        ia.W1 = p.W1; ia.W2 = p.W2; ia.W3 = p.W3; ia.b1 = p.b1; ia.b2 = p.b2; ia.b3 = p.b3;
+    }
+    const float* epsd = nullptr;
+    if (eps) CHK(staged_in(m, eps, w.eps, (size_t)S * N * D * 4, &epsd));
+    float* logwd = nullptr;
+    CHK(staged_out(m, log_w, w.logw, (size_t)S * N * 4, &logwd));      // (always computed: the later passes read it)
+    CHK(ensure(w.wstat, (size_t)N * 8, st));
+    CHK(ensure(w.lpx, (size_t)N * 8, st));
+    if (want_ess) CHK(ensure(w.ess, (size_t)N * 4, st));
+    // ---- launches of whole images, at most `cap` rows each
+    const int cap = m->opt.impute_rows > 0 ? m->opt.impute_rows : IMPUTE_ROWS_DEFAULT;
+    const int nbmax = std::min((int)N, std::max(1, cap / S)), nchunk = S > 64 ? (S + 63) / 64 : 1;
+    ia.D = D; ia.H = H; ia.X = X; ia.Dp = Dp; ia.Hp = Hp; ia.Xp = Xp;
+    ia.x = c.xd; ia.mask = maskd; ia.head = c.head; ia.ldh = c.ldh; ia.soff = Dh;
+    ia.N = N; ia.S = S; ia.ipw = S <= 64 ? 64 / S : 1; ia.nchunk = nchunk;
+    ia.eps = epsd; ia.seed = m->cfg.seed; ia.row_offset = (uint64_t)m->batch_offset * (uint64_t)S; ia.step = m->noise_step;
+    ia.log_w = logwd; ia.wstat = ptr<float2>(w.wstat);
+    m->time_this = m->timing > 0;
+    // pass (a): log_w of every row
+    for (int i0 = 0; i0 < N; i0 += nbmax) {
+        ia.img0 = i0; ia.nimg = std::min(nbmax, (int)N - i0);
+        ScopedTimer tm(m, T_IMPUTE, st);
+        launch_impute_rows(ia, false, st);
+        HIPCHK(hipGetLastError());
+    }
+    // pass (b): per image the maximum, the sum, log_px and ess, in sample order
+    ImputeStatsArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.log_w = logwd; sa.N = N; sa.S = S; sa.log_px = ptr<double>(w.lpx); sa.ess = want_ess ? ptr<float>(w.ess) : nullptr; sa.wstat = ptr<float2>(w.wstat);
+    launch_impute_stats(sa, st);
+    HIPCHK(hipGetLastError());
+    iw.logwd = logwd; iw.nbmax = nbmax; iw.nchunk = nchunk;
     return IWAE_OK;
 }
 
@@ -639,67 +716,20 @@ int iwae_impute(iwae_handle m, const float* x, int32_t N, const iwae_impute_opti
     if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "impute: need x, options and outputs");
     if (o->struct_size != sizeof(iwae_impute_options)) return fail(IWAE_ERR_ARG, "impute: iwae_impute_options.struct_size must be sizeof(iwae_impute_options) = " + std::to_string(sizeof(iwae_impute_options)));
     if (!out->log_px) return fail(IWAE_ERR_ARG, "impute: log_px is required");
-    if (N <= 0 || o->k < 1 || o->k > IMPUTE_K_MAX) return fail(IWAE_ERR_ARG, "impute: needs N > 0 and 1 <= k <= " + std::to_string(IMPUTE_K_MAX));
-    if (m->cfg.n_layers != 1) return fail(IWAE_ERR_ARG, "impute: only the 1-layer model");
-    if (m->C != 0 || m->has_prior) return fail(IWAE_ERR_ARG, "impute: only the unconditional model (cond_dim = 0, no learned prior)");
-    if ((int64_t)N * o->k > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "impute: too large (N * k > 2^27 rows)");
-    const int D = m->D[0], H = m->H[0], X = m->X, Dp = round_up(D, 16), Hp = round_up(H, 16), Xp = round_up(X, 16), Dh = m->Dp[0];
-    if (Hp > 16 * AIS_NT || Dp > 16 * AIS_DT) return fail(IWAE_ERR_ARG, "impute: needs n_hidden <= " + std::to_string(16 * AIS_NT) + " and n_latent <= " + std::to_string(16 * AIS_DT));
-    const int S = o->k;
+    CHK(impute_scope(m, "impute", N, o->k));
+    const int X = m->X, Xp = round_up(X, 16), S = o->k;
     EvalCall c;
     CHK(eval_begin(m, x, N, c));
     hipStream_t st = c.st;
     iwae_model::ImputeWs& w = m->imp;
-    // ---- the masked input xin = m ? x : 0 into the call's own buffer: what the encoder and the rows read from here on
-    const uint8_t* maskd = nullptr;
-    if (o->mask) {
-        CHK(staged_in(m, o->mask, w.mask, (size_t)N * X, &maskd));
-        CHK(ensure(w.xin, (size_t)N * X * 4, st));
-        launch_impute_mask(c.xd, maskd, (long)N * X, ptr<float>(w.xin), st);
-        HIPCHK(hipGetLastError());
-        c.xd = ptr<float>(w.xin);
-    }
-    // ---- encoder heads mu, sigma of the masked input (src/iwae1.py:39-42), in the eval precision
-    CHK(eval_heads(c, N));
-    CHK(eval_copy_heads(c, N, out->q_mu, out->q_sigma));
-    ImputeArgs ia;
-    memset(&ia, 0, sizeof(ia));
-    {
-        DecPad p;
-        CHK(pad_decoder(m, st, Dp, Hp, Xp, p));
-        ia.W1 = p.W1; ia.W2 = p.W2; ia.W3 = p.W3; ia.b1 = p.b1; ia.b2 = p.b2; ia.b3 = p.b3;
-    }
-    const float* epsd = nullptr;
-    if (o->eps) CHK(staged_in(m, o->eps, w.eps, (size_t)S * N * D * 4, &epsd));
-    float *logwd = nullptr, *xhatd = nullptr;
-    CHK(staged_out(m, out->log_w, w.logw, (size_t)S * N * 4, &logwd));      // (always computed: passes (b) and (c) read it)
+    ImputeWeights iw;
+    CHK(impute_weights(c, N, S, o->mask, o->eps, out->log_w, out->ess != nullptr, out->q_mu, out->q_sigma, iw));
+    ImputeArgs& ia = iw.ia;
+    const int nbmax = iw.nbmax, nchunk = iw.nchunk;
+    float* xhatd = nullptr;
     if (out->xhat) CHK(staged_out(m, out->xhat, w.xhat, (size_t)N * X * 4, &xhatd));
-    CHK(ensure(w.wstat, (size_t)N * 8, st));
-    CHK(ensure(w.lpx, (size_t)N * 8, st));
-    if (out->ess) CHK(ensure(w.ess, (size_t)N * 4, st));
-    // ---- launches of whole images, at most `cap` rows each
-    const int cap = m->opt.impute_rows > 0 ? m->opt.impute_rows : IMPUTE_ROWS_DEFAULT;
-    const int nbmax = std::min((int)N, std::max(1, cap / S)), nchunk = S > 64 ? (S + 63) / 64 : 1;
     if (xhatd && nchunk > 1) CHK(ensure(w.part, (size_t)nbmax * nchunk * Xp * 4, st));
-    ia.D = D; ia.H = H; ia.X = X; ia.Dp = Dp; ia.Hp = Hp; ia.Xp = Xp;
-    ia.x = c.xd; ia.mask = maskd; ia.head = c.head; ia.ldh = c.ldh; ia.soff = Dh;
-    ia.N = N; ia.S = S; ia.ipw = S <= 64 ? 64 / S : 1; ia.nchunk = nchunk;
-    ia.eps = epsd; ia.seed = m->cfg.seed; ia.row_offset = (uint64_t)m->batch_offset * (uint64_t)S; ia.step = m->noise_step;
-    ia.log_w = logwd; ia.wstat = ptr<float2>(w.wstat); ia.xhat = xhatd; ia.part = nchunk > 1 ? ptr<float>(w.part) : nullptr;
-    m->time_this = m->timing > 0;
-    // pass (a): log_w of every row
-    for (int i0 = 0; i0 < N; i0 += nbmax) {
-        ia.img0 = i0; ia.nimg = std::min(nbmax, (int)N - i0);
-        ScopedTimer tm(m, T_IMPUTE, st);
-        launch_impute_rows(ia, false, st);
-        HIPCHK(hipGetLastError());
-    }
-    // pass (b): per image the maximum, the sum, log_px and ess, in sample order
-    ImputeStatsArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.log_w = logwd; sa.N = N; sa.S = S; sa.log_px = ptr<double>(w.lpx); sa.ess = out->ess ? ptr<float>(w.ess) : nullptr; sa.wstat = ptr<float2>(w.wstat);
-    launch_impute_stats(sa, st);
-    HIPCHK(hipGetLastError());
+    ia.xhat = xhatd; ia.part = nchunk > 1 ? ptr<float>(w.part) : nullptr;
     // pass (c): the decoder once more with the weights final (only when xhat is wanted)
     for (int i0 = 0; xhatd && i0 < N; i0 += nbmax) {
         ia.img0 = i0; ia.nimg = std::min(nbmax, (int)N - i0);
@@ -718,10 +748,99 @@ int iwae_impute(iwae_handle m, const float* x, int32_t N, const iwae_impute_opti
     m->time_this = false;
     CHK(copy_out(m, out->log_px, w.lpx.p, (size_t)N * 8));
     if (out->ess) CHK(copy_out(m, out->ess, w.ess.p, (size_t)N * 4));
-    CHK(finish_out(m, out->log_w, logwd, (size_t)S * N * 4));
+    CHK(finish_out(m, out->log_w, iw.logwd, (size_t)S * N * 4));
     CHK(finish_out(m, out->xhat, xhatd, (size_t)N * X * 4));
     CHK(eval_end(c));
     if (!o->eps) m->noise_step += 1;
+    return IWAE_OK;
+}
+
+// SNIS latent mean and covariance and sampling importance resampling on iwae_impute's weights: DESIGN.md section 18
+int iwae_posterior(iwae_handle m, const float* x, int32_t N, const iwae_posterior_options* o, const iwae_posterior_outputs* out) {
+    if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "posterior: need x, options and outputs");
+    if (o->struct_size != sizeof(iwae_posterior_options)) return fail(IWAE_ERR_ARG, "posterior: iwae_posterior_options.struct_size must be sizeof(iwae_posterior_options) = " + std::to_string(sizeof(iwae_posterior_options)));
+    if (o->reserved != 0) return fail(IWAE_ERR_ARG, "posterior: iwae_posterior_options.reserved must be 0");
+    if (!out->log_px) return fail(IWAE_ERR_ARG, "posterior: log_px is required");
+    CHK(impute_scope(m, "posterior", N, o->k));
+    if (o->R < 0 || o->R > POSTERIOR_R_MAX) return fail(IWAE_ERR_ARG, "posterior: needs 0 <= R <= " + std::to_string(POSTERIOR_R_MAX));
+    if ((int64_t)N * o->R > (int64_t)1 << 27) return fail(IWAE_ERR_ARG, "posterior: too large (N * R > 2^27 draws)");
+    if (o->R == 0 && (out->idx || out->z || out->u)) return fail(IWAE_ERR_ARG, "posterior: idx, z and u need R > 0");
+    const int D = m->D[0], Dp = round_up(D, 16), S = o->k, R = o->R;
+    const bool want_mom = out->mean || out->cov, want_sir = R > 0 && (out->idx || out->z || out->u);
+    EvalCall c;
+    CHK(eval_begin(m, x, N, c));
+    hipStream_t st = c.st;
+    iwae_model::ImputeWs& w = m->imp;
+    iwae_model::PosteriorWs& pw = m->post;
+    ImputeWeights iw;
+    CHK(impute_weights(c, N, S, o->mask, o->eps, out->log_w, out->ess != nullptr, out->q_mu, out->q_sigma, iw));
+    const ImputeArgs& ia = iw.ia;
+    // ---- the moments: launches of whole images, cut by pass (a)'s cap and by the size of the chunk sums
+    float *meand = nullptr, *covd = nullptr;
+    if (want_mom) {
+        const int nchunk = (S + 63) / 64;
+        const size_t stride = posterior_part_floats(Dp);
+        const int nbm = (int)std::min<size_t>((size_t)iw.nbmax, std::max<size_t>(1, POSTERIOR_PART_FLOATS / ((size_t)nchunk * stride)));
+        if (out->mean) CHK(staged_out(m, out->mean, pw.mean, (size_t)N * D * 4, &meand));
+        if (out->cov) CHK(staged_out(m, out->cov, pw.cov, (size_t)N * D * D * 4, &covd));
+        CHK(ensure(pw.part, (size_t)nbm * nchunk * stride * 4, st));
+        PosteriorMomArgs pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.D = D; pa.Dp = Dp; pa.N = N; pa.S = S; pa.nchunk = nchunk; pa.want_cov = covd ? 1 : 0;
+        pa.eps = ia.eps; pa.seed = ia.seed; pa.row_offset = ia.row_offset; pa.step = ia.step;
+        pa.log_w = iw.logwd; pa.wstat = ia.wstat; pa.part = ptr<float>(pw.part);
+        PosteriorMergeArgs ma;
+        memset(&ma, 0, sizeof(ma));
+        ma.part = pa.part; ma.nchunk = nchunk; ma.D = D; ma.Dp = Dp; ma.head = c.head; ma.ldh = c.ldh; ma.soff = ia.soff; ma.mean = meand; ma.cov = covd;
+        for (int i0 = 0; i0 < N; i0 += nbm) {
+            pa.img0 = ma.img0 = i0; pa.nimg = ma.nimg = std::min(nbm, (int)N - i0);
+            ScopedTimer tm(m, T_POSTERIOR, st);
+            launch_posterior_moments(pa, st);
+            launch_posterior_merge(ma, st);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    m->time_this = false;
+    // ---- the resampling: per launch the running sums of its images, the picks, the picked draws' z
+    int32_t* idxd = nullptr;
+    float *zd = nullptr, *ud = nullptr;
+    if (want_sir) {
+        const float* unifd = nullptr;
+        if (o->unif) CHK(staged_in(m, o->unif, pw.unif, (size_t)R * N * 4, &unifd));
+        CHK(staged_out(m, out->idx, pw.idx, (size_t)R * N * 4, &idxd));      // (always computed: the gather reads it)
+        if (out->z) CHK(staged_out(m, out->z, pw.z, (size_t)R * N * D * 4, &zd));
+        if (out->u) CHK(staged_out(m, out->u, pw.u, (size_t)R * N * 4, &ud));
+        CHK(ensure(pw.cdf, (size_t)iw.nbmax * S * 8, st));
+        PosteriorCdfArgs ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.log_w = iw.logwd; ca.wstat = ia.wstat; ca.N = N; ca.S = S; ca.cdf = ptr<double>(pw.cdf);
+        PosteriorPickArgs ka;
+        memset(&ka, 0, sizeof(ka));
+        ka.cdf = ca.cdf; ka.N = N; ka.S = S; ka.R = R; ka.top = 1;
+        while (2 * ka.top <= S) ka.top *= 2;
+        ka.unif = unifd; ka.seed = ia.seed; ka.batch_offset = m->batch_offset; ka.step = m->noise_step; ka.idx = idxd; ka.u = ud;
+        PosteriorGatherArgs ga;
+        memset(&ga, 0, sizeof(ga));
+        ga.idx = idxd; ga.D = D; ga.Dp = Dp; ga.N = N; ga.S = S; ga.R = R; ga.head = c.head; ga.ldh = c.ldh; ga.soff = ia.soff;
+        ga.eps = ia.eps; ga.seed = ia.seed; ga.row_offset = ia.row_offset; ga.step = ia.step; ga.z = zd;
+        for (int i0 = 0; i0 < N; i0 += iw.nbmax) {
+            ca.img0 = ka.img0 = ga.img0 = i0; ca.nimg = ka.nimg = ga.nimg = std::min(iw.nbmax, (int)N - i0);
+            launch_posterior_cdf(ca, st);
+            launch_posterior_pick(ka, st);
+            if (zd) launch_posterior_gather(ga, st);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    CHK(copy_out(m, out->log_px, w.lpx.p, (size_t)N * 8));
+    if (out->ess) CHK(copy_out(m, out->ess, w.ess.p, (size_t)N * 4));
+    CHK(finish_out(m, out->log_w, iw.logwd, (size_t)S * N * 4));
+    CHK(finish_out(m, out->mean, meand, (size_t)N * D * 4));
+    CHK(finish_out(m, out->cov, covd, (size_t)N * D * D * 4));
+    CHK(finish_out(m, out->idx, idxd, (size_t)R * N * 4));
+    CHK(finish_out(m, out->z, zd, (size_t)R * N * D * 4));
+    CHK(finish_out(m, out->u, ud, (size_t)R * N * 4));
+    CHK(eval_end(c));
+    if (!o->eps || (want_sir && !o->unif)) m->noise_step += 1;
     return IWAE_OK;
 }
 

@@ -641,4 +641,48 @@ void launch_impute_rows(const ImputeArgs& a, bool xhat, hipStream_t st);
 void launch_impute_stats(const ImputeStatsArgs& a, hipStream_t st);
 void launch_impute_merge(const ImputeMergeArgs& a, hipStream_t st);
 
+// ---- SNIS latent moments and posterior resampling (posterior_kernels.hip; iwae_posterior): on the log_w [S][N] and wstat of iwae_impute's
+// passes (a) and (b).  The moments are taken in the standardised variable e (z = mu + sigma e): a workgroup owns chunk c of
+// nchunk = ceil(S / 64) of one image; a launch holds the whole images [img0, img0 + nimg).  A draw is regenerated from its index, never stored.
+struct PosteriorMomArgs {             // posterior_moments_kernel: per chunk m1[d] = sum_s al_s e_sd and (cov wanted) m2[d][d'] = sum_s (al_s e_sd) e_sd', d-tile <= d'-tile
+    int D, Dp;
+    int N, S, nchunk;                 // N: the call's images (the stride of eps and log_w)
+    int img0, nimg;                   // this launch's images
+    int want_cov;
+    const float* eps;                 // the caller's draws [S][N][D] or null: Philox stream 0 at `step`, row row_offset + n S + s
+    uint64_t seed, row_offset; uint32_t step;
+    const float* log_w;               // [S][N]
+    const float2* wstat;              // [N]: (max_s log_w, 1 / sum_s exp(log_w - max))
+    float* part;                      // [nimg][nchunk][Dp Dp + Dp]: m2 (row-major, the upper tiles only), then m1
+};
+struct PosteriorMergeArgs {           // posterior_merge_kernel: the chunks in chunk order in double -> mean [N][D], cov [N][D][D]
+    const float* part; int nimg, nchunk, D, Dp, img0;
+    const float* head; int ldh, soff;
+    float *mean, *cov;                // either may be null
+};
+struct PosteriorCdfArgs {             // posterior_expw_kernel, then posterior_cdf_kernel: c[s][i] = sum_{j <= s} exp((double)(log_w_j - max)), image img0 + i, sample order
+    const float* log_w; const float2* wstat; int N, S, img0, nimg;
+    double* cdf;                      // [S][nimg]
+};
+struct PosteriorPickArgs {            // posterior_pick_kernel: idx[r][n] = the smallest s with c_s > u c_{S-1} (u = 1: the first s that reaches c_{S-1})
+    const double* cdf; int N, S, R, img0, nimg, top;      // top: the largest power of two <= S
+    const float* unif;                // the caller's uniforms [R][N] or null: Philox stream 5 at `step`, row (batch_offset + n) R + r, word 0
+    uint64_t seed, batch_offset; uint32_t step;
+    int32_t* idx;                     // [R][N]
+    float* u;                         // [R][N] or null: the uniforms used
+};
+struct PosteriorGatherArgs {          // posterior_gather_kernel: z[r][n] = mu + exp(log sigma) e_idx, e regenerated (or gathered from the caller's eps)
+    const int32_t* idx; int D, Dp, N, S, R, img0, nimg;
+    const float* head; int ldh, soff;
+    const float* eps; uint64_t seed, row_offset; uint32_t step;
+    float* z;                         // [R][N][D]
+};
+size_t posterior_lds_bytes(int Dp);
+size_t posterior_part_floats(int Dp);      // per (image, chunk)
+void launch_posterior_moments(const PosteriorMomArgs& a, hipStream_t st);
+void launch_posterior_merge(const PosteriorMergeArgs& a, hipStream_t st);
+void launch_posterior_cdf(const PosteriorCdfArgs& a, hipStream_t st);
+void launch_posterior_pick(const PosteriorPickArgs& a, hipStream_t st);
+void launch_posterior_gather(const PosteriorGatherArgs& a, hipStream_t st);
+
 }  // namespace iwae

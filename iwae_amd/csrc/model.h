@@ -54,7 +54,7 @@ template <class Ws> void free_all(Ws& ws) {
 }
 
 // kernels iwae_enable_timing brackets with HIP events (on the stream each is launched on); names: iwae_kernel_time
-enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_IMPUTE, T_COUNT };
+enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_IMPUTE, T_POSTERIOR, T_COUNT };
 
 // What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
 // images and samples in chunks and needs log_w only.
@@ -315,6 +315,9 @@ struct iwae_model {
     // iwae_impute's buffers (the padded weights are ais.wpad): the masked input, the caller's mask and noise when they arrive on the host,
     // the log-weights, per image (max, 1 / sum), the chunk sums of xhat (more than 64 draws per image) and the outputs
     struct ImputeWs { DevBuf xin, mask, eps, logw, wstat, part, lpx, ess, xhat; } imp;
+    // iwae_posterior's buffers beyond those (it shares imp with iwae_impute): the chunk moments and the running sums of a launch, the
+    // caller's uniforms when they arrive on the host, and the outputs
+    struct PosteriorWs { DevBuf part, cdf, unif, mean, cov, idx, z, u; } post;
     bool fwd_was_f32 = false;                 // the last forward ran in float32 mode (its backward must too)
     // data-parallel training inside the library (iwae_comm_init): one communicator per stream that carries a collective
     ncclComm_t comm_main = nullptr, comm_side = nullptr;

@@ -24,6 +24,9 @@ static_assert(sizeof(iwae_local_options) == 64 && offsetof(iwae_local_options, o
               offsetof(iwae_local_options, mu0) == 40 && offsetof(iwae_local_options, eps) == 56 && sizeof(iwae_local_outputs) == 9 * sizeof(void*), "iwae_local_options / iwae_local_outputs layout is part of the ABI (iwae_amd/_capi.py)");
 static_assert(sizeof(iwae_impute_options) == 24 && offsetof(iwae_impute_options, k) == 4 && offsetof(iwae_impute_options, mask) == 8 && offsetof(iwae_impute_options, eps) == 16 &&
               sizeof(iwae_impute_outputs) == 6 * sizeof(void*), "iwae_impute_options / iwae_impute_outputs layout is part of the ABI (iwae_amd/_capi.py)");
+static_assert(sizeof(iwae_posterior_options) == 40 && offsetof(iwae_posterior_options, k) == 4 && offsetof(iwae_posterior_options, R) == 8 && offsetof(iwae_posterior_options, reserved) == 12 &&
+              offsetof(iwae_posterior_options, mask) == 16 && offsetof(iwae_posterior_options, eps) == 24 && offsetof(iwae_posterior_options, unif) == 32 &&
+              sizeof(iwae_posterior_outputs) == 10 * sizeof(void*), "iwae_posterior_options / iwae_posterior_outputs layout is part of the ABI (iwae_amd/_capi.py)");
 
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -71,7 +74,8 @@ static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgra
                                                  "allreduce_enc", "allreduce_dec",       // (the data-parallel step's two ncclAllReduce calls, each on its own stream)
                                                  "ais_chain",                            // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
                                                  "local_q",                              // (iwae_local_posterior: likewise local_q_kernel)
-                                                 "impute"};                              // (iwae_impute: likewise both passes of impute_rows_kernel)
+                                                 "impute",                               // (iwae_impute: likewise both passes of impute_rows_kernel)
+                                                 "posterior"};                           // (iwae_posterior: likewise its moments and merge launches)
 
 namespace {      // (closed and reopened around each helper that model.h declares for step_f32.hip; what is added in between stays internal)
 
@@ -1748,6 +1752,7 @@ void iwae_destroy(iwae_handle m) {
     free_all(m->ais);
     free_all(m->loc);
     free_all(m->imp);
+    free_all(m->post);
     for (BlockWs* w : {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior}) free_all(*w);
     free_all(m->wdec1);
     free_all(m->f32);

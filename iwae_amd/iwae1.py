@@ -158,3 +158,25 @@ class IWAE(BaseIWAE):
         r = self.impute(X, None, n_samples=n_samples, **kwargs)
         r["xhat"] = r["xhat_raw"]
         return r
+
+    # ---- the posterior in latent space: SNIS moments and sampling importance resampling (the reference's README; tasks/task01.py:52-58)
+    def posterior(self, X, mask=None, n_samples=5000, n_draws=0, **kwargs):
+        """The self-normalised estimates of the mean and covariance of p(z | x_obs) of every image of X, and n_draws latent vectors per
+        image resampled from it (iwae_posterior; kwargs: noise, uniforms, outputs).  Returns the binding's dict."""
+        if self._net.cond_dim:
+            raise NotImplementedError("the latent posterior covers the unconditional 1-layer model only")
+        X = np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim)
+        return self._net.posterior(X, mask=mask, n_samples=n_samples, n_draws=n_draws, **kwargs)
+
+    def multiple_imputations(self, X, mask, n_samples=5000, n_draws=5, seed=0, **kwargs):
+        """Mattei & Frellsen's multiple imputation: n_draws latent vectors per image by SIR from the n_samples importance draws given the
+        observed pixels, decoded, the unobserved pixels sampled Bernoulli(sigmoid(l)) on the host (seed), the observed ones put back
+        exactly as given.  Returns [n_draws, N, x_dim] float32."""
+        X = np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim)
+        r = self.posterior(X, mask=mask, n_samples=n_samples, n_draws=n_draws, outputs=("z",), **kwargs)
+        R, N = int(n_draws), X.shape[0]
+        probs = self._net.decode(r["z"].reshape(R * N, -1)).reshape(R, N, -1)
+        draws = (np.random.default_rng(seed).random(probs.shape) < probs).astype(np.float32)
+        if mask is None:
+            return np.ascontiguousarray(np.broadcast_to(X[None], draws.shape))
+        return np.where(np.asarray(mask).reshape(X.shape)[None] != 0, X[None], draws).astype(np.float32)

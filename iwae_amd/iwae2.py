@@ -59,3 +59,9 @@ class IWAE(BaseIWAE):
 
     def reconstruct(self, X, n_samples=50, **kwargs):
         self.impute(None, None)
+
+    def posterior(self, X, mask=None, n_samples=5000, n_draws=0, **kwargs):
+        raise ValueError("the latent posterior covers the 1-layer model only: the 2-layer proposal q(z2|z1) q(z1|x) needs its own weights")
+
+    def multiple_imputations(self, X, mask, n_samples=5000, n_draws=5, seed=0, **kwargs):
+        self.posterior(None)

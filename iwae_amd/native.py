@@ -7,8 +7,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (AIS_INITS, IMPUTE_OUTPUT_FIELDS, LOCAL_OBJECTIVES, OBJECTIVES, PRECISIONS, AisOptions, AisOutputs, Config, ImputeOptions, ImputeOutputs,
-                    LocalOptions, LocalOutputs, Scalars, Tensors, check)
+from ._capi import (AIS_INITS, IMPUTE_OUTPUT_FIELDS, LOCAL_OBJECTIVES, OBJECTIVES, POSTERIOR_OUTPUT_FIELDS, PRECISIONS, AisOptions, AisOutputs, Config, ImputeOptions,
+                    ImputeOutputs, LocalOptions, LocalOutputs, PosteriorOptions, PosteriorOutputs, Scalars, Tensors, check)
 
 _SCALAR_NAMES = ("vae_elbo", "vae_elbo_kl", "iwae_elbo", "iwae_eq14", "inference_loss",
                  "mean_lpxz", "mean_lpz", "mean_lqzx", "mean_kl")
@@ -491,6 +491,52 @@ class NativeModel:
         for name, arr in res.items():
             setattr(outs, name, arr.ctypes.data)
         check(self.lib.iwae_impute(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
+        return res
+
+    def posterior(self, x, mask=None, n_samples=5000, n_draws=0, noise=None, uniforms=None, outputs=None):
+        """iwae_posterior: on the n_samples importance draws iwae_impute would take for the images x [N, x_dim] (mask, noise: as impute),
+        the self-normalised estimates mean [N, D] and cov [N, D, D] of the posterior p(z | x_obs), and n_draws latent vectors per image
+        resampled from it with replacement (SIR): idx [n_draws, N] (int32, into the proposals), z [n_draws, N, D], u [n_draws, N] the
+        uniforms used.  uniforms [n_draws, N] replaces the device generator; u_r = (r + u0) / n_draws gives systematic resampling.  The
+        noise step advances by one unless everything drawn was the caller's.  outputs: which of log_px [N] (float64; always), ess, mean,
+        cov, idx, z, u, log_w [n_samples, N], q_mu, q_sigma to return (None: all, idx / z / u only when n_draws > 0).  Returns a dict."""
+        x = _f32(x).reshape(-1, self.x_dim)
+        N, D, S, R = x.shape[0], self.n_latent[0], int(n_samples), int(n_draws)
+        if outputs is None:
+            outputs = tuple(f for f in POSTERIOR_OUTPUT_FIELDS if R > 0 or f not in ("idx", "z", "u"))
+        unknown = set(outputs) - set(POSTERIOR_OUTPUT_FIELDS)
+        if unknown:
+            raise ValueError("posterior: unknown outputs %s (known: %s)" % (sorted(unknown), ", ".join(POSTERIOR_OUTPUT_FIELDS)))
+        o = PosteriorOptions()
+        o.k, o.R = S, R
+        keep = []
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1, self.x_dim)
+            if mk.shape != x.shape:
+                raise ValueError("posterior: mask must be [N, x_dim] = %s, got %s" % (x.shape, mk.shape))
+            o.mask = mk.ctypes.data
+            keep.append(mk)
+        n0, s0, r0 = max(N, 0), max(S, 0), max(R, 0)      # (bad counts: the library rejects them; nothing is written)
+        if noise is not None:
+            e = _f32(noise)
+            if e.shape != (s0, n0, D):
+                raise ValueError("posterior: noise must be [n_samples, N, %d] = %s, got %s" % (D, (s0, n0, D), e.shape))
+            o.eps = e.ctypes.data
+            keep.append(e)
+        if uniforms is not None:
+            un = _f32(uniforms)
+            if un.shape != (r0, n0):
+                raise ValueError("posterior: uniforms must be [n_draws, N] = %s, got %s" % ((r0, n0), un.shape))
+            o.unif = un.ctypes.data
+            keep.append(un)
+        shapes = {"log_px": ((n0,), np.float64), "ess": ((n0,), np.float32), "mean": ((n0, D), np.float32), "cov": ((n0, D, D), np.float32),
+                  "idx": ((r0, n0), np.int32), "z": ((r0, n0, D), np.float32), "u": ((r0, n0), np.float32),
+                  "log_w": ((s0, n0), np.float32), "q_mu": ((n0, D), np.float32), "q_sigma": ((n0, D), np.float32)}
+        res = {name: np.empty(*shapes[name]) for name in POSTERIOR_OUTPUT_FIELDS if name == "log_px" or name in outputs}
+        outs = PosteriorOutputs()
+        for name, arr in res.items():
+            setattr(outs, name, arr.ctypes.data)
+        check(self.lib.iwae_posterior(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
         return res
 
     def grad_moments(self, x, k, draws, beta=1.0, objective="iwae_elbo"):
