@@ -125,7 +125,7 @@ struct DecBwdRowsArgs {               // dec_bwd_rows_kernel: the decoder's dX c
     LseArgs lse;
 };
 bool dec_bwd_rows_ok(const DecBwdRowsArgs& a);
-void launch_dec_bwd_rows(const DecBwdRowsArgs& a, hipStream_t st);
+void launch_dec_bwd_rows(const DecBwdRowsArgs& a, hipStream_t st, hipEvent_t done = nullptr);
 
 struct LatentBwdArgs {
     const float* dz; int ldDZ;
@@ -255,7 +255,7 @@ struct GBlockBwdArgs {                // gblock_bwd_kernel: backward of a per-sa
     uint16_t* DZOUT;                  // MODE 1: the three terms of dz1 summed, bf16 [M][32*KTIN] natural feature order (latent_bwd_kernel's input)
 };
 bool gblock_bwd_ok(int KT0, int KTH, int KT1, int M);
-void launch_gblock_bwd(int mode, const GBlockBwdArgs& a, hipStream_t st);
+void launch_gblock_bwd(int mode, const GBlockBwdArgs& a, hipStream_t st, hipEvent_t done = nullptr);
 
 struct GaussLpArgs {
     const float* zhead; int ldZH; int Dzp;   // head that generated z (per image)
@@ -290,16 +290,15 @@ struct LayerDesc {
     int rblock_begin;                 // same for the slab-reduce grid (64 elements per block)
 };
 
-// arms a completion event for the NEXT launch_dense / launch_out_bwd / launch_reduce_grads of this thread: it rides on that
-// kernel's dispatch packet (cheaper on both streams than hipEventRecord behind the kernel); consumed by that launch
-void set_launch_stop_event(hipEvent_t e);
-void launch_dense(int epi, const DenseArgs& a, hipStream_t st);
-void launch_out_bwd(const OutBwdArgs& a, hipStream_t st);
+// done (here and below): a completion event that rides on the launch's dispatch packet (cheaper on both streams than hipEventRecord behind
+// the kernel: LAUNCH_EV in step_helpers.h); launch_out_bwd gives it to its LAST kernel.  A launcher without the argument cannot carry one.
+void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done = nullptr);
+void launch_out_bwd(const OutBwdArgs& a, hipStream_t st, hipEvent_t done = nullptr);
 bool bern_lse_ok(const DenseArgs& a);   // ... and can take lse_kernel's work for its rows (DenseArgs.lse_on)
 bool bern_pipe_ok(const DenseArgs& a);  // shapes bern_pipe_kernel covers (launch_dense falls back to dense_kernel<EPI_BERN> otherwise)
 bool out_bwd_has_s_mode(int KT);      // hidden widths with a compiled out_bwd_s_kernel / dec_bwd_kernel
-void launch_dec_bwd(const DecBwdArgs& d, hipStream_t st);
-void launch_wgradp(const WgradPArgs& a, int nsplit, int shape, hipStream_t st);      // shape: see wgradp_strip
+void launch_dec_bwd(const DecBwdArgs& d, hipStream_t st, hipEvent_t done = nullptr);
+void launch_wgradp(const WgradPArgs& a, int nsplit, int shape, hipStream_t st, hipEvent_t done = nullptr);      // shape: see wgradp_strip
 int wgradp_strip(int shape);          // j-tiles (16 out-features each) per block of a shape: 8 -> 8, 16 / 7 -> 16
 void launch_wgradp_group(const WgradPGroup& g, hipStream_t st);
 void launch_wgradws_group(const WgradPGroup& g, hipStream_t st);     // shape-7 (specialised waves) gradients, non-row-weighted, in one launch
@@ -311,7 +310,7 @@ void launch_eps_gen(const EpsSrc& e, int M, int D, int ld, float* out, hipStream
 void launch_eps_gen_multi(const EpsSrc& e, int M, int D, int ld, float* out, int nsteps, size_t step_stride, hipStream_t st);   // steps e.step .. e.step + nsteps - 1, step s at out + s * step_stride
 void launch_sample(const SampleArgs& a, hipStream_t st);
 void launch_gauss_lp(const GaussLpArgs& a, hipStream_t st);
-void launch_lse(const LseArgs& a, hipStream_t st);
+void launch_lse(const LseArgs& a, hipStream_t st, hipEvent_t done = nullptr);
 void launch_latent_bwd(const LatentBwdArgs& a, hipStream_t st);
 void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st);
 // Sums the slabs of reduce blocks [first_block, first_block + nblocks) of the layer table into the flat gradient.
@@ -319,13 +318,13 @@ void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st);
 // fuse_adam: the Adam update (grad_scale 1) + weight-image refresh of each element follows its slab sum in the same thread.
 void launch_reduce_grads(const LayerDesc* layers, int nlayers, int first_block, int nblocks, float* grad, float* param, float* mom, float* vel,
                          float alpha, float beta1, float beta2, float eps, int fuse_adam, const float* per_b, int B, float beta, float* scalars, hipStream_t st,
-                         int first_block2 = 0, int nblocks2 = 0);      // (optional second block range of the same launch)
+                         int first_block2 = 0, int nblocks2 = 0, hipEvent_t done = nullptr);      // (optional second block range of the same launch)
 // fuse_adam: Keras Adam (grad_scale 1) + image refresh in the epilogue; per_b != null: one extra block makes the step's batch means
 void launch_wgrad_rows(const WgradRowsJob* jobs, int njobs, const LayerDesc* layers, float* grad, float* param, float* mom, float* vel, float alpha,
                        float beta1, float beta2, float eps, int fuse_adam, const float* per_b, int B, float beta, float* scalars, const char* zero, hipStream_t st);
 void launch_scalars(const float* per_b, int B, float beta, float* out, hipStream_t st);
 void launch_adam(const LayerDesc* layers, int nlayers, int nblocks, float* param, const float* grad, float* mom, float* vel,
-                 float alpha, float gscale, float beta1, float beta2, float eps, int do_update, hipStream_t st, int first_block = 0);   // blocks [first_block, first_block + nblocks) of the elementwise grid
+                 float alpha, float gscale, float beta1, float beta2, float eps, int do_update, hipStream_t st, int first_block = 0, hipEvent_t done = nullptr);   // blocks [first_block, first_block + nblocks) of the elementwise grid
 void launch_export_rows(const float* in, int B, int k, float* out, hipStream_t st);
 void launch_export_z(const SampleArgs& a, float* zout, hipStream_t st);
 void launch_snis(const float* z, const float* wn, int B, int k, int D, float* out, hipStream_t st);

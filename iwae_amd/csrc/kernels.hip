@@ -16,96 +16,9 @@
 #include "kernels.h"
 #include "layout.h"
 #include "device_helpers.h"
+#include "step_helpers.h"
 
-#ifdef IWAE_DIAG
-#define WG_DBG(a, bit) (((a).dbg & (bit)) != 0)
-#else
-#define WG_DBG(a, bit) false
-#endif
 namespace iwae {
-
-// 4 consecutive eps values for features 4*d4 .. 4*d4+3 of data row (b,s)
-__device__ __forceinline__ void eps4(const EpsSrc& e, int b, int s, int row, int d4, int D, float n[4]) {
-    if (e.cache) {
-        const float4 v = *(const float4*)(e.cache + (size_t)row * e.ldC + 4 * d4);
-        n[0] = v.x; n[1] = v.y; n[2] = v.z; n[3] = v.w;
-    } else if (e.user) {
-        const float* p = e.user + ((size_t)s * e.B + b) * D + 4 * d4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) n[i] = (4 * d4 + i < D) ? p[i] : 0.0f;
-    } else {
-        const uint64_t grow = e.k_total ? e.row_offset + (uint64_t)b * (uint64_t)e.k_total + (uint64_t)(e.s_off + s) : e.row_offset + (uint64_t)row;
-        normal4(grow, (uint32_t)d4, e.stream, e.step, e.seed, n);
-    }
-}
-
-// One 32-feature step t of z = mu + sigma*eps for the lane's (row, quad): the lane's 8 features of P-layout chunk 4t+q (features
-// 32t+4q..+3 and 32t+16+4q..+3) and their contributions to the row's log-densities (sample_kernel; block_fwd_kernel's sampling mode)
-__device__ __forceinline__ void sample_step(const SampleArgs& a, int t, int q, int rowc, int b, int s, const float* hd, float z8[8], float& lp, float& lq, float& lq2) {
-    // Round 5: the density arithmetic in the decoder kernel's new form -- a density scored at its own sample has (z - mu)/sigma = eps, the
-    // chunks that straddle or lie beyond the latent width take a wave-uniform masked path instead of a branch per element, and the
-    // log-scales are summed as log2 of pair products (one v_log per 2 elements; __logf was ~12 instructions per element).  The k = 5000
-    // evaluator's sampling pass is this function behind Philox + Box-Muller: 107 us per 520 k rows before.
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int f0 = 32 * t + 16 * h + 4 * q;
-        float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        float4 mu4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sg4 = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-        float4 pm4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ps4 = make_float4(1.0f, 1.0f, 1.0f, 1.0f);     // prior: N(0,1) unless a head is given
-        if (f0 < a.D) {
-            eps4(a.eps, b, s, rowc, f0 >> 2, a.D, e);
-            mu4 = *(const float4*)(hd + f0);
-            sg4 = *(const float4*)(hd + a.Dp + f0);
-            if (a.prior_head) {      // learned conditional prior p(z|y) of tasks/task04.py:124-130, one head per image
-                pm4 = *(const float4*)(a.prior_head + (size_t)b * a.ldH + f0);
-                ps4 = *(const float4*)(a.prior_head + (size_t)b * a.ldH + a.Dp + f0);
-            }
-        }
-        float muv[4] = {mu4.x, mu4.y, mu4.z, mu4.w}, sgv[4] = {sg4.x, sg4.y, sg4.z, sg4.w};
-        float pmv[4] = {pm4.x, pm4.y, pm4.z, pm4.w}, psv[4] = {ps4.x, ps4.y, ps4.z, ps4.w};
-        float cnt = 4.0f;                                     // valid features of this chunk
-        const bool ragged = 32 * t + 16 * h + 16 > a.D;      // wave-uniform where t is (sample_kernel, block_fwd_kernel's sampling mode)
-        if (ragged) {
-            cnt = (float)max(0, min(4, a.D - f0));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const bool in = f0 + i < a.D;
-                e[i] = in ? e[i] : 0.0f; muv[i] = in ? muv[i] : 0.0f; sgv[i] = in ? sgv[i] : 1.0f;
-                pmv[i] = in ? pmv[i] : 0.0f; psv[i] = in ? psv[i] : 1.0f;
-            }
-        }
-        float sz = 0.0f, se = 0.0f, su = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float z = muv[i] + sgv[i] * e[i];                  // iwae1.py:59 (pad features: exactly 0)
-            se = fmaf(e[i], e[i], se);                               // iwae1.py:109: (z - mu)/sigma = eps
-            if (a.prior_head) {
-                const float up = (z - pmv[i]) * __builtin_amdgcn_rcpf(psv[i]);
-                sz = fmaf(up, up, sz);                               // task04.py:130
-            } else sz = fmaf(z, z, sz);                              // iwae1.py:107
-            if (a.lq_dreg) {                                         // tasks/task02.py:63-65: scale sigma + 1e-6
-                const float u2 = (sgv[i] * __builtin_amdgcn_rcpf(sgv[i] + 1e-6f)) * e[i];
-                su = fmaf(u2, u2, su);
-            }
-            z8[4 * h + i] = z;
-        }
-        if (a.cond && ragged) {      // decoder input = concat(z, y): the condition sits in the pad features behind D
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (f0 + i >= a.D && f0 + i < a.D + a.C) z8[4 * h + i] = a.cond[(size_t)b * a.C + (f0 + i - a.D)];
-        }
-        const float c0 = -0.5f * LOG2PI_F * cnt;
-        lp += fmaf(-0.5f, sz, c0) - (a.prior_head ? LN2_F * (log2_raw(psv[0] * psv[1]) + log2_raw(psv[2] * psv[3])) : 0.0f);
-        lq += fmaf(-0.5f, se, c0) - LN2_F * (log2_raw(sgv[0] * sgv[1]) + log2_raw(sgv[2] * sgv[3]));
-        if (a.lq_dreg) {
-            const float s20 = sgv[0] + 1e-6f, s21 = sgv[1] + 1e-6f, s22 = sgv[2] + 1e-6f, s23 = sgv[3] + 1e-6f;
-            const float m0 = ragged && !(f0 + 0 < a.D) ? 1.0f : s20, m1 = ragged && !(f0 + 1 < a.D) ? 1.0f : s21;
-            const float m2 = ragged && !(f0 + 2 < a.D) ? 1.0f : s22, m3 = ragged && !(f0 + 3 < a.D) ? 1.0f : s23;
-            lq2 += fmaf(-0.5f, su, c0) - LN2_F * (log2_raw(m0 * m1) + log2_raw(m2 * m3));
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------
 // Bernoulli log-likelihood of the lane's 8 logits of one 32-pixel step (accumulator tiles a0: pixels f0..f0+3,
 // a1: f0+16..f0+19, bias already in), x = the lane's 8 bf16 pixel values:
@@ -151,21 +64,6 @@ __device__ __forceinline__ float bern8(const f32x4& a0, const f32x4& a1, const u
 // so neither load latency nor store acknowledgement sits in front of a barrier.
 // ---------------------------------------------------------------------------------
 #define DENSE_UNIT 33792   // 8 k-steps x 4 KiB + 1 KiB bias block
-
-// diagnostic build only (./build.sh with STAMPS=1): per-phase s_memtime sums per wave -> a.stamps[wave][8]
-#ifdef IWAE_DENSE_STAMPS
-#define DS_STAMP(slot)                                                                 \
-    {                                                                                  \
-        unsigned long long t_;                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                             \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");     \
-        __builtin_amdgcn_sched_barrier(0);                                             \
-        ds_sum[slot] += t_ - ds_prev;                                                  \
-        ds_prev = t_;                                                                  \
-    }
-#else
-#define DS_STAMP(slot)
-#endif
 
 // G = 16-row column groups per wave.  G = 2: 4 waves x 32 rows, every weight fragment read from LDS feeds two MFMAs
 // (the LDS-frugal shape).  G = 1: 8 waves x 16 rows in <= 128 registers, i.e. FOUR waves per SIMD with two workgroups
@@ -931,180 +829,6 @@ __global__ __launch_bounds__(1024, 4) void block_bwd_kernel(BlockBwdArgs a) {
     for (int ks = 0; ks < BLOCKFWD_MAX_KT; ++ks)
         if (ks < a.KT1) acc = mfma16(A2[ks], *(const uint4*)(act1 + ks * 1024 + a_off), acc);
     if (has && valid) *(uint2*)(a.D1 + (size_t)row * a.ldH + kso * 32 + q * 8 + 4 * hh) = dtanh(acc, y1);
-}
-
-
-// Wave-wide sum / max through the DPP path (row_shr 1, 2, 4, 8, then row_bcast 15 and 31: the total arrives in lane 63 and is handed to
-// every lane through an SGPR): six vector instructions of ~10 cycles each, where the ds_bpermute butterfly of __shfl_xor is six LDS
-// round trips of ~100 -- lse_image is four such reductions deep, on the tail of the decoder kernel.
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float dpp_or(float old, float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROWMASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v += dpp_or<0x111, 0xf>(0.0f, v); v += dpp_or<0x112, 0xf>(0.0f, v); v += dpp_or<0x114, 0xf>(0.0f, v); v += dpp_or<0x118, 0xf>(0.0f, v);
-    v += dpp_or<0x142, 0xa>(0.0f, v);
-    v += dpp_or<0x143, 0xc>(0.0f, v);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, dpp_or<0x111, 0xf>(-INFINITY, v)); v = fmaxf(v, dpp_or<0x112, 0xf>(-INFINITY, v));
-    v = fmaxf(v, dpp_or<0x114, 0xf>(-INFINITY, v)); v = fmaxf(v, dpp_or<0x118, 0xf>(-INFINITY, v));
-    v = fmaxf(v, dpp_or<0x142, 0xa>(-INFINITY, v));
-    v = fmaxf(v, dpp_or<0x143, 0xc>(-INFINITY, v));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
-// What one wave does for image b: log_w over its k samples, logmeanexp / softmax / objective gradients (iwae1.py:113-139).  `src` says where
-// the rows' terms come from: LseGlobalSrc (lse_kernel: the arrays of LseArgs) or the LDS copies bern_pipe_kernel keeps of what it made itself.
-struct LseGlobalSrc {
-    __device__ __forceinline__ float px(const LseArgs& a, int, int r) const {
-        float px = a.term[0][r];
-        if (a.n_px_part > 1) {      // log p(x|z) as partial sums over pixel groups (small row counts): fixed order
-            // (all partials requested at once: as a loop of dependent adds each load waited for the one before it -- 13 L2 round
-            // trips, most of this kernel's 10 us at B = 20)
-            float part[16];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) part[i] = (i < a.n_px_part) ? a.term[0][(size_t)i * a.px_stride + r] : 0.0f;
-#pragma unroll
-            for (int i = 1; i < 16; ++i) px += part[i];
-            for (int i = 16; i < a.n_px_part; ++i) px += a.term[0][(size_t)i * a.px_stride + r];
-            a.term0_out[r] = px;
-        }
-        return px;
-    }
-    __device__ __forceinline__ float px_total(const LseArgs& a, int, int r) const { return a.term0_out[r]; }      // (total log p(x|z), written by px() above)
-    __device__ __forceinline__ float term(const LseArgs& a, int t, int, int r) const { return a.term[t][r]; }
-    __device__ __forceinline__ float lq_dreg(const LseArgs& a, int, int r) const { return a.lq_dreg[r]; }
-};
-
-// RED = the team working on one image: a wave (WaveRed: the training step's k) or a whole workgroup (BlockRed<NW>: the k = 5000 evaluator, where a wave
-// per image is ~100 waves on the machine walking 5 000 samples each: 26 % of the bf16 evaluator's time in round 3's profile).  `lane` = index in the team.
-struct WaveRed {
-    static constexpr int NT = 64;
-    __device__ __forceinline__ float sum(float v) const { return wave_sum(v); }
-    __device__ __forceinline__ float max(float v) const { return wave_max(v); }
-};
-template <int NW>
-struct BlockRed {      // (every thread of the workgroup calls sum / max the same number of times: they hold barriers)
-    static constexpr int NT = 64 * NW;
-    float* slots;      // NW floats of LDS
-    __device__ __forceinline__ float sum(float v) const {
-        const float w = wave_sum(v);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = w;
-        __syncthreads();
-        float t = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NW; ++i) t += slots[i];
-        return t;
-    }
-    __device__ __forceinline__ float max(float v) const {
-        const float w = wave_max(v);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = w;
-        __syncthreads();
-        float t = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < NW; ++i) t = fmaxf(t, slots[i]);
-        return t;
-    }
-};
-
-template <class SRC, class RED = WaveRed>
-__device__ __forceinline__ void lse_image(const LseArgs& a, const int b, const int lane, const SRC& src, const RED red = RED()) {
-    constexpr int NT = RED::NT;
-    const int k = a.k;
-    const bool single = NT == 64 && k <= 64;          // one sample per lane: log_w stays in a register between the passes
-    // the image's head (for the KL term at the end): requested first, so that its round trip runs beside the log_w terms' instead of
-    // behind the whole kernel
-    float kmu[2] = {0.0f, 0.0f}, ksg[2] = {1.0f, 1.0f};
-    if (a.head) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = lane + NT * i;
-            if (f < a.D) { kmu[i] = a.head[(size_t)b * a.ldH + f]; ksg[i] = a.head[(size_t)b * a.ldH + a.Dp + f]; }
-        }
-    }
-    float lw_reg = 0.0f;
-    float m = -INFINITY, sum_lw = 0.0f, sum_px = 0.0f, sum_t1 = 0.0f, sum_t2 = 0.0f;
-    for (int s = lane; s < k; s += NT) {
-        const int r = b * k + s;
-        const float px = src.px(a, s, r);
-        float lw = a.coef[0] * px;
-#pragma unroll
-        for (int t = 1; t < 5; ++t)
-            if (a.term[t]) lw += a.coef[t] * src.term(a, t, s, r);
-        a.logw[r] = lw;
-        lw_reg = lw;
-        m = fmaxf(m, lw);
-        sum_lw += lw;
-        sum_px += px;
-        if (a.term[1]) sum_t1 += src.term(a, 1, s, r);
-        if (a.term[2]) sum_t2 += src.term(a, 2, s, r);
-    }
-    m = red.max(m); sum_lw = red.sum(sum_lw); sum_px = red.sum(sum_px); sum_t1 = red.sum(sum_t1); sum_t2 = red.sum(sum_t2);
-    float se = 0.0f;
-    for (int s = lane; s < k; s += NT) se += __expf((single ? lw_reg : a.logw[b * k + s]) - m);
-    se = red.sum(se);
-    const float inv_se = 1.0f / se;
-    const float invB = 1.0f / (float)a.B, invkB = invB / (float)k;
-    float eq14 = 0.0f, dreg = 0.0f;
-    if (!a.lme_only)
-    for (int s = lane; s < k; s += NT) {
-        const int r = b * k + s;
-        const float lw = single ? lw_reg : a.logw[r];
-        const float wn = __expf(lw - m) * inv_se;       // iwae1.py:128-131 == softmax over k (:137)
-        eq14 += wn * lw;
-        a.wn[r] = wn;
-        float G;                                         // dLoss/dlog_w, loss = -objective (iwae1.py:157)
-        float4 cf = make_float4(1.0f, 0.0f, 0.0f, 0.0f); // (ca, cz, cq, cs) for latent_bwd_kernel
-        if (a.objective == OBJ_VAE_ELBO) {
-            G = -invkB; cf.y = -G * a.beta * a.cz_on; cf.w = G * a.beta;
-        } else if (a.objective == OBJ_VAE_ELBO_KL) {
-            G = -invkB;
-        } else if (a.objective == OBJ_DREG) {            // tasks/task02.py:61-76,95-96
-            G = -wn * invB;
-            const float c2 = wn * wn * invB;
-            cf.x = wn; cf.y = c2; cf.z = -c2;
-        } else {                                         // iwae_elbo, iwae_eq14 (same gradient)
-            G = -wn * invB; cf.y = -G * a.beta * a.cz_on; cf.w = G * a.beta;
-        }
-        if (a.lq_dreg) dreg += wn * wn * (src.term(a, 1, s, r) + src.px_total(a, s, r) - src.lq_dreg(a, s, r));   // tasks/task02.py:70-73
-        a.gx[r] = G;
-        if (a.gx_local && r >= a.gx_r0 && r < a.gx_r0 + a.gx_n) a.gx_local[r - a.gx_r0] = G;
-        a.cf[r] = cf;
-    }
-    eq14 = red.sum(eq14); dreg = red.sum(dreg);
-    // KL(q(z|x) || N(0,1)) per image (iwae1.py:116), TFP closed form
-    float kl = 0.0f;
-    if (a.head) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if (lane + NT * i < a.D) {
-                const float ls = __logf(ksg[i]);
-                kl += 0.5f * kmu[i] * kmu[i] + 0.5f * expm1f(2.0f * ls) - ls;
-            }
-        }
-        for (int f = lane + 2 * NT; f < a.D; f += NT) {      // (latent widths beyond 128)
-            const float mu = a.head[(size_t)b * a.ldH + f], sg = a.head[(size_t)b * a.ldH + a.Dp + f];
-            const float ls = __logf(sg);
-            kl += 0.5f * mu * mu + 0.5f * expm1f(2.0f * ls) - ls;
-        }
-        kl = red.sum(kl);
-    }
-    if (lane == 0) {
-        float* pb = a.per_b;
-        const int B = a.B;
-        pb[PB_LME * B + b] = m + __logf(se / (float)k);          // utils.py:6-8
-        pb[PB_MEAN * B + b] = sum_lw / (float)k;
-        pb[PB_EQ14 * B + b] = eq14;
-        pb[PB_KL * B + b] = kl;
-        pb[PB_PX * B + b] = sum_px / (float)k;
-        pb[PB_T1 * B + b] = sum_t1 / (float)k;
-        pb[PB_T2 * B + b] = sum_t2 / (float)k;
-        pb[PB_DREG * B + b] = dreg;
-    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -3146,7 +2870,7 @@ __device__ __forceinline__ void wait_vmem_but(int n) {      // n wave-uniform, 0
 #define WG_NST 4
 // diagnostic ablations of the weight-gradient kernels (WgradPArgs.dbg: timing only, results are wrong) exist in DIAG=1 builds only;
 // in the shipped kernels the conditions fold to false at compile time
-// (WG_DBG: defined at the top of the file)
+// (WG_DBG: defined in step_helpers.h)
 // Shapes <NW waves, IGC i-groups, AI x BJ accumulator tiles per wave>: the waves form an IGC x (NW/IGC) grid, the workgroup's
 // output tile is IGC*AI i-tiles x (NW/IGC)*BJ j-tiles.  A 32-row stage costs a wave AI + BJ fragment reads for AI*BJ MFMAs:
 //   <16, 4, 4, 4>  256 x 256 features, 0.50 reads per MFMA (round 1's shape; the hidden layers at large row counts)
@@ -3706,206 +3430,6 @@ __global__ __launch_bounds__(512, 2) void wgradp_group_sc_kernel(WgradPGroup g) 
     if ((int)blockIdx.x >= g.gx[l] || (int)blockIdx.y >= g.gy[l]) return;
     if (l == 0) wgradp_body<8, 4, 4, 4, true>(g.a[0], blockIdx.x, blockIdx.y, blockIdx.z);
     else wgradp_body<8, 4, 4, 4, false>(g.a[l], blockIdx.x, blockIdx.y, blockIdx.z - g.zbeg[l]);
-}
-
-// ---------------------------------------------------------------------------------
-// elementwise / reduction kernels
-// ---------------------------------------------------------------------------------
-// x fp32 [B][X] -> bf16 P-layout [B][Xp] (pads written as zero).
-// block = 64 rows (lanes) x 4 chunk-waves; a thread converts one 8-feature P chunk of one row.
-// cond != null: C more features per row taken from cond [B][C] (conditional model: concat(x, y), tasks/task05.py:113).
-__global__ __launch_bounds__(256) void prep_rows_kernel(const float* x, const float* cond, int B, int X, int C, int Xp, int Bp, uint16_t* XP) {
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * 64 + lane;
-    const int nchunk = Xp / 8;
-    if (b >= Bp) return;
-    for (int c = blockIdx.y * 4 + (threadIdx.x >> 6); c < nchunk; c += gridDim.y * 4) {
-        const int t = c >> 2, qq = c & 3;
-        float v[8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int f0 = 32 * t + 16 * h + 4 * qq;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int f = f0 + i;
-                float t = 0.0f;
-                if (b < B && f < X) t = x[(size_t)b * X + f];
-                else if (b < B && f < X + C) t = cond[(size_t)b * C + (f - X)];
-                v[4 * h + i] = t;
-            }
-        }
-        if (b < B) *(uint4*)(XP + (size_t)b * Xp + 8 * c) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-    }
-}
-
-// Fused batch gather + dynamic binarisation (main.py:117-120 + src/utils.py:26-27 done per batch on the
-// device): row b of the batch is image idx[start+b] of the uint8 dataset resident in HBM; pixel f is
-// 1 iff (philox(seed, epoch, image, f/4)[f%4] >> 8) < T(gray), T(g) = floor(g * 2^24 / 255 + 0.5), i.e.
-// Bernoulli(gray/255) with an integer threshold (bit-exactly reproducible on the host).  Keyed by
-// (epoch, image): one binarisation per image per epoch, as in the reference.  Same block shape and
-// output as prep_rows_kernel (P-layout) + optional float32 copy.
-// labels != null (conditional models, tasks/task05.py:296-322: the training set is (x, y) pairs): the image's class y rides along -- features
-// X .. X + C - 1 of the row are onehot(y) (the encoder's input concat(x, onehot(y)), task05.py:113), and cond_out [B][C] gets the same
-// one-hot row as float32 (what iwae_set_condition would have been handed for a host-fed batch).
-__global__ __launch_bounds__(256) void gather_binarize_kernel(const uint8_t* data, const int32_t* order, int start, int N, int B, int X, int Xp,
-                                                              int Bp, uint64_t seed, uint32_t epoch, uint16_t* XP, float* xf,
-                                                              const uint8_t* labels, int C, float* cond_out) {
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * 64 + lane;
-    const int nchunk = Xp / 8;
-    if (b >= Bp) return;
-    const int img = (b < B) ? order[start + b] : 0;
-    const int lab = (labels && b < B) ? (int)labels[img] : -1;
-    if (cond_out && blockIdx.y == 0 && threadIdx.x < 64 && b < B)
-        for (int j = 0; j < C; ++j) cond_out[(size_t)b * C + j] = (j == lab) ? 1.0f : 0.0f;
-    for (int c = blockIdx.y * 4 + (threadIdx.x >> 6); c < nchunk; c += gridDim.y * 4) {
-        const int t = c >> 2, qq = c & 3;
-        float v[8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int f0 = 32 * t + 16 * h + 4 * qq;
-            uint32_t r[4];
-            philox4x32_10((uint32_t)img, 0x42494E41u /* 'BINA' */, (uint32_t)(f0 >> 2), epoch, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float bit = 0.0f;
-                if (b < B && f0 + i < X) {
-                    const uint32_t g = data[(size_t)img * X + f0 + i];
-                    const uint32_t thr = (uint32_t)(((uint64_t)g * 16777216ull * 2ull + 255ull) / 510ull);   // floor(g*2^24/255 + 0.5)
-                    bit = ((r[i] >> 8) < thr) ? 1.0f : 0.0f;
-                    if (xf) xf[(size_t)b * X + f0 + i] = bit;
-                } else if (lab >= 0 && f0 + i == X + lab) bit = 1.0f;
-                v[4 * h + i] = bit;
-            }
-        }
-        if (b < B) *(uint4*)(XP + (size_t)b * Xp + 8 * c) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-    }
-}
-
-// The N(0,1) draws of one latent layer for a whole step, fp32 [rows][ld] (4 per thread).  They depend on nothing but
-// the counters, so the host launches this a whole step ahead, on the side stream beside the forward pass: the ~40
-// quarter-rate integer multiplies per Philox call are off every dependency chain.
-// Grid-stride: drawn ahead (a whole step early, beside the forward pass) the launch is a few hundred small blocks that
-// take their time in a corner of every CU; as 5 000 blocks it filled the machine for 11 us and the forward's large
-// workgroups queued behind it.
-// The draws of `nsteps` consecutive steps in one launch (few rows: a step's 2 000 draws are a 4.5 us launch on a chain of 9-17 us kernels; eight steps'
-// worth cost the same): step e.step + s goes to out + s * step_stride, each value exactly what eps_gen_kernel would draw for that step.
-__global__ __launch_bounds__(256) void eps_gen_multi_kernel(EpsSrc e, int M, int nd4, int ld, float* out, int nsteps, size_t step_stride) {
-    const size_t per = (size_t)M * nd4, total = per * nsteps;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int s = (int)(idx / per);
-        const size_t r = idx - (size_t)s * per;
-        const int row = (int)(r / nd4), d4 = (int)(r - (size_t)row * nd4);
-        float n[4];
-        normal4(e.row_offset + (uint64_t)row, (uint32_t)d4, e.stream, e.step + (uint32_t)s, e.seed, n);
-        *(float4*)(out + (size_t)s * step_stride + (size_t)row * ld + 4 * d4) = make_float4(n[0], n[1], n[2], n[3]);
-    }
-}
-__global__ __launch_bounds__(256) void eps_gen_kernel(EpsSrc e, int M, int nd4, int ld, float* out) {
-    const size_t total = (size_t)M * nd4;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int row = (int)(idx / nd4), d4 = (int)(idx - (size_t)row * nd4);
-        float n[4];
-        uint64_t grow = e.row_offset + (uint64_t)row;
-        if (e.k_total) { const int b = row / e.kc; grow = e.row_offset + (uint64_t)b * (uint64_t)e.k_total + (uint64_t)(e.s_off + row - b * e.kc); }
-        normal4(grow, (uint32_t)d4, e.stream, e.step, e.seed, n);
-        *(float4*)(out + (size_t)row * ld + 4 * d4) = make_float4(n[0], n[1], n[2], n[3]);
-    }
-}
-
-// z = mu + sigma*eps, prior/posterior log-densities, z written bf16 P-layout.
-// wave = 16 data rows x 4 quads.  In every 32-feature step t lane (r, q) owns P-layout chunk 4t+q, i.e. features
-// 32t+4q..+3 and 32t+16+4q..+3: float4 loads of eps / mu / sigma, one 16-byte store per step, and the row sums
-// meet across the 4 quads with two shuffles -- no LDS, no barrier, 800 small blocks instead of 800 of 1024 threads.
-__global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    const int row = (blockIdx.x * 4 + wave) * 16 + r;
-    const bool valid = row < a.M;
-    const int rowc = valid ? row : a.M - 1;        // loads come from a clamped row, results are masked
-    const int b = rowc / a.k, s = rowc - b * a.k;
-    const float* hd = a.head + (size_t)(a.head_per_row ? rowc : b) * a.ldH;
-    float lp = 0.0f, lq = 0.0f, lq2 = 0.0f;
-    const int nt = a.Dp / 32;
-    for (int t = 0; t < nt; ++t) {
-        float z8[8];
-        sample_step(a, t, q, rowc, b, s, hd, z8, lp, lq, lq2);
-        if (valid && a.ZP)
-            *(uint4*)(a.ZP + (size_t)row * a.Dp + 8 * (4 * t + q)) = make_uint4(pack2(z8[0], z8[1]), pack2(z8[2], z8[3]), pack2(z8[4], z8[5]), pack2(z8[6], z8[7]));
-        if (valid && a.ZF) {       // float32 mode: z in natural feature order, unrounded
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int f0 = 32 * t + 16 * h + 4 * q;
-                // (one 16-byte store per lane where the row pitch allows it: as four dword stores under four conditions the evaluator's sampling
-                // kernel took 225 us for 416 k rows -- 64 scattered 4-byte pieces per instruction)
-                if ((a.ldZF & 3) == 0 && f0 + 3 < a.ldZF) {
-                    *(float4*)(a.ZF + (size_t)row * a.ldZF + f0) = make_float4(z8[4 * h], z8[4 * h + 1], z8[4 * h + 2], z8[4 * h + 3]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (f0 + i < a.ldZF) a.ZF[(size_t)row * a.ldZF + f0 + i] = z8[4 * h + i];
-                }
-            }
-        }
-    }
-    lp += __shfl_xor(lp, 16); lp += __shfl_xor(lp, 32);
-    lq += __shfl_xor(lq, 16); lq += __shfl_xor(lq, 32);
-    lq2 += __shfl_xor(lq2, 16); lq2 += __shfl_xor(lq2, 32);
-    if (q == 0 && valid) {
-        if (a.lp_prior) a.lp_prior[row] = lp;
-        a.lq[row] = lq;
-        if (a.lq_dreg) a.lq_dreg[row] = lq2;
-    }
-}
-
-// thread per data row: sum_d log N(z1; mup[row], sigp[row]) with z1 recomputed from the encoder head
-// and eps (iwae2.py:122); also the per-row gradients wrt the dec2 head when G != null is done in
-// gauss_bwd_kernel.
-__global__ __launch_bounds__(256) void gauss_lp_kernel(GaussLpArgs a) {
-    // wave = 16 data rows x 4 quads: quad q takes feature groups d4 = q, q+4, ... (float4 loads), two shuffles add them up
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    const int row = (blockIdx.x * 4 + wave) * 16 + r;
-    const bool valid = row < a.M;
-    const int rowc = valid ? row : a.M - 1;
-    const int b = rowc / a.k, s = rowc - b * a.k;
-    const float* hz = a.zhead + (size_t)b * a.ldZH;           // generating head (per image)
-    const float* hp = a.phead + (size_t)rowc * a.ldPH;        // evaluating head (per row)
-    float lp = 0.0f;
-    const int nd4 = (a.D + 3) / 4;
-    for (int d4 = q; d4 < nd4; d4 += 4) {
-        float e[4];
-        eps4(a.eps, b, s, rowc, d4, a.D, e);
-        const float4 zm = *(const float4*)(hz + 4 * d4), zs = *(const float4*)(hz + a.Dzp + 4 * d4);
-        const float4 pm = *(const float4*)(hp + 4 * d4), ps = *(const float4*)(hp + a.Dpp + 4 * d4);
-        const float zmv[4] = {zm.x, zm.y, zm.z, zm.w}, zsv[4] = {zs.x, zs.y, zs.z, zs.w};
-        const float pmv[4] = {pm.x, pm.y, pm.z, pm.w}, psv[4] = {ps.x, ps.y, ps.z, ps.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (4 * d4 + i < a.D) {
-                const float z = zmv[i] + zsv[i] * e[i];
-                const float u = (z - pmv[i]) * __builtin_amdgcn_rcpf(psv[i]);
-                lp += -0.5f * u * u - 0.5f * LOG2PI_F - __logf(psv[i]);
-            }
-        }
-    }
-    lp += __shfl_xor(lp, 16);
-    lp += __shfl_xor(lp, 32);
-    if (q == 0 && valid) a.out[row] = lp;
-}
-
-// one wave per image b
-__global__ void lse_kernel(LseArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (b >= a.B) return;
-    lse_image(a, b, lane, LseGlobalSrc{});
-}
-// one workgroup of NW waves per image (many samples per image: the evaluator's k)
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void lse_block_kernel(LseArgs a) {
-    __shared__ float slots[NW];
-    lse_image(a, (int)blockIdx.x, (int)threadIdx.x, LseGlobalSrc{}, BlockRed<NW>{slots});
 }
 
 // Batch means of the per-image values (the scalar entries of the reference's result dict), one 256-thread block.
@@ -4524,115 +4048,48 @@ __global__ __launch_bounds__(256, 1) void wgrad_rows_kernel(WgradRowsArgs a) {
 }
 
 // ---------------------------------------------------------------------------------
-// exports in the reference's [k, B, ...] order (iwae1.py:141-151), debug dumps
+// launch wrappers (plain C++ callers in model.hip; LAUNCH_EV and grid1: step_helpers.h)
 // ---------------------------------------------------------------------------------
-__global__ void export_rows_kernel(const float* in, int B, int k, float* out) {   // [B*k] row order -> [k][B]
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= B * k) return;
-    const int b = r / k, s = r - b * k;
-    out[(size_t)s * B + b] = in[r];
-}
-__global__ void export_z_kernel(SampleArgs a, float* zout, const float* wn, float* snis) {
-    // thread per (row, d4): z[k][B][D]; snis_z via atomics-free second kernel below
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int nd4 = (a.D + 3) / 4;
-    const int row = idx / nd4, d4 = idx % nd4;
-    if (row >= a.M) return;
-    const int b = row / a.k, s = row - b * a.k;
-    const float* hd = a.head + (size_t)(a.head_per_row ? row : b) * a.ldH;
-    float e[4];
-    eps4(a.eps, b, s, row, d4, a.D, e);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int f = 4 * d4 + i;
-        if (f < a.D) zout[((size_t)s * a.B + b) * a.D + f] = hd[f] + hd[a.Dp + f] * e[i];
-    }
-}
-__global__ void snis_kernel(const float* z, const float* wn, int B, int k, int D, float* out) {   // iwae1.py:139
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= B * D) return;
-    const int b = idx / D, d = idx % D;
-    float s = 0.0f;
-    for (int i = 0; i < k; ++i) s += wn[b * k + i] * z[((size_t)i * B + b) * D + d];
-    out[idx] = s;
-}
-__global__ void unpack_p_kernel(const uint16_t* P, int rows, int F, int Fp, float* out) {   // P-layout bf16 -> [rows][F] fp32
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * F) return;
-    const int r = idx / F, f = idx % F;
-    out[idx] = __uint_as_float((uint32_t)P[(size_t)r * Fp + p_pos(f)] << 16);
-}
-__global__ void eps_dump_kernel(EpsSrc e, int B, int k, int D, float* out) {   // [k][B][D]
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int nd4 = (D + 3) / 4;
-    const int row = idx / nd4, d4 = idx % nd4;
-    if (row >= B * k) return;
-    const int b = row / k, s = row - b * k;
-    float n[4];
-    eps4(e, b, s, row, d4, D, n);
-    for (int i = 0; i < 4; ++i)
-        if (4 * d4 + i < D) out[((size_t)s * B + b) * D + 4 * d4 + i] = n[i];
-}
-
-// ---------------------------------------------------------------------------------
-// launch wrappers (plain C++ callers in model.cpp)
-// ---------------------------------------------------------------------------------
-// Completion event riding on a kernel's own dispatch packet (hipExtLaunchKernelGGL stop event) instead of a separate
-// hipEventRecord behind it.  Measured on MI355X (tools/probe/event_latency.hip): the record puts a 5.5-7 us bubble in
-// front of the recording stream's next kernel and the waiting stream starts 12 us after the kernel ended; with the event
-// on the dispatch packet these are 2.2 and 7.6 us, and a join back 6.2 instead of 10.  set_launch_stop_event(e) arms it
-// for the NEXT launch that goes through LAUNCH_EV on this thread.
-static thread_local hipEvent_t g_stop_event = nullptr;
-void set_launch_stop_event(hipEvent_t e) { g_stop_event = e; }
-#define LAUNCH_EV(kern, grid, block, lds, st, ...)                                                        \
-    do {                                                                                                  \
-        hipEvent_t ev_ = g_stop_event;                                                                    \
-        g_stop_event = nullptr;                                                                           \
-        if (ev_) hipExtLaunchKernelGGL(kern, grid, block, lds, st, nullptr, ev_, 0, __VA_ARGS__);         \
-        else hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);                                 \
-    } while (0)
-static inline dim3 grid1(size_t n, int bs) { return dim3((unsigned)((n + bs - 1) / bs)); }
-
 template <int KTC>
-static void launch_dense_k(int epi, const DenseArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+static void launch_dense_k(int epi, const DenseArgs& a, dim3 grid, size_t lds, hipStream_t st, hipEvent_t done) {
     switch (epi) {
-        case EPI_TANH: LAUNCH_EV((dense_kernel<EPI_TANH, KTC, 2>), grid, dim3(256), lds, st, a); break;
-        case EPI_HEAD: LAUNCH_EV((dense_kernel<EPI_HEAD, KTC, 2>), grid, dim3(256), lds, st, a); break;
-        case EPI_DX: LAUNCH_EV((dense_kernel<EPI_DX, KTC, 2>), grid, dim3(256), lds, st, a); break;
-        case EPI_F32: LAUNCH_EV((dense_kernel<EPI_F32, KTC, 2>), grid, dim3(256), lds, st, a); break;
-        case EPI_BERN: LAUNCH_EV((dense_kernel<EPI_BERN, KTC, 2>), grid, dim3(256), lds, st, a); break;
-        case EPI_SIGMOID: LAUNCH_EV((dense_kernel<EPI_SIGMOID, KTC, 2>), grid, dim3(256), lds, st, a); break;
+        case EPI_TANH: LAUNCH_EV(done, (dense_kernel<EPI_TANH, KTC, 2>), grid, dim3(256), lds, st, a); break;
+        case EPI_HEAD: LAUNCH_EV(done, (dense_kernel<EPI_HEAD, KTC, 2>), grid, dim3(256), lds, st, a); break;
+        case EPI_DX: LAUNCH_EV(done, (dense_kernel<EPI_DX, KTC, 2>), grid, dim3(256), lds, st, a); break;
+        case EPI_F32: LAUNCH_EV(done, (dense_kernel<EPI_F32, KTC, 2>), grid, dim3(256), lds, st, a); break;
+        case EPI_BERN: LAUNCH_EV(done, (dense_kernel<EPI_BERN, KTC, 2>), grid, dim3(256), lds, st, a); break;
+        case EPI_SIGMOID: LAUNCH_EV(done, (dense_kernel<EPI_SIGMOID, KTC, 2>), grid, dim3(256), lds, st, a); break;
     }
 }
 // 8 waves x 16 rows (four waves per SIMD): instantiated for the large-row-count launches of the reference shapes
-static bool launch_dense_g1(int epi, const DenseArgs& a, dim3 grid, size_t lds, hipStream_t st) {
+static bool launch_dense_g1(int epi, const DenseArgs& a, dim3 grid, size_t lds, hipStream_t st, hipEvent_t done) {
     // K > 256 (the 784-pixel input layer): the window loop is bound by issuing its LDS-DMA pieces and row loads (phase stamps:
     // 37 % issue + 45 % wait, 3 % MFMA at B = 1024) -- eight waves share that issue work
     if (a.KT > 8 && epi == EPI_TANH) {
-        LAUNCH_EV((dense_kernel<EPI_TANH, 0, 1>), grid, dim3(512), a.stage_all ? 4 * DENSE_UNIT : lds, st, a);
+        LAUNCH_EV(done, (dense_kernel<EPI_TANH, 0, 1>), grid, dim3(512), a.stage_all ? 4 * DENSE_UNIT : lds, st, a);
         return true;
     }
     if (a.zhead) {      // sampled-input mode (host asks for it only where an instantiation exists: 1-layer training step, latent <= 128)
-        if (a.KT == 4) LAUNCH_EV((dense_kernel<EPI_TANH, 4, 1, 8, true>), grid, dim3(512), lds, st, a);
-        else LAUNCH_EV((dense_kernel<EPI_TANH, 2, 1, 8, true>), grid, dim3(512), lds, st, a);
+        if (a.KT == 4) LAUNCH_EV(done, (dense_kernel<EPI_TANH, 4, 1, 8, true>), grid, dim3(512), lds, st, a);
+        else LAUNCH_EV(done, (dense_kernel<EPI_TANH, 2, 1, 8, true>), grid, dim3(512), lds, st, a);
         return true;
     }
     if (a.M < 8192 || !((a.g1_mask >> epi) & 1u)) return false;
     // the 200 -> 200 tanh layer (d2): 16 waves x 16 rows, one workgroup per CU -- half the LDS-DMA pieces and row loads per
     // wave again, one weight stream per 256 rows (measured: -5 us per step; the other epilogues and the 100 -> 200 layer: no change)
     if (a.KT == 7 && epi == EPI_TANH) {
-        LAUNCH_EV((dense_kernel<EPI_TANH, 7, 1, 16>), dim3((a.M + 255) / 256, grid.y), dim3(1024), lds, st, a);
+        LAUNCH_EV(done, (dense_kernel<EPI_TANH, 7, 1, 16>), dim3((a.M + 255) / 256, grid.y), dim3(1024), lds, st, a);
         return true;
     }
     if (a.KT == 7) {
         switch (epi) {
-            case EPI_DX: LAUNCH_EV((dense_kernel<EPI_DX, 7, 1>), grid, dim3(512), lds, st, a); return true;
-            case EPI_F32: LAUNCH_EV((dense_kernel<EPI_F32, 7, 1>), grid, dim3(512), lds, st, a); return true;
-            case EPI_BERN: LAUNCH_EV((dense_kernel<EPI_BERN, 7, 1>), grid, dim3(512), lds, st, a); return true;
+            case EPI_DX: LAUNCH_EV(done, (dense_kernel<EPI_DX, 7, 1>), grid, dim3(512), lds, st, a); return true;
+            case EPI_F32: LAUNCH_EV(done, (dense_kernel<EPI_F32, 7, 1>), grid, dim3(512), lds, st, a); return true;
+            case EPI_BERN: LAUNCH_EV(done, (dense_kernel<EPI_BERN, 7, 1>), grid, dim3(512), lds, st, a); return true;
             default: return false;
         }
     }
-    if (a.KT == 4 && epi == EPI_TANH) { LAUNCH_EV((dense_kernel<EPI_TANH, 4, 1>), grid, dim3(512), lds, st, a); return true; }
+    if (a.KT == 4 && epi == EPI_TANH) { LAUNCH_EV(done, (dense_kernel<EPI_TANH, 4, 1>), grid, dim3(512), lds, st, a); return true; }
     return false;
 }
 // the launch's guard: the shapes block_fwd_kernel covers, with the buffers its sampling prologue / output layer need in place
@@ -4651,10 +4108,10 @@ bool block_fwd_shape_ok(const BlockFwdArgs& a) {
 bool dec_bwd_rows_ok(const DecBwdRowsArgs& a) {
     return a.KT <= BLOCKFWD_MAX_KT && a.NT1 <= 16 && a.NT1 == 2 * a.KT && a.NT3 <= 16 && (size_t)(a.KTX + 2 * a.KT) * 1024 <= 150 * 1024;
 }
-void launch_dec_bwd_rows(const DecBwdRowsArgs& a, hipStream_t st) {
+void launch_dec_bwd_rows(const DecBwdRowsArgs& a, hipStream_t st, hipEvent_t done) {
     const size_t lds = (size_t)(a.KTX + 2 * a.KT) * 1024 + 64;      // (+ the 16 row weights of lse_on)
-    if (a.M <= 512 && a.KTX > 8) LAUNCH_EV((dec_bwd_rows_kernel<13>), dim3((a.M + 15) / 16), dim3(1024), lds, st, a);
-    else LAUNCH_EV((dec_bwd_rows_kernel<6>), dim3((a.M + 15) / 16), dim3(1024), lds, st, a);
+    if (a.M <= 512 && a.KTX > 8) LAUNCH_EV(done, (dec_bwd_rows_kernel<13>), dim3((a.M + 15) / 16), dim3(1024), lds, st, a);
+    else LAUNCH_EV(done, (dec_bwd_rows_kernel<6>), dim3((a.M + 15) / 16), dim3(1024), lds, st, a);
 }
 bool block_bwd_ok(const BlockBwdArgs& a) {
     return a.R <= 4096 && a.KTH <= BLOCKFWD_MAX_KT && a.KT1 <= BLOCKFWD_MAX_KT && a.NT1 <= 16 && a.NT1 == 2 * a.KT1;
@@ -4685,7 +4142,7 @@ bool bern_lse_ok(const DenseArgs& a) {
     return bern_pipe_ok(a) && a.pre_img1 && a.pipe >= 2 && (198 + a.k) / a.k + 1 <= 8 && a.k >= 13 && 200 % a.k == 0 &&
            (!a.zhead || (a.lse.term[1] == a.zlp && a.lse.term[2] == a.zlq && (!a.lse.lq_dreg || a.lse.lq_dreg == a.zlq_dreg))) && a.lse.n_px_part <= 1;
 }
-void launch_dense(int epi, const DenseArgs& a, hipStream_t st) {
+void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done) {
     dim3 grid((a.M + 127) / 128, (a.MG + a.mg_per_block - 1) / a.mg_per_block);
     const size_t lds = 2 * DENSE_UNIT;
     if (epi == EPI_BERN && a.pipe && bern_pipe_ok(a)) {
@@ -4693,63 +4150,61 @@ void launch_dense(int epi, const DenseArgs& a, hipStream_t st) {
         if (a.pre_img1 && a.pipe >= 2 && (198 + a.k) / a.k + 1 <= 8) {       // 16-wave / 200-row shape (see QW)
             const size_t ldsq = 2 * (7 * 4096 + 1024) + (size_t)8 * a.ldXB * 4 + 128 + 4096 + 2 * 7 * 1024 + 4096 + 1024      // (last 5 KiB: the rows' terms for the in-kernel lse_image, 208 floats each, and its row weights)
                                 + (a.zhead ? (size_t)8 * 3 * a.zDp * 4 + 256 : 0);      // (the sampling prologue's heads of <= 8 images: mu | sigma | sigma/(sigma + 1e-6), + their log-sigma sums)
-            if (a.YP) LAUNCH_EV((bern_pipe_kernel<7, true, true, true>), dim3((a.M + 199) / 200), dim3(1024), ldsq, st, a);
-            else LAUNCH_EV((bern_pipe_kernel<7, false, true, true>), dim3((a.M + 199) / 200), dim3(1024), ldsq, st, a);
+            if (a.YP) LAUNCH_EV(done, (bern_pipe_kernel<7, true, true, true>), dim3((a.M + 199) / 200), dim3(1024), ldsq, st, a);
+            else LAUNCH_EV(done, (bern_pipe_kernel<7, false, true, true>), dim3((a.M + 199) / 200), dim3(1024), ldsq, st, a);
         } else if (a.pre_img1) {       // the whole decoder in one launch
-            if (a.YP) LAUNCH_EV((bern_pipe_kernel<7, true, true>), dim3(grid.x), dim3(512), ldsb, st, a);
-            else LAUNCH_EV((bern_pipe_kernel<7, false, true>), dim3(grid.x), dim3(512), ldsb, st, a);
-        } else if (a.YP) LAUNCH_EV((bern_pipe_kernel<7, true, false>), dim3(grid.x), dim3(512), ldsb, st, a);
-        else LAUNCH_EV((bern_pipe_kernel<7, false, false>), dim3(grid.x), dim3(512), ldsb, st, a);
+            if (a.YP) LAUNCH_EV(done, (bern_pipe_kernel<7, true, true>), dim3(grid.x), dim3(512), ldsb, st, a);
+            else LAUNCH_EV(done, (bern_pipe_kernel<7, false, true>), dim3(grid.x), dim3(512), ldsb, st, a);
+        } else if (a.YP) LAUNCH_EV(done, (bern_pipe_kernel<7, true, false>), dim3(grid.x), dim3(512), ldsb, st, a);
+        else LAUNCH_EV(done, (bern_pipe_kernel<7, false, false>), dim3(grid.x), dim3(512), ldsb, st, a);
         return;
     }
-    if (launch_dense_g1(epi, a, grid, lds, st)) return;
+    if (launch_dense_g1(epi, a, grid, lds, st, done)) return;
     // compile-time k-step counts for the reference model's shapes (200->224, 100->128, 50->64, head 256)
     switch (a.KT) {
-        case 2: launch_dense_k<2>(epi, a, grid, lds, st); break;
-        case 4: launch_dense_k<4>(epi, a, grid, lds, st); break;
-        case 7: launch_dense_k<7>(epi, a, grid, lds, st); break;
-        case 8: launch_dense_k<8>(epi, a, grid, lds, st); break;
-        default: launch_dense_k<0>(epi, a, grid, a.stage_all ? 4 * DENSE_UNIT : lds, st); break;
+        case 2: launch_dense_k<2>(epi, a, grid, lds, st, done); break;
+        case 4: launch_dense_k<4>(epi, a, grid, lds, st, done); break;
+        case 7: launch_dense_k<7>(epi, a, grid, lds, st, done); break;
+        case 8: launch_dense_k<8>(epi, a, grid, lds, st, done); break;
+        default: launch_dense_k<0>(epi, a, grid, a.stage_all ? 4 * DENSE_UNIT : lds, st, done); break;
     }
 }
 bool chain2_fwd_ok(int KT0, int KTH, int KT1, int M) { return KT0 == 4 && KTH == 4 && KT1 == 2 && M >= 8192; }
 void launch_chain2_fwd(const Chain2FwdArgs& a, hipStream_t st) {
-    LAUNCH_EV((chain2_fwd_kernel<4, 4, 2>), dim3((a.M + 127) / 128), dim3(512), 2 * (4 * 4096 + 1024), st, a);
+    hipLaunchKernelGGL((chain2_fwd_kernel<4, 4, 2>), dim3((a.M + 127) / 128), dim3(512), 2 * (4 * 4096 + 1024), st, a);
 }
 bool gblock_bwd_ok(int KT0, int KTH, int KT1, int M) { return KT0 == 4 && KTH == 4 && KT1 == 2 && M >= 8192; }
-void launch_gblock_bwd(int mode, const GBlockBwdArgs& a, hipStream_t st) {
+void launch_gblock_bwd(int mode, const GBlockBwdArgs& a, hipStream_t st, hipEvent_t done) {
     dim3 grid((a.M + 127) / 128);
-    if (mode == 0) LAUNCH_EV((gblock_bwd_kernel<0, 2, 4, 4>), grid, dim3(512), 2 * (8 * 4096 + 1024), st, a);      // decode_z2_to_z1: head over z1 (KTL = 4), input z2
-    else LAUNCH_EV((gblock_bwd_kernel<1, 4, 4, 2>), grid, dim3(512), 2 * (4 * 4096 + 1024), st, a);                // encode_z1_to_z2: head over z2 (KTL = 2), input z1
+    if (mode == 0) LAUNCH_EV(done, (gblock_bwd_kernel<0, 2, 4, 4>), grid, dim3(512), 2 * (8 * 4096 + 1024), st, a);      // decode_z2_to_z1: head over z1 (KTL = 4), input z2
+    else LAUNCH_EV(done, (gblock_bwd_kernel<1, 4, 4, 2>), grid, dim3(512), 2 * (4 * 4096 + 1024), st, a);                // encode_z1_to_z2: head over z2 (KTL = 2), input z1
 }
 bool out_bwd_has_s_mode(int KT) { return KT == 7 || KT == 4 || KT == 2; }
-void launch_dec_bwd(const DecBwdArgs& d, hipStream_t st) {
+void launch_dec_bwd(const DecBwdArgs& d, hipStream_t st, hipEvent_t done) {
     const size_t lds = 2 * ((size_t)d.o.KT * 4096 + 1024);
     dim3 grid((d.o.M + 127) / 128);
-    if (d.nw == 8 && d.o.KT == 7) { LAUNCH_EV((dec_bwd_kernel<7, 8, 1>), grid, dim3(512), lds, st, d); return; }
+    if (d.nw == 8 && d.o.KT == 7) { LAUNCH_EV(done, (dec_bwd_kernel<7, 8, 1>), grid, dim3(512), lds, st, d); return; }
     switch (d.o.KT) {
-        case 7: LAUNCH_EV(dec_bwd_kernel<7>, grid, dim3(256), lds, st, d); break;
-        case 4: LAUNCH_EV(dec_bwd_kernel<4>, grid, dim3(256), lds, st, d); break;
-        case 2: LAUNCH_EV(dec_bwd_kernel<2>, grid, dim3(256), lds, st, d); break;
+        case 7: LAUNCH_EV(done, dec_bwd_kernel<7>, grid, dim3(256), lds, st, d); break;
+        case 4: LAUNCH_EV(done, dec_bwd_kernel<4>, grid, dim3(256), lds, st, d); break;
+        case 2: LAUNCH_EV(done, dec_bwd_kernel<2>, grid, dim3(256), lds, st, d); break;
         default: break;      // the host only asks where out_bwd_has_s_mode(KT)
     }
 }
-void launch_out_bwd(const OutBwdArgs& a, hipStream_t st) {
+void launch_out_bwd(const OutBwdArgs& a, hipStream_t st, hipEvent_t done) {
     if (a.SP) {      // the forward pass kept s = x - sigmoid(l): one product, B operand from HBM
         const size_t lds = 2 * ((size_t)a.KT * 4096 + 1024);
         const int nparts = a.part ? (a.NG + a.gpb - 1) / a.gpb : 1;
         dim3 grid((a.M + 127) / 128, nparts);
-        hipEvent_t stop = g_stop_event;      // belongs to the LAST kernel of this wrapper
-        if (a.part) g_stop_event = nullptr;
+        const hipEvent_t done_s = a.part ? nullptr : done;      // the event belongs to the LAST kernel of this wrapper
         switch (a.KT) {
-            case 7: LAUNCH_EV(out_bwd_s_kernel<7>, grid, dim3(256), lds, st, a); break;
-            case 4: LAUNCH_EV(out_bwd_s_kernel<4>, grid, dim3(256), lds, st, a); break;
-            case 2: LAUNCH_EV(out_bwd_s_kernel<2>, grid, dim3(256), lds, st, a); break;
+            case 7: LAUNCH_EV(done_s, out_bwd_s_kernel<7>, grid, dim3(256), lds, st, a); break;
+            case 4: LAUNCH_EV(done_s, out_bwd_s_kernel<4>, grid, dim3(256), lds, st, a); break;
+            case 2: LAUNCH_EV(done_s, out_bwd_s_kernel<2>, grid, dim3(256), lds, st, a); break;
             default: return;      // the host only asks for this mode when out_bwd_has_s_mode(KT)
         }
         if (a.part) {
-            g_stop_event = stop;
-            LAUNCH_EV(out_bwd_finish_kernel, grid1((size_t)a.M * (a.ldG / 8), 256), dim3(256), 0, st, a, nparts);
+            LAUNCH_EV(done, out_bwd_finish_kernel, grid1((size_t)a.M * (a.ldG / 8), 256), dim3(256), 0, st, a, nparts);
         }
         return;
     }
@@ -4761,24 +4216,24 @@ void launch_out_bwd(const OutBwdArgs& a, hipStream_t st) {
     dim3 gridp((a.M + PAIRS * 32 - 1) / (PAIRS * 32));
 #ifdef IWAE_DIAG
     if (a.stamps) {   // diagnostic build
-        LAUNCH_EV((out_bwd_pair_kernel<7, PAIRS, true>), gridp, dim3(PAIRS * 128), 2 * ((size_t)7 * 4096 + 1024) + (size_t)PAIRS * 4096, st, a);
+        LAUNCH_EV(done, (out_bwd_pair_kernel<7, PAIRS, true>), gridp, dim3(PAIRS * 128), 2 * ((size_t)7 * 4096 + 1024) + (size_t)PAIRS * 4096, st, a);
         return;
     }
 #endif
     switch (a.KT) {
-        case 7: LAUNCH_EV((out_bwd_pair_kernel<7, PAIRS, false>), gridp, dim3(PAIRS * 128), ldsp, st, a); break;
-        case 4: LAUNCH_EV((out_bwd_pair_kernel<4, PAIRS, false>), gridp, dim3(PAIRS * 128), ldsp, st, a); break;
-        case 2: LAUNCH_EV((out_bwd_pair_kernel<2, PAIRS, false>), gridp, dim3(PAIRS * 128), ldsp, st, a); break;
+        case 7: LAUNCH_EV(done, (out_bwd_pair_kernel<7, PAIRS, false>), gridp, dim3(PAIRS * 128), ldsp, st, a); break;
+        case 4: LAUNCH_EV(done, (out_bwd_pair_kernel<4, PAIRS, false>), gridp, dim3(PAIRS * 128), ldsp, st, a); break;
+        case 2: LAUNCH_EV(done, (out_bwd_pair_kernel<2, PAIRS, false>), gridp, dim3(PAIRS * 128), ldsp, st, a); break;
         default: {   // run-time hidden width: generic 4-wave kernel with both weight images
             const size_t lds = 2 * ((size_t)a.KT * 8192 + 1024);
-            LAUNCH_EV((out_bwd_kernel<0, false>), dim3((a.M + 127) / 128), dim3(256), lds, st, a);
+            LAUNCH_EV(done, (out_bwd_kernel<0, false>), dim3((a.M + 127) / 128), dim3(256), lds, st, a);
         }
     }
 }
 void launch_wgradws_group(const WgradPGroup& g, hipStream_t st) {
     int mx = 0;
     for (int l = 0; l < g.n; ++l) mx = std::max(mx, g.gx[l]);
-    LAUNCH_EV(wgradws_group_kernel, dim3(mx, 1, g.zbeg[g.n]), dim3(768), WG_NST * (WG_SR * 512 + WG_SR * 512), st, g);
+    hipLaunchKernelGGL(wgradws_group_kernel, dim3(mx, 1, g.zbeg[g.n]), dim3(768), WG_NST * (WG_SR * 512 + WG_SR * 512), st, g);
 }
 void launch_wgradp_group(const WgradPGroup& g, hipStream_t st) {
     int mx = 0, my = 0;
@@ -4789,53 +4244,26 @@ void launch_wgradp_group(const WgradPGroup& g, hipStream_t st) {
 // shape: 8 = 8 waves / 8 j-tiles per block (small), 16 = 16 waves / 16 j-tiles; specialised waves (IT <= 14): 7 = 8 + 4 waves / 16 j-tiles,
 // 9 = 8 + 8 waves / 8 j-tiles
 int wgradp_strip(int shape) { return (shape == 8 || shape == 9) ? 8 : 16; }
-void launch_wgradp(const WgradPArgs& a, int nsplit, int shape, hipStream_t st) {
+void launch_wgradp(const WgradPArgs& a, int nsplit, int shape, hipStream_t st, hipEvent_t done) {
     dim3 grid((a.JT + wgradp_strip(shape) - 1) / wgradp_strip(shape), (a.IT + 15) / 16, nsplit);
     const size_t sc = a.rowscale ? 1024 : 0;
     if (shape == 7) {        // specialised waves: 8 compute + 4 loader (needs IT <= 14, one i-block)
         const size_t lds = WG_NST * (WG_SR * 512 + WG_SR * 512);
-        if (a.rowscale) LAUNCH_EV((wgradws_kernel<true, 4, 4>), grid, dim3(768), lds, st, a);
-        else LAUNCH_EV((wgradws_kernel<false, 4, 4>), grid, dim3(768), lds, st, a);
+        if (a.rowscale) LAUNCH_EV(done, (wgradws_kernel<true, 4, 4>), grid, dim3(768), lds, st, a);
+        else LAUNCH_EV(done, (wgradws_kernel<false, 4, 4>), grid, dim3(768), lds, st, a);
     } else if (shape == 9) { // specialised waves: 8 compute + 8 loader, 128-feature column blocks
         const size_t lds = WG_NST * (WG_SR * 512 + WG_SR * 256);
-        if (a.rowscale) LAUNCH_EV((wgradws_kernel<true, 2, 8>), grid, dim3(1024), lds, st, a);
-        else LAUNCH_EV((wgradws_kernel<false, 2, 8>), grid, dim3(1024), lds, st, a);
+        if (a.rowscale) LAUNCH_EV(done, (wgradws_kernel<true, 2, 8>), grid, dim3(1024), lds, st, a);
+        else LAUNCH_EV(done, (wgradws_kernel<false, 2, 8>), grid, dim3(1024), lds, st, a);
     } else if (shape == 16) {
         const size_t lds = WG_NST * (WG_SR * 512 + WG_SR * 512 + sc);
-        if (a.rowscale) LAUNCH_EV((wgradp_kernel<16, 2, 8, 2, true>), grid, dim3(1024), lds, st, a);
-        else LAUNCH_EV((wgradp_kernel<16, 4, 4, 4, false>), grid, dim3(1024), lds, st, a);
+        if (a.rowscale) LAUNCH_EV(done, (wgradp_kernel<16, 2, 8, 2, true>), grid, dim3(1024), lds, st, a);
+        else LAUNCH_EV(done, (wgradp_kernel<16, 4, 4, 4, false>), grid, dim3(1024), lds, st, a);
     } else {
         const size_t lds = WG_NST * (WG_SR * 512 + WG_SR * 256 + sc);
-        if (a.rowscale) LAUNCH_EV((wgradp_kernel<8, 4, 4, 4, true>), grid, dim3(512), lds, st, a);
-        else LAUNCH_EV((wgradp_kernel<8, 4, 4, 4, false>), grid, dim3(512), lds, st, a);
+        if (a.rowscale) LAUNCH_EV(done, (wgradp_kernel<8, 4, 4, 4, true>), grid, dim3(512), lds, st, a);
+        else LAUNCH_EV(done, (wgradp_kernel<8, 4, 4, 4, false>), grid, dim3(512), lds, st, a);
     }
-}
-void launch_prep_rows(const float* x, const float* cond, int B, int X, int C, int Xp, int Bp, uint16_t* XP, hipStream_t st) {
-    const int nchunk = Xp / 8;
-    hipLaunchKernelGGL(prep_rows_kernel, dim3(Bp / 64, std::min(32, (nchunk + 3) / 4)), dim3(256), 0, st, x, cond, B, X, cond ? C : 0, Xp, Bp, XP);
-}
-void launch_gather_binarize(const uint8_t* data, const int32_t* order, int start, int N, int B, int X, int Xp, int Bp, uint64_t seed,
-                            uint32_t epoch, uint16_t* XP, float* xf, hipStream_t st, const uint8_t* labels, int C, float* cond_out) {
-    const int nchunk = Xp / 8;
-    hipLaunchKernelGGL(gather_binarize_kernel, dim3(Bp / 64, std::min(32, (nchunk + 3) / 4)), dim3(256), 0, st, data, order, start, N, B, X, Xp,
-                       Bp, seed, epoch, XP, xf, labels, labels ? C : 0, cond_out);
-}
-void launch_eps_gen_multi(const EpsSrc& e, int M, int D, int ld, float* out, int nsteps, size_t step_stride, hipStream_t st) {
-    const int nd4 = (D + 3) / 4;
-    hipLaunchKernelGGL(eps_gen_multi_kernel, grid1((size_t)nsteps * M * nd4, 256), dim3(256), 0, st, e, M, nd4, ld, out, nsteps, step_stride);
-}
-void launch_eps_gen(const EpsSrc& e, int M, int D, int ld, float* out, hipStream_t st, int max_blocks) {
-    const int nd4 = (D + 3) / 4;
-    dim3 grid = grid1((size_t)M * nd4, 256);
-    if (max_blocks > 0 && (int)grid.x > max_blocks) grid.x = max_blocks;
-    hipLaunchKernelGGL(eps_gen_kernel, grid, dim3(256), 0, st, e, M, nd4, ld, out);
-}
-void launch_sample(const SampleArgs& a, hipStream_t st) { hipLaunchKernelGGL(sample_kernel, dim3((a.M + 63) / 64), dim3(256), 0, st, a); }
-void launch_gauss_lp(const GaussLpArgs& a, hipStream_t st) { hipLaunchKernelGGL(gauss_lp_kernel, dim3((a.M + 63) / 64), dim3(256), 0, st, a); }
-void launch_lse(const LseArgs& a, hipStream_t st) {
-    if (a.k >= 2048) LAUNCH_EV(lse_block_kernel<16>, dim3(a.B), dim3(1024), 0, st, a);
-    else if (a.k > 256) LAUNCH_EV(lse_block_kernel<4>, dim3(a.B), dim3(256), 0, st, a);
-    else LAUNCH_EV(lse_kernel, grid1((size_t)a.B * 64, 256), dim3(256), 0, st, a);
 }
 void launch_latent_bwd(const LatentBwdArgs& a, hipStream_t st) {
     if (a.dzh && !a.dz2 && a.eps.cache && !a.prior_head) hipLaunchKernelGGL(latent_bwd_kernel<1>, dim3(a.Bp), dim3(256), 0, st, a);
@@ -4847,19 +4275,19 @@ void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st) {
 }
 void launch_reduce_grads(const LayerDesc* layers, int nlayers, int first_block, int nblocks, float* grad, float* param, float* mom, float* vel,
                          float alpha, float beta1, float beta2, float eps, int fuse_adam, const float* per_b, int B, float beta, float* scalars, hipStream_t st,
-                         int first_block2, int nblocks2) {
+                         int first_block2, int nblocks2, hipEvent_t done) {
     const AdamCoef c = {alpha, 1.0f, beta1, beta2, eps, fuse_adam};
     const MeansArgs mn = {per_b, B, beta, scalars};
-    LAUNCH_EV(reduce_grads_kernel, dim3(nblocks + nblocks2 + (per_b ? 1 : 0)), dim3(256), 0, st, layers, nlayers, grad, param, mom, vel, c, mn, first_block, nblocks,
+    LAUNCH_EV(done, reduce_grads_kernel, dim3(nblocks + nblocks2 + (per_b ? 1 : 0)), dim3(256), 0, st, layers, nlayers, grad, param, mom, vel, c, mn, first_block, nblocks,
               first_block2);
 }
 void launch_scalars(const float* per_b, int B, float beta, float* out, hipStream_t st) {
     hipLaunchKernelGGL(scalars_kernel, dim3(1), dim3(256), 0, st, per_b, B, beta, out);
 }
 void launch_adam(const LayerDesc* layers, int nlayers, int nblocks, float* param, const float* grad, float* mom, float* vel,
-                 float alpha, float gscale, float beta1, float beta2, float eps, int do_update, hipStream_t st, int first_block) {
+                 float alpha, float gscale, float beta1, float beta2, float eps, int do_update, hipStream_t st, int first_block, hipEvent_t done) {
     const AdamCoef c = {alpha, gscale, beta1, beta2, eps, do_update};
-    LAUNCH_EV(adam_kernel, dim3(nblocks), dim3(256), 0, st, layers, nlayers, param, grad, mom, vel, c, first_block);
+    LAUNCH_EV(done, adam_kernel, dim3(nblocks), dim3(256), 0, st, layers, nlayers, param, grad, mom, vel, c, first_block);
 }
 void launch_wgrad_rows(const WgradRowsJob* jobs, int njobs, const LayerDesc* layers, float* grad, float* param, float* mom, float* vel, float alpha,
                        float beta1, float beta2, float eps, int fuse_adam, const float* per_b, int B, float beta, float* scalars, const char* zero, hipStream_t st) {
@@ -4878,22 +4306,7 @@ void launch_wgrad_rows(const WgradRowsJob* jobs, int njobs, const LayerDesc* lay
     a.c = AdamCoef{alpha, 1.0f, beta1, beta2, eps, fuse_adam};
     a.mn = MeansArgs{per_b, B, beta, scalars};
     a.zero = zero;
-    LAUNCH_EV(wgrad_rows_kernel, dim3(wgs + (per_b ? 1 : 0)), dim3(256), (size_t)4 * WGR_NST * WGR_STAGE, st, a);
-}
-void launch_export_rows(const float* in, int B, int k, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(export_rows_kernel, grid1((size_t)B * k, 256), dim3(256), 0, st, in, B, k, out);
-}
-void launch_export_z(const SampleArgs& a, float* zout, hipStream_t st) {
-    hipLaunchKernelGGL(export_z_kernel, grid1((size_t)a.M * ((a.D + 3) / 4), 256), dim3(256), 0, st, a, zout, (const float*)nullptr, (float*)nullptr);
-}
-void launch_snis(const float* z, const float* wn, int B, int k, int D, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(snis_kernel, grid1((size_t)B * D, 256), dim3(256), 0, st, z, wn, B, k, D, out);
-}
-void launch_unpack_p(const uint16_t* P, int rows, int F, int Fp, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(unpack_p_kernel, grid1((size_t)rows * F, 256), dim3(256), 0, st, P, rows, F, Fp, out);
-}
-void launch_eps_dump(const EpsSrc& e, int B, int k, int D, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(eps_dump_kernel, grid1((size_t)B * k * ((D + 3) / 4), 256), dim3(256), 0, st, e, B, k, D, out);
+    hipLaunchKernelGGL(wgrad_rows_kernel, dim3(wgs + (per_b ? 1 : 0)), dim3(256), (size_t)4 * WGR_NST * WGR_STAGE, st, a);
 }
 
 }  // namespace iwae

@@ -238,15 +238,13 @@ namespace {      // (internal linkage again)
 // refresh in the epilogue; done: its completion event, riding on the dispatch packet; with_means: one extra block makes the step's batch means
 void reduce_blocks(iwae_model* m, hipStream_t st, BlockRange a, BlockRange b, float alpha, bool update, hipEvent_t done, bool with_means) {
     const float* per_b = with_means ? ptr<float>(m->per_b) : nullptr;
-    if (done) set_launch_stop_event(done);
     launch_reduce_grads(m->d_descs, (int)m->descs.size(), a.first, a.count, m->grad, m->param, m->mom, m->vel, alpha, m->adam_b1, m->adam_b2, m->adam_eps, update ? 1 : 0,
-                        per_b, per_b ? m->B : 0, !per_b ? 0.f : m->cfg.n_layers == 2 ? 1.f : m->beta, per_b ? m->d_scalars : nullptr, st, b.first, b.count);
+                        per_b, per_b ? m->B : 0, !per_b ? 0.f : m->cfg.n_layers == 2 ? 1.f : m->beta, per_b ? m->d_scalars : nullptr, st, b.first, b.count, done);
 }
 }  // namespace -- adam_blocks: external (hidden) linkage, declared in model.h, step_f32.hip calls it too
 // adam_blocks: Adam on elementwise blocks [first, first + count) of the flat gradient times grad_scale; done as above (update = false: the weight images only)
 void adam_blocks(iwae_model* m, hipStream_t st, int first, int count, float alpha, float grad_scale, hipEvent_t done, bool update) {
-    if (done) set_launch_stop_event(done);
-    launch_adam(m->d_descs, (int)m->descs.size(), count, m->param, m->grad, m->mom, m->vel, alpha, grad_scale, m->adam_b1, m->adam_b2, m->adam_eps, update ? 1 : 0, st, first);
+    launch_adam(m->d_descs, (int)m->descs.size(), count, m->param, m->grad, m->mom, m->vel, alpha, grad_scale, m->adam_b1, m->adam_b2, m->adam_eps, update ? 1 : 0, st, first, done);
 }
 namespace {      // (internal linkage again)
 
@@ -337,7 +335,7 @@ int wgradp_plan(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP
 }
 
 int wgradp(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP, int rows, hipStream_t st = nullptr,
-           const float* rowscale = nullptr) {
+           const float* rowscale = nullptr, hipEvent_t done = nullptr) {
     WgradPArgs a;
     int nsplit = 1, nw = 8;
     CHK(wgradp_plan(m, L, XP, GP, rows, a, nsplit, nw));
@@ -350,7 +348,7 @@ int wgradp(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t* GP, int
         a.stamps = ptr<unsigned long long>(m->dstamps);
     }
 #endif
-    launch_wgradp(a, nsplit, nw, st ? st : m->stream);
+    launch_wgradp(a, nsplit, nw, st ? st : m->stream, done);
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
@@ -383,7 +381,7 @@ int wgradp_two_plan(iwae_model* m, Linear& L, const uint16_t* XP, const uint16_t
     return IWAE_OK;
 }
 
-int dense_dx(iwae_model* m, Linear& L, const uint16_t* GP, int rows, const uint16_t* ACT, uint16_t* YP, float* YF) {
+int dense_dx(iwae_model* m, Linear& L, const uint16_t* GP, int rows, const uint16_t* ACT, uint16_t* YP, float* YF, hipEvent_t done = nullptr) {
     DenseArgs a;
     memset(&a, 0, sizeof(a));
     a.X = GP; a.ldX = L.Np32; a.img = L.imgB;
@@ -392,7 +390,7 @@ int dense_dx(iwae_model* m, Linear& L, const uint16_t* GP, int rows, const uint1
     a.YP = YP; a.ldYP = L.Kp32; a.YF = YF; a.ldYF = L.Kp32;
     a.ACT = ACT; a.ldACT = L.Kp32;
     CHK(attach_dense_stamps(m, ACT ? EPI_DX : EPI_F32, a));
-    launch_dense(ACT ? EPI_DX : EPI_F32, a, m->stream);
+    launch_dense(ACT ? EPI_DX : EPI_F32, a, m->stream, done);
     HIPCHK(hipGetLastError());
     return IWAE_OK;
 }
@@ -1061,7 +1059,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         // The side stream of an early output-layer weight gradient forks behind THIS kernel (event on its dispatch packet) where the row
         // weights come from it or from the side stream's own copy of lse_kernel
         const bool fork_here = p.lse_dup || (p.lse_fused && p.early_wout);
-        if (p.dec_fwd != DEC_BLOCK_OUT) { ScopedTimer tm(m, T_DEC_FWD); if (fork_here && !m->time_this) set_launch_stop_event(m->ev_lse); launch_dense(EPI_BERN, a, st); }
+        if (p.dec_fwd != DEC_BLOCK_OUT) { ScopedTimer tm(m, T_DEC_FWD); launch_dense(EPI_BERN, a, st, (fork_here && !m->time_this) ? m->ev_lse : nullptr); }
         if (fork_here && m->time_this) HIPCHK(hipEventRecord(m->ev_lse, st));      // (a timed step: the timer's stop event sits behind the kernel)
         HIPCHK(hipGetLastError());
         // The NEXT step's noise (speculating step + 1 with the same batch shape; the tag is checked on use): drawn now, on the stream the plan
@@ -1083,8 +1081,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         // s-mode training step: the output layer's weight gradient needs s, g2 and the row weights lse_kernel leaves -- not
         // out_bwd -- so the side stream forks here (ev_lse on this kernel's dispatch packet), one kernel earlier, and the
         // gradient runs beside out_bwd (both read s)
-        if (p.early_wout && !p.lse_dup) set_launch_stop_event(m->ev_lse);
-        if (p.lse_at == LSE_FWD) launch_lse(a, st);      // (LSE_BWD_ROWS: the backward pass's first kernel does it)
+        if (p.lse_at == LSE_FWD) launch_lse(a, st, (p.early_wout && !p.lse_dup) ? m->ev_lse : nullptr);      // (LSE_BWD_ROWS: the backward pass's first kernel does it)
         if (p.lse_dup) {       // the side stream's copy: same inputs, its own outputs
             CHK(ensure(m->logw2, (size_t)Mp * 4, st));
             CHK(ensure(m->wn2, (size_t)Mp * 4, st));
@@ -1168,8 +1165,7 @@ int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
             r.DZ = ptr<float>(w.dz); r.DZH = p.dz_half ? (uint16_t*)w.dz.p : nullptr;
             if (p.lse_at == LSE_BWD_ROWS) lse_args_parts(m, objective, true, nullptr, r.lse);      // (the forward pass left the log-mean-exp to this kernel)
             ScopedTimer tm(m, T_DEC_BWD);
-            if (!p.dec_rows) set_launch_stop_event(m->ev_fork2);
-            launch_dec_bwd_rows(r, st);
+            launch_dec_bwd_rows(r, st, p.dec_rows ? nullptr : m->ev_fork2);
         } else if (p.dx == DX_DEC_BWD) {      // out_bwd + dX of d2 + dX of d1 in one launch
             DecBwdArgs d;
             memset(&d, 0, sizeof(d));
@@ -1184,11 +1180,10 @@ int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
                 d.o.stamps = ptr<unsigned long long>(m->dstamps);
             }
             ScopedTimer tm(m, T_DEC_BWD);
-            if (!p.dec_rows) set_launch_stop_event(m->ev_fork2);          // dpre2, dpre1 and the last read of the decoder's weight images: one event
-            launch_dec_bwd(d, st);
+            launch_dec_bwd(d, st, p.dec_rows ? nullptr : m->ev_fork2);          // dpre2, dpre1 and the last read of the decoder's weight images: one event
         } else {
             // (forked behind lse_kernel already: the side stream then needs nothing from the main stream until dX of d1 is done)
-            { ScopedTimer tm(m, T_OUT_BWD); if (!p.early_wout) set_launch_stop_event(m->ev_fork); launch_out_bwd(a, st); }
+            { ScopedTimer tm(m, T_OUT_BWD); launch_out_bwd(a, st, p.early_wout ? nullptr : m->ev_fork); }
         }
         HIPCHK(hipGetLastError());
     }
@@ -1231,21 +1226,20 @@ int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
             CHK(wgradp_two_plan(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, gx_out, a1, n1, a2, n2));
             launch_wgradp(a1, n1, 7, sd);
             HIPCHK(hipStreamWaitEvent(sd, m->ev_fork2, 0));      // (the late part starts behind dec_bwd_kernel, beside the hidden layers' gradients)
-            set_launch_stop_event(m->ev_s2);
-            launch_wgradp(a2, n2, 7, sd);
+            launch_wgradp(a2, n2, 7, sd, m->ev_s2);
             HIPCHK(hipGetLastError());
         } else if (m->abl_skip & 1) {      // (DIAG builds, timing only: slabs allocated, the reduction still reads them)
             if (wout_beside) HIPCHK(hipEventRecord(m->ev_s2, sd));
             WgradPArgs a0; int n0 = 1, w0 = 8; CHK(wgradp_plan(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, a0, n0, w0));
         } else {
-            if (wout_beside) set_launch_stop_event(m->ev_s2);
-            if (p.g2w) CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2wP), ptr<uint16_t>(w.dlP), M, sd, nullptr));      // (pre-weighted X operand: the unweighted kernel)
-            else CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, sd, p.s_mode ? gx_out : nullptr));
+            const hipEvent_t done = wout_beside ? m->ev_s2 : nullptr;
+            if (p.g2w) CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2wP), ptr<uint16_t>(w.dlP), M, sd, nullptr, done));      // (pre-weighted X operand: the unweighted kernel)
+            else CHK(wgradp(m, m->dec1[2], ptr<uint16_t>(w.g2P), ptr<uint16_t>(w.dlP), M, sd, p.s_mode ? gx_out : nullptr, done));
         }
     }
     if (!fused_dx) {
         { ScopedTimer tm(m, T_DX_HID); CHK(dense_dx(m, m->dec1[1], ptr<uint16_t>(w.d2P), M, ptr<uint16_t>(w.g1P), ptr<uint16_t>(w.d1P), nullptr)); }
-        { ScopedTimer tm(m, T_DX_LAT); set_launch_stop_event(m->ev_fork2); CHK(dense_dx(m, m->dec1[0], ptr<uint16_t>(w.d1P), M, nullptr, nullptr, ptr<float>(w.dz))); }
+        { ScopedTimer tm(m, T_DX_LAT); CHK(dense_dx(m, m->dec1[0], ptr<uint16_t>(w.d1P), M, nullptr, nullptr, ptr<float>(w.dz), m->ev_fork2)); }
     }
     // ONE event (ev_fork2) behind the whole dX chain -- the last of its kernels carries it on its dispatch packet (every separate
     // record costs the main stream a ~6 us bubble): the hidden layers' weight gradients need dpre2 and dpre1, and the deferred
@@ -1300,8 +1294,7 @@ int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
             gb.head1 = ptr<float>(m->wenc1.head); gb.ldH1 = 2 * m->Dp[0];
             gb.DHP = ptr<uint16_t>(m->wdec2.dheadP); gb.D2P = ptr<uint16_t>(m->wdec2.d2P); gb.D1P = ptr<uint16_t>(m->wdec2.d1P);
             gb.DZ2 = ptr<float>(m->wdec2.dx); gb.DZD = (uint16_t*)m->wenc2.dx.p;
-            set_launch_stop_event(m->ev_blk);
-            launch_gblock_bwd(0, gb, st);
+            launch_gblock_bwd(0, gb, st, m->ev_blk);
             CHK(block_bwd(m, m->dec2, m->wdec2, ptr<uint16_t>(m->zP[1]), M, false, true, true));
             memset(&gb, 0, sizeof(gb));
             gb.imgH = m->enc2[2].imgF; gb.imgBh = m->enc2[2].imgB; gb.imgB2 = m->enc2[1].imgB; gb.imgB1 = m->enc2[0].imgB;
@@ -1310,8 +1303,7 @@ int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f) {
             gb.DZIN = ptr<float>(m->wdec2.dx);
             gb.DHP = ptr<uint16_t>(m->wenc2.dheadP); gb.D2P = ptr<uint16_t>(m->wenc2.d2P); gb.D1P = ptr<uint16_t>(m->wenc2.d1P);
             gb.DZD = (uint16_t*)m->wenc2.dx.p; gb.DZDEC = ptr<float>(w.dz); gb.ldDZDEC = m->dec1[0].Kp32; gb.DZOUT = (uint16_t*)m->dzdir.p;
-            set_launch_stop_event(m->ev_blk);
-            launch_gblock_bwd(1, gb, st);
+            launch_gblock_bwd(1, gb, st, m->ev_blk);
             // (the encode block's weight gradients on the second side stream, free by now: beside the decode block's, not behind them)
             CHK(block_bwd(m, m->enc2, m->wenc2, ptr<uint16_t>(m->zP[0]), M, false, true, true, p.hid_on == ON_SIDE2 ? m->side2 : nullptr));
             HIPCHK(hipGetLastError());

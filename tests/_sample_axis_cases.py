@@ -53,7 +53,7 @@ BF16_1L = [
     case(3, 70, "dreg"),                     # the negative control's shape (test_sample_axis_host.py)
     case(5, 129, "vae_elbo_kl", 0.7),        # lse_image: three passes over a.logw, beta != 1
     case(3, 257, "iwae_elbo"),               # M = 771 <= 1 024: a WAVE walks 257 samples (launch_lse's block kernels are not used inside dec_bwd_rows_kernel)
-    # -- 1 025 .. 4 096 rows: the separate launch_lse (kernels.hip: lse_block_kernel<4> for k > 256, <16> for k >= 2 048) in a training
+    # -- 1 025 .. 4 096 rows: the separate launch_lse (row_kernels.hip: lse_block_kernel<4> for k > 256, <16> for k >= 2 048) in a training
     #    step -- the BlockRed reductions through the softmax, gx, cf, eq14 and DReG passes
     case(5, 256, "iwae_eq14"),               # launch_lse `k > 256` false: the last k of lse_kernel, a wave in four full passes
     case(5, 257, "iwae_elbo"),               # launch_lse `k > 256`: lse_block_kernel<4>

@@ -122,3 +122,23 @@ def test_product_path_does_not_import_oracle():
             src = open(os.path.join(pkg, fn)).read()
             assert "oracle" not in src.replace("# oracle", ""), "%s references the oracle" % fn
     assert "oracle" not in open(os.path.join(ROOT, "main.py")).read()
+
+
+def test_every_source_file_is_compiled_and_hashed():
+    """Every *.hip / *.h under iwae_amd/csrc is in the build id's file list, every *.hip has its compile line in build.sh and its object on the
+    link line, and build.sh hashes the list _capi hashes: a source file that is compiled but not hashed (or listed but not built) fails here."""
+    from iwae_amd import _capi
+    csrc = os.path.join(ROOT, "iwae_amd", "csrc")
+    b = open(os.path.join(csrc, "build.sh")).read()
+    link = [l for l in b.splitlines() if "-shared" in l]
+    assert len(link) == 1
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert sources
+    for f in sources:
+        assert f in _capi._ID_SOURCES, "%s is not part of the build id" % f
+        if f.endswith(".hip"):
+            stem = f[:-len(".hip")]
+            assert re.search(r"-c %s -o %s\.o\b" % (re.escape(f), re.escape(stem)), b), "build.sh has no compile line for %s" % f
+            assert re.search(r"\s%s\.o\b" % re.escape(stem), link[0]), "%s.o is not on build.sh's link line" % stem
+    listed = re.search(r"BUILD_ID=\$\(for f in (.*?); do", b).group(1).split()
+    assert [os.path.basename(f) for f in listed] == [os.path.basename(f) for f in _capi._ID_SOURCES]
