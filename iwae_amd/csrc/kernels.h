@@ -1,4 +1,4 @@
-// Argument blocks and launch wrappers for kernels.hip (internal; the public ABI is include/iwae_amd.h).
+// Argument blocks and launch wrappers of the kernel files, one section per file (internal; the public ABI is include/iwae_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +13,11 @@ enum { PB_LME = 0, PB_MEAN, PB_EQ14, PB_KL, PB_PX, PB_T1, PB_T2, PB_DREG, PB_COU
 // scalar outputs (device float[16]); must match iwae_scalars in include/iwae_amd.h
 enum { SC_VAE_ELBO = 0, SC_VAE_ELBO_KL, SC_IWAE_ELBO, SC_IWAE_EQ14, SC_INFERENCE_LOSS, SC_MEAN_LPXZ, SC_MEAN_T1, SC_MEAN_T2, SC_KL, SC_COUNT = 16 };
 
+// done (in the launchers below): a completion event that rides on the launch's dispatch packet (cheaper on both streams than hipEventRecord behind
+// the kernel: LAUNCH_EV in step_helpers.h); launch_out_bwd gives it to its LAST kernel.  A launcher without the argument cannot carry one.
+
+// ---- bf16 step, what walks rows or elements once (row_kernels.hip; iwae_forward, iwae_train_step, iwae_eval_llh): input conversion, noise,
+// sampling, log-densities, log-mean-exp, exports.  EpsSrc, LseArgs and SampleArgs are members of the later sections' argument blocks too.
 struct EpsSrc {
     const float* user = nullptr;     // [k][B][D] host-supplied draws (reference order) or null -> Philox
     const float* cache = nullptr;    // [rows][ldC] draws eps_gen_kernel made ahead of the step (Philox costs ~40 quarter-rate
@@ -40,6 +45,41 @@ struct LseArgs {
     float* gx_local; int gx_r0, gx_n;    // optional: the row weights of rows [gx_r0, gx_r0 + gx_n) also go to gx_local[row - gx_r0] (kernels that do lse_image's work for their own rows: dec_bwd_rows_kernel, bern_pipe_kernel)
 };
 
+struct SampleArgs {
+    const float* head; int ldH; int Dp; int D; int head_per_row;
+    int M, Mp, k, B;
+    EpsSrc eps;
+    uint16_t* ZP;                     // z as bf16 P-layout [M][Dp], or null
+    float* ZF; int ldZF;              // z as float32 rows [M][ldZF] (float32 mode), or null
+    const float* prior_head;          // conditional prior: per-image head [B][ldH] (mu_p | sigma_p) scoring z, or null = N(0,1)
+    const float* cond; int C;         // conditional model: y [B][C] goes into features D..D+C-1 of the z rows (decoder input concat(z, y))
+    float* lp_prior; float* lq; float* lq_dreg;
+};
+
+struct GaussLpArgs {
+    const float* zhead; int ldZH; int Dzp;   // head that generated z (per image)
+    const float* phead; int ldPH; int Dpp;   // head that scores z (per row)
+    int D, M, k;
+    EpsSrc eps;
+    float* out;
+};
+void launch_prep_rows(const float* x, const float* cond, int B, int X, int C, int Xp, int Bp, uint16_t* XP, hipStream_t st);
+void launch_gather_binarize(const uint8_t* data, const int32_t* order, int start, int N, int B, int X, int Xp, int Bp, uint64_t seed,
+                            uint32_t epoch, uint16_t* XP, float* xf, hipStream_t st,
+                            const uint8_t* labels = nullptr, int C = 0, float* cond_out = nullptr);      // labels: class ids of the resident set (conditional models)
+void launch_eps_gen(const EpsSrc& e, int M, int D, int ld, float* out, hipStream_t st, int max_blocks = 0);   // max_blocks > 0: grid-stride over at most that many blocks
+void launch_eps_gen_multi(const EpsSrc& e, int M, int D, int ld, float* out, int nsteps, size_t step_stride, hipStream_t st);   // steps e.step .. e.step + nsteps - 1, step s at out + s * step_stride
+void launch_sample(const SampleArgs& a, hipStream_t st);
+void launch_gauss_lp(const GaussLpArgs& a, hipStream_t st);
+void launch_lse(const LseArgs& a, hipStream_t st, hipEvent_t done = nullptr);
+void launch_export_rows(const float* in, int B, int k, float* out, hipStream_t st);
+void launch_export_z(const SampleArgs& a, float* zout, hipStream_t st);
+void launch_snis(const float* z, const float* wn, int B, int k, int D, float* out, hipStream_t st);
+void launch_unpack_p(const uint16_t* P, int rows, int F, int Fp, float* out, hipStream_t st);
+void launch_eps_dump(const EpsSrc& e, int B, int k, int D, float* out, hipStream_t st);
+
+// ---- bf16 step, forward (kernels.hip, its forward part; iwae_forward, iwae_train_step, iwae_eval_llh): activations and the Bernoulli term; launch_dense also
+// launches the dx pass's EPI_DX / EPI_F32 products
 struct DenseArgs {
     const uint16_t* X; int ldX;       // P-layout rows [M][ldX], ldX = 32*KT
     const char* img;                  // MG-major A-image of the weight
@@ -79,17 +119,9 @@ struct DenseArgs {
     uint16_t* G2W; int g2w_feat;
     int dbg;                          // DIAG builds only (option fake_s): 32 = the Bernoulli epilogue does not store s
 };
-
-struct SampleArgs {
-    const float* head; int ldH; int Dp; int D; int head_per_row;
-    int M, Mp, k, B;
-    EpsSrc eps;
-    uint16_t* ZP;                     // z as bf16 P-layout [M][Dp], or null
-    float* ZF; int ldZF;              // z as float32 rows [M][ldZF] (float32 mode), or null
-    const float* prior_head;          // conditional prior: per-image head [B][ldH] (mu_p | sigma_p) scoring z, or null = N(0,1)
-    const float* cond; int C;         // conditional model: y [B][C] goes into features D..D+C-1 of the z rows (decoder input concat(z, y))
-    float* lp_prior; float* lq; float* lq_dreg;
-};
+void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done = nullptr);
+bool bern_pipe_ok(const DenseArgs& a);  // shapes bern_pipe_kernel covers (launch_dense falls back to dense_kernel<EPI_BERN> otherwise)
+bool bern_lse_ok(const DenseArgs& a);   // ... and can take lse_kernel's work for its rows (DenseArgs.lse_on)
 
 struct BlockFwdArgs {                 // block_fwd_kernel: one BasicBlock on R <= 4096 rows
     const uint16_t* X; int ldX;       // input rows, P-layout [R][32*KT0]
@@ -107,6 +139,29 @@ struct BlockFwdArgs {                 // block_fwd_kernel: one BasicBlock on R <
     const uint16_t* oXB; int oldXB; int ok;   // x as bf16 P-layout [B][oldXB]; samples per image (row r belongs to image r / ok)
     uint16_t* oSP; int oldS; float* olpxz;
 };
+bool block_fwd_ok(const BlockFwdArgs& a);
+bool block_fwd_shape_ok(const BlockFwdArgs& a);      // block_fwd_ok's shape part: reads no buffer pointer
+void launch_block_fwd(const BlockFwdArgs& a, hipStream_t st);
+
+struct Chain2FwdArgs {                // chain2_fwd_kernel: the 2-layer model's per-sample blocks (q(z2|z1) and p(z1|z2)) on M rows, one launch
+    uint16_t* Z1P;                    // z1 rows, bf16 P-layout [M][32*KT0]: MADE here (z1 = mu1 + sigma1*eps1, iwae2.py:61) and kept for the decoder and the weight gradient
+    float* lqz1x;                     // log q(z1|x) per row (iwae2.py:123)
+    const char *e_img1, *e_img2, *e_imgh;     // MG-major forward images of encode_z1_to_z2: l1 (KT0 k-steps), l2, head (KTH k-steps each)
+    const char *d_img1, *d_img2, *d_imgh;     // ... of decode_z2_to_z1: l1 (KT1 k-steps), l2, head (KTH k-steps each)
+    int M, k, B, D0, D1;              // data rows, samples per image, images; latent widths of z1 and z2
+    uint16_t *EH1, *EH2;              // encode block's tanh activations, P-layout [M][32*KTH], kept for the backward pass (null: forward only)
+    float* EHEAD;                     // its head, fp32 [M][64*KT1] (mu2 | sigma2), or null
+    uint16_t* Z2P;                    // z2 rows, P-layout [M][32*KT1], or null
+    uint16_t *DH1, *DH2;              // decode block's tanh activations, or null
+    float* DHEAD;                     // its head, fp32 [M][64*KT0] (mu_p | sigma_p), or null
+    const float* head1; int ldH1;     // head of q(z1|x) per image [B][ldH1] (mu1 | sigma1 at 32*KT0): z1 in float32 for log p(z1|z2)
+    EpsSrc eps1, eps2;                // the draws of z1 and z2
+    float *lpz1z2, *lpz2, *lqz2z1;    // per-row log-densities (iwae2.py:122-124)
+};
+bool chain2_fwd_ok(int KT0, int KTH, int KT1, int M);
+void launch_chain2_fwd(const Chain2FwdArgs& a, hipStream_t st);
+
+// ---- bf16 step, dx (kernels.hip, its dX part; iwae_train_step, iwae_forward_backward): gradients back through the activations
 struct DecBwdRowsArgs {               // dec_bwd_rows_kernel: the decoder's dX chain on few rows (16-row workgroups, weights straight from L2)
     const uint16_t* SP; int ldS; int KTX;     // s = x - sigmoid(l), P-layout [M][ldS], KTX = ldS/32 pixel k-steps
     const char* imgK3; int MT3;               // K-major image of the output layer's W (block (pixel k-step, hidden tile)), MT3 hidden tiles per k-step
@@ -142,6 +197,7 @@ struct LatentBwdArgs {
     uint16_t* DHP2;                   // its dhead, P-layout [B][2Dp] (written when prior_head != null)
     float* DHF2;                      // float32 mode: the same as float32 [B][2Dp]
 };
+void launch_latent_bwd(const LatentBwdArgs& a, hipStream_t st);
 struct BlockBwdArgs {                 // block_bwd_kernel: the dX chain of a BasicBlock on R <= 4096 rows
     const uint16_t* DH; int ldDH;     // dhead, bf16 P-layout [R][32*KTH]
     const char *imgH, *imgL2;         // backward images (MG-major: out-feature groups over hidden) of the head (KTH k-steps) and of l2 (KT1)
@@ -158,9 +214,6 @@ struct BlockBwdArgs {                 // block_bwd_kernel: the dX chain of a Bas
 };
 bool block_bwd_ok(const BlockBwdArgs& a);
 void launch_block_bwd(const BlockBwdArgs& a, hipStream_t st);
-bool block_fwd_ok(const BlockFwdArgs& a);
-bool block_fwd_shape_ok(const BlockFwdArgs& a);      // block_fwd_ok's shape part: reads no buffer pointer
-void launch_block_fwd(const BlockFwdArgs& a, hipStream_t st);
 
 struct OutBwdArgs {
     const uint16_t* G2; int ldG;      // last hidden activation, P-layout [M][32*KT]
@@ -177,6 +230,7 @@ struct OutBwdArgs {
     unsigned long long* stamps;       // diagnostic build only: [blocks*4 waves][8] phase cycle sums, else null
     int dbg;                          // DIAG builds only (option fake_s; timing only -- results are wrong): 32 = s rows read from the first 32 rows (no HBM stream)
 };
+void launch_out_bwd(const OutBwdArgs& a, hipStream_t st, hipEvent_t done = nullptr);
 
 struct DecBwdArgs {                  // dec_bwd_kernel: out_bwd_s + dX of the two tanh layers in one launch
     OutBwdArgs o;                     // SP (s), G2, gx, img1 (W3^T image), M, KT, NG, Xp32, ldG, DPP (dpre2 out); part = null
@@ -188,54 +242,8 @@ struct DecBwdArgs {                  // dec_bwd_kernel: out_bwd_s + dX of the tw
     uint16_t* DZH;                    // dz as bf16 [M][ldDZ], natural feature order (1-layer model: latent_bwd_kernel is its only reader), or null
     int nw;                           // 8: the 8-wave x 16-row shape (KT = 7 only), else 4 waves x 32 rows
 };
-
-struct WgradPArgs {
-    const uint16_t* X; int ldX; int IT;     // layer input, P-layout [rows][ldX]; IT = ldX/16 i-tiles
-    const uint16_t* G; int ldG; int JT;     // dpre of layer output, P-layout [rows][ldG]
-    int M, rows_per_split;                  // valid rows; rows per split (multiple of 64)
-    float* slabW;                           // [nsplit][IT*16][JT*16]
-    float* slabB;                           // [nsplit][JT*16]
-    const char* zero;                       // >= 512 B of zeros (source of rows >= M and of unused slots)
-    const float* rowscale;                  // optional [M]: G rows are multiplied by it (rounded to bf16) on the way in, else null
-    int dbg;                                // diagnostic ablations (DIAG build, option wg_debug; timing only -- results are wrong): 1 no DMA in the loop, 2 no A reads / MFMAs, 4 no bias sums, 8 no row scaling
-    unsigned long long* stamps;             // diagnostic build (STAMPS=1) only: wgradws_kernel's per-wave phase cycle sums [workgroups * waves][8], else null
-};
-
-// wgrad_rows_kernel (round 4): weight gradient of one linear map on FEW rows (<= 2 048) with the whole row reduction inside the workgroup
-// and the optimizer update in its epilogue -- no slabs, no reduction launch
-#define WGR_MAX_JOBS 6
-struct WgradRowsJob {
-    const uint16_t* X; int ldX;             // layer input, P-layout [R][ldX]
-    const uint16_t* G; int ldG;             // dpre of the layer's outputs, P-layout [R][ldG]
-    int R;                                  // valid rows
-    const float* rowscale;                  // optional [>= R rounded up to 32]: G rows are multiplied by it on the way in (the output layer: G = the stored s), else null
-    int sub0, sub1, split;                  // layer-table index of out-features < split and (merged mu | sigma head) >= split; sub1 = -1: none
-    int ib, jb, wg_begin;                   // filled by launch_wgrad_rows: 64-feature blocks of the in / out space, first workgroup
-};
-struct WgradPGroup {                        // up to 3 independent 8-wave weight gradients in one launch
-    WgradPArgs a[3];
-    int n;
-    int gx[3], gy[3];                       // j-blocks / i-blocks of each
-    int zbeg[4];                            // first blockIdx.z of each (zbeg[n] = total)
-};
-
-struct Chain2FwdArgs {                // chain2_fwd_kernel: the 2-layer model's per-sample blocks (q(z2|z1) and p(z1|z2)) on M rows, one launch
-    uint16_t* Z1P;                    // z1 rows, bf16 P-layout [M][32*KT0]: MADE here (z1 = mu1 + sigma1*eps1, iwae2.py:61) and kept for the decoder and the weight gradient
-    float* lqz1x;                     // log q(z1|x) per row (iwae2.py:123)
-    const char *e_img1, *e_img2, *e_imgh;     // MG-major forward images of encode_z1_to_z2: l1 (KT0 k-steps), l2, head (KTH k-steps each)
-    const char *d_img1, *d_img2, *d_imgh;     // ... of decode_z2_to_z1: l1 (KT1 k-steps), l2, head (KTH k-steps each)
-    int M, k, B, D0, D1;              // data rows, samples per image, images; latent widths of z1 and z2
-    uint16_t *EH1, *EH2;              // encode block's tanh activations, P-layout [M][32*KTH], kept for the backward pass (null: forward only)
-    float* EHEAD;                     // its head, fp32 [M][64*KT1] (mu2 | sigma2), or null
-    uint16_t* Z2P;                    // z2 rows, P-layout [M][32*KT1], or null
-    uint16_t *DH1, *DH2;              // decode block's tanh activations, or null
-    float* DHEAD;                     // its head, fp32 [M][64*KT0] (mu_p | sigma_p), or null
-    const float* head1; int ldH1;     // head of q(z1|x) per image [B][ldH1] (mu1 | sigma1 at 32*KT0): z1 in float32 for log p(z1|z2)
-    EpsSrc eps1, eps2;                // the draws of z1 and z2
-    float *lpz1z2, *lpz2, *lqz2z1;    // per-row log-densities (iwae2.py:122-124)
-};
-bool chain2_fwd_ok(int KT0, int KTH, int KT1, int M);
-void launch_chain2_fwd(const Chain2FwdArgs& a, hipStream_t st);
+bool out_bwd_has_s_mode(int KT);      // hidden widths with a compiled out_bwd_s_kernel / dec_bwd_kernel
+void launch_dec_bwd(const DecBwdArgs& d, hipStream_t st, hipEvent_t done = nullptr);
 
 struct GBlockBwdArgs {                // gblock_bwd_kernel: backward of a per-sample BasicBlock of the 2-layer model from its Gaussian head, one launch
     const char* imgH;                 // FORWARD image of the head (KTH k-steps, KTL groups: mu groups then sigma groups): the head is recomputed
@@ -257,16 +265,6 @@ struct GBlockBwdArgs {                // gblock_bwd_kernel: backward of a per-sa
 bool gblock_bwd_ok(int KT0, int KTH, int KT1, int M);
 void launch_gblock_bwd(int mode, const GBlockBwdArgs& a, hipStream_t st, hipEvent_t done = nullptr);
 
-struct GaussLpArgs {
-    const float* zhead; int ldZH; int Dzp;   // head that generated z (per image)
-    const float* phead; int ldPH; int Dpp;   // head that scores z (per row)
-    int D, M, k;
-    EpsSrc eps;
-    float* out;
-};
-
-
-
 struct GaussBwdArgs {
     int mode;
     const float* G;
@@ -278,7 +276,33 @@ struct GaussBwdArgs {
     uint16_t* DHP;                    // dhead bf16 P-layout [M][2Dp], or null
     float* DHF;                       // float32 mode: dhead float32 [M][2Dp], or null
 };
+void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st);
 
+// ---- bf16 step, weight gradients (wgrad_kernels.hip; iwae_train_step, iwae_forward_backward): activations x gradients -> fp32 slabs per row split
+struct WgradPArgs {
+    const uint16_t* X; int ldX; int IT;     // layer input, P-layout [rows][ldX]; IT = ldX/16 i-tiles
+    const uint16_t* G; int ldG; int JT;     // dpre of layer output, P-layout [rows][ldG]
+    int M, rows_per_split;                  // valid rows; rows per split (multiple of 64)
+    float* slabW;                           // [nsplit][IT*16][JT*16]
+    float* slabB;                           // [nsplit][JT*16]
+    const char* zero;                       // >= 512 B of zeros (source of rows >= M and of unused slots)
+    const float* rowscale;                  // optional [M]: G rows are multiplied by it (rounded to bf16) on the way in, else null
+    int dbg;                                // diagnostic ablations (DIAG build, option wg_debug; timing only -- results are wrong): 1 no DMA in the loop, 2 no A reads / MFMAs, 4 no bias sums, 8 no row scaling
+    unsigned long long* stamps;             // diagnostic build (STAMPS=1) only: wgradws_kernel's per-wave phase cycle sums [workgroups * waves][8], else null
+};
+void launch_wgradp(const WgradPArgs& a, int nsplit, int shape, hipStream_t st, hipEvent_t done = nullptr);      // shape: see wgradp_strip
+int wgradp_strip(int shape);          // j-tiles (16 out-features each) per block of a shape: 8 -> 8, 16 / 7 -> 16
+struct WgradPGroup {                        // up to 3 independent 8-wave weight gradients in one launch
+    WgradPArgs a[3];
+    int n;
+    int gx[3], gy[3];                       // j-blocks / i-blocks of each
+    int zbeg[4];                            // first blockIdx.z of each (zbeg[n] = total)
+};
+void launch_wgradp_group(const WgradPGroup& g, hipStream_t st);
+void launch_wgradws_group(const WgradPGroup& g, hipStream_t st);     // shape-7 (specialised waves) gradients, non-row-weighted, in one launch
+
+// ---- bf16 step, update (kernels.hip, its reduce / Adam part; iwae_train_step, iwae_forward_backward): slabs -> flat gradient -> Adam and the weight images;
+// the step's batch means
 struct LayerDesc {
     int Kin, Nout, joff;
     size_t offW, offb;                // offsets into the flat parameter / gradient buffers
@@ -289,47 +313,30 @@ struct LayerDesc {
     int block_begin;                  // first block of this layer in the flat elementwise grid (256 elements per block)
     int rblock_begin;                 // same for the slab-reduce grid (64 elements per block)
 };
-
-// done (here and below): a completion event that rides on the launch's dispatch packet (cheaper on both streams than hipEventRecord behind
-// the kernel: LAUNCH_EV in step_helpers.h); launch_out_bwd gives it to its LAST kernel.  A launcher without the argument cannot carry one.
-void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done = nullptr);
-void launch_out_bwd(const OutBwdArgs& a, hipStream_t st, hipEvent_t done = nullptr);
-bool bern_lse_ok(const DenseArgs& a);   // ... and can take lse_kernel's work for its rows (DenseArgs.lse_on)
-bool bern_pipe_ok(const DenseArgs& a);  // shapes bern_pipe_kernel covers (launch_dense falls back to dense_kernel<EPI_BERN> otherwise)
-bool out_bwd_has_s_mode(int KT);      // hidden widths with a compiled out_bwd_s_kernel / dec_bwd_kernel
-void launch_dec_bwd(const DecBwdArgs& d, hipStream_t st, hipEvent_t done = nullptr);
-void launch_wgradp(const WgradPArgs& a, int nsplit, int shape, hipStream_t st, hipEvent_t done = nullptr);      // shape: see wgradp_strip
-int wgradp_strip(int shape);          // j-tiles (16 out-features each) per block of a shape: 8 -> 8, 16 / 7 -> 16
-void launch_wgradp_group(const WgradPGroup& g, hipStream_t st);
-void launch_wgradws_group(const WgradPGroup& g, hipStream_t st);     // shape-7 (specialised waves) gradients, non-row-weighted, in one launch
-void launch_prep_rows(const float* x, const float* cond, int B, int X, int C, int Xp, int Bp, uint16_t* XP, hipStream_t st);
-void launch_gather_binarize(const uint8_t* data, const int32_t* order, int start, int N, int B, int X, int Xp, int Bp, uint64_t seed,
-                            uint32_t epoch, uint16_t* XP, float* xf, hipStream_t st,
-                            const uint8_t* labels = nullptr, int C = 0, float* cond_out = nullptr);      // labels: class ids of the resident set (conditional models)
-void launch_eps_gen(const EpsSrc& e, int M, int D, int ld, float* out, hipStream_t st, int max_blocks = 0);   // max_blocks > 0: grid-stride over at most that many blocks
-void launch_eps_gen_multi(const EpsSrc& e, int M, int D, int ld, float* out, int nsteps, size_t step_stride, hipStream_t st);   // steps e.step .. e.step + nsteps - 1, step s at out + s * step_stride
-void launch_sample(const SampleArgs& a, hipStream_t st);
-void launch_gauss_lp(const GaussLpArgs& a, hipStream_t st);
-void launch_lse(const LseArgs& a, hipStream_t st, hipEvent_t done = nullptr);
-void launch_latent_bwd(const LatentBwdArgs& a, hipStream_t st);
-void launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t st);
 // Sums the slabs of reduce blocks [first_block, first_block + nblocks) of the layer table into the flat gradient.
 // per_b != null: one extra block turns the per-image values into the batch means (scalars) of the step.
 // fuse_adam: the Adam update (grad_scale 1) + weight-image refresh of each element follows its slab sum in the same thread.
 void launch_reduce_grads(const LayerDesc* layers, int nlayers, int first_block, int nblocks, float* grad, float* param, float* mom, float* vel,
                          float alpha, float beta1, float beta2, float eps, int fuse_adam, const float* per_b, int B, float beta, float* scalars, hipStream_t st,
                          int first_block2 = 0, int nblocks2 = 0, hipEvent_t done = nullptr);      // (optional second block range of the same launch)
-// fuse_adam: Keras Adam (grad_scale 1) + image refresh in the epilogue; per_b != null: one extra block makes the step's batch means
-void launch_wgrad_rows(const WgradRowsJob* jobs, int njobs, const LayerDesc* layers, float* grad, float* param, float* mom, float* vel, float alpha,
-                       float beta1, float beta2, float eps, int fuse_adam, const float* per_b, int B, float beta, float* scalars, const char* zero, hipStream_t st);
 void launch_scalars(const float* per_b, int B, float beta, float* out, hipStream_t st);
 void launch_adam(const LayerDesc* layers, int nlayers, int nblocks, float* param, const float* grad, float* mom, float* vel,
                  float alpha, float gscale, float beta1, float beta2, float eps, int do_update, hipStream_t st, int first_block = 0, hipEvent_t done = nullptr);   // blocks [first_block, first_block + nblocks) of the elementwise grid
-void launch_export_rows(const float* in, int B, int k, float* out, hipStream_t st);
-void launch_export_z(const SampleArgs& a, float* zout, hipStream_t st);
-void launch_snis(const float* z, const float* wn, int B, int k, int D, float* out, hipStream_t st);
-void launch_unpack_p(const uint16_t* P, int rows, int F, int Fp, float* out, hipStream_t st);
-void launch_eps_dump(const EpsSrc& e, int B, int k, int D, float* out, hipStream_t st);
+
+// wgrad_rows_kernel (round 4): weight gradient of one linear map on FEW rows (<= 2 048) with the whole row reduction inside the workgroup
+// and the optimizer update in its epilogue -- no slabs, no reduction launch
+#define WGR_MAX_JOBS 6
+struct WgradRowsJob {
+    const uint16_t* X; int ldX;             // layer input, P-layout [R][ldX]
+    const uint16_t* G; int ldG;             // dpre of the layer's outputs, P-layout [R][ldG]
+    int R;                                  // valid rows
+    const float* rowscale;                  // optional [>= R rounded up to 32]: G rows are multiplied by it on the way in (the output layer: G = the stored s), else null
+    int sub0, sub1, split;                  // layer-table index of out-features < split and (merged mu | sigma head) >= split; sub1 = -1: none
+    int ib, jb, wg_begin;                   // filled by launch_wgrad_rows: 64-feature blocks of the in / out space, first workgroup
+};
+// fuse_adam: Keras Adam (grad_scale 1) + image refresh in the epilogue; per_b != null: one extra block makes the step's batch means
+void launch_wgrad_rows(const WgradRowsJob* jobs, int njobs, const LayerDesc* layers, float* grad, float* param, float* mom, float* vel, float alpha,
+                       float beta1, float beta2, float eps, int fuse_adam, const float* per_b, int B, float beta, float* scalars, const char* zero, hipStream_t st);
 
 // ---- float32 mode (fp32_kernels.hip)
 enum { GEMM_EPI_NONE = 0, GEMM_EPI_TANH = 1, GEMM_EPI_EXP = 2, GEMM_EPI_DTANH = 3, GEMM_EPI_BERN = 4 };

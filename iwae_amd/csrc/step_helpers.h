@@ -1,7 +1,9 @@
-// What both kernel files of the bf16 train / eval step need (kernels.hip, row_kernels.hip): no kernels; include it after device_helpers.h.
+// What more than one kernel file of the bf16 train / eval step needs (kernels.hip, row_kernels.hip, wgrad_kernels.hip): no kernels; include
+// it after device_helpers.h.
 // bern_pipe_kernel, dec_bwd_rows_kernel and lse_kernel must produce the same log-mean-exp bit for bit (lse_image), and every kernel that
 // makes z runs the same sample_step: each exists once, here.  They take LseArgs / SampleArgs / EpsSrc and are of no use to the analysis
-// kernels, hence not device_helpers.h.  Also here: the launch helper that puts a completion event on a kernel's dispatch packet (host side).
+// kernels, hence not device_helpers.h.  Also here: the counted vector-memory wait (wgradws_kernel in wgrad_kernels.hip, wgrad_rows_kernel in
+// kernels.hip) and the launch helper that puts a completion event on a kernel's dispatch packet (host side).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -288,6 +290,18 @@ __device__ __forceinline__ void lse_image(const LseArgs& a, const int b, const i
         pb[PB_T2 * B + b] = sum_t2 / (float)k;
         pb[PB_DREG * B + b] = dreg;
     }
+}
+
+// counted wait for any count 0..24 (wave-uniform)
+__device__ __forceinline__ void wait_vmem_but_ws(int n) {
+#define IWAE_WS_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
+    switch (n) {
+        IWAE_WS_CASE(0) IWAE_WS_CASE(1) IWAE_WS_CASE(2) IWAE_WS_CASE(3) IWAE_WS_CASE(4) IWAE_WS_CASE(5) IWAE_WS_CASE(6) IWAE_WS_CASE(7)
+        IWAE_WS_CASE(8) IWAE_WS_CASE(9) IWAE_WS_CASE(10) IWAE_WS_CASE(11) IWAE_WS_CASE(12) IWAE_WS_CASE(13) IWAE_WS_CASE(14) IWAE_WS_CASE(15)
+        IWAE_WS_CASE(16) IWAE_WS_CASE(17) IWAE_WS_CASE(18) IWAE_WS_CASE(19) IWAE_WS_CASE(20) IWAE_WS_CASE(21) IWAE_WS_CASE(22) IWAE_WS_CASE(23)
+        default: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
+    }
+#undef IWAE_WS_CASE
 }
 
 // Completion event riding on a kernel's own dispatch packet (hipExtLaunchKernelGGL stop event) instead of a separate

@@ -1,7 +1,7 @@
 """Developer script (no GPU needed): is a move of kernels between source files a pure move?  Compiles two sets of .hip files to gfx950 device
 assembly with build.sh's flags, cuts each .s into one piece per kernel and compares the pieces and the compiler's resource remarks.
 
-    python tools/dev/isa_compare.py --old OLD_CSRC/kernels.hip --new iwae_amd/csrc/kernels.hip iwae_amd/csrc/row_kernels.hip [--count-new iwae_amd/csrc/step_helpers.h] [--work DIR] [--flags "-DIWAE_DIAG"]
+    python tools/dev/isa_compare.py --old OLD_CSRC/kernels.hip --new iwae_amd/csrc/kernels.hip iwae_amd/csrc/wgrad_kernels.hip [--count-new iwae_amd/csrc/step_helpers.h] [--work DIR] [--flags=-DIWAE_DIAG]
 
 A piece runs from the kernel's .globl line to its .Lfunc_end label; comments and the .file / .ident / __hip_cuid lines are dropped, and the
 per-file function ordinal in local labels (.LBB<n>_<m>, .Lfunc_begin<n>, .Lfunc_end<n>, .Ltmp<n>) is rewritten away -- the ordinals number the
@@ -80,7 +80,7 @@ def main():
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--count-new", nargs="*", default=[], help="headers that came with the new files: counted with them in the line totals")
     ap.add_argument("--work", default="/tmp/isa_compare")
-    ap.add_argument("--flags", default="", help="extra compiler flags, e.g. -DIWAE_DIAG")
+    ap.add_argument("--flags", default="", help="extra compiler flags, as --flags=-DIWAE_DIAG (a single flag given as a separate word is taken for an option)")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     a = ap.parse_args()
     os.makedirs(a.work, exist_ok=True)
