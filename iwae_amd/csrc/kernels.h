@@ -301,7 +301,7 @@ struct WgradPGroup {                        // up to 3 independent 8-wave weight
 void launch_wgradp_group(const WgradPGroup& g, hipStream_t st);
 void launch_wgradws_group(const WgradPGroup& g, hipStream_t st);     // shape-7 (specialised waves) gradients, non-row-weighted, in one launch
 
-// ---- bf16 step, update (kernels.hip, its reduce / Adam part; iwae_train_step, iwae_forward_backward): slabs -> flat gradient -> Adam and the weight images;
+// ---- bf16 step, update (update_kernels.hip; iwae_train_step, iwae_forward_backward): slabs -> flat gradient -> Adam and the weight images;
 // the step's batch means
 struct LayerDesc {
     int Kin, Nout, joff;

@@ -1,5 +1,5 @@
 // The float32 step (iwae_config.precision = IWAE_PREC_FP32, and iwae_eval_llh / the analyses by default): host code; kernels in fp32_kernels.hip
-// and, shared with the bf16 path, kernels.hip / row_kernels.hip.  plan_step_f32 decides the step's kernels and streams once; forward_f32, backward_f32 and f32_dw
+// and, shared with the bf16 path, kernels.hip / row_kernels.hip / update_kernels.hip.  plan_step_f32 decides the step's kernels and streams once; forward_f32, backward_f32 and f32_dw
 // execute what it decided.
 #include <string.h>
 #include <algorithm>

@@ -1,9 +1,9 @@
-// What more than one kernel file of the bf16 train / eval step needs (kernels.hip, row_kernels.hip, wgrad_kernels.hip): no kernels; include
-// it after device_helpers.h.
+// What more than one kernel file of the bf16 train / eval step needs (kernels.hip, row_kernels.hip, wgrad_kernels.hip, update_kernels.hip): no
+// kernels; include it after device_helpers.h.
 // bern_pipe_kernel, dec_bwd_rows_kernel and lse_kernel must produce the same log-mean-exp bit for bit (lse_image), and every kernel that
 // makes z runs the same sample_step: each exists once, here.  They take LseArgs / SampleArgs / EpsSrc and are of no use to the analysis
 // kernels, hence not device_helpers.h.  Also here: the counted vector-memory wait (wgradws_kernel in wgrad_kernels.hip, wgrad_rows_kernel in
-// kernels.hip) and the launch helper that puts a completion event on a kernel's dispatch packet (host side).
+// update_kernels.hip) and the launch helper that puts a completion event on a kernel's dispatch packet (host side).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

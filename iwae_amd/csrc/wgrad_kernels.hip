@@ -1,5 +1,5 @@
 // gfx950 (CDNA4, MI355X) kernels of the bf16 train step that turn activations and their gradients into weight-gradient slabs
-// (reduce_grads_kernel in kernels.hip sums the slabs); the launchers are at the end of the file.
+// (reduce_grads_kernel in update_kernels.hip sums the slabs); the launchers are at the end of the file.
 // Layout rules: layout.h.  Kernel -> reference mapping (file:line in the reference, as at the top of kernels.hip):
 //   wgradp_kernel / wgradws_kernel / the *_group*_kernel
 //                                    tape.gradient(loss, w)   src/iwae1.py:155-159
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(NW * 64, (AI * BJ > 16) ? 2 : NW / 4) void wgradp_k
 // One barrier per stage: behind it the compute waves own stage c + 1 (landed, weighted) and the loaders own the buffer of
 // stage c (to refill).
 // ---------------------------------------------------------------------------------
-// (wait_vmem_but_ws, the counted wait for any count 0..24: step_helpers.h -- wgrad_rows_kernel in kernels.hip waits with it too)
+// (wait_vmem_but_ws, the counted wait for any count 0..24: step_helpers.h -- wgrad_rows_kernel in update_kernels.hip waits with it too)
 // <SC, BJ, NLW>: BJ = j-tiles per compute wave (the workgroup's G strip is 4*BJ tiles wide), NLW = loader waves.
 //   <.., 4, 4>: 224 x 256 features per workgroup, 8 + 4 waves at <= 168 registers (three per SIMD)
 //   <.., 2, 8>: 224 x 128 features, 8 + 8 waves at <= 128 registers (four per SIMD): a third of the DMA issues and a quarter of the

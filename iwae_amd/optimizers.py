@@ -1,6 +1,6 @@
 """The slice of keras.optimizers.Adam that main.py touches (main.py:93-94,128-133):
 Adam(lr, epsilon=1e-4), .learning_rate.numpy(), .learning_rate.assign(v).  The moment
-buffers and the update itself live on the GPU inside the model handle (adam_element in kernels.hip)."""
+buffers and the update itself live on the GPU inside the model handle (adam_element in update_kernels.hip)."""
 import numpy as np
 
 

@@ -1,4 +1,4 @@
-"""Shared by test_adam_host.py and test_gpu_adam.py: the float64 reference of the device's Adam update (adam_math in kernels.hip, the one
+"""Shared by test_adam_host.py and test_gpu_adam.py: the float64 reference of the device's Adam update (adam_math in update_kernels.hip, the one
 function inlined into adam_kernel, reduce_grads_kernel and wgrad_rows_kernel), per-element error bounds for it, constructed inputs and the
 hyper-parameter cases.
 

@@ -1,11 +1,11 @@
 """Developer script (no GPU needed): instruction mix per basic block of one kernel in the gfx950 ISA of the step's kernel files.
 usage: python tools/dev/isa_mix.py <mangled-name-substring> [min MFMAs per block to print] [file.hip ...]
-(compiles the given files of iwae_amd/csrc -- default: kernels.hip row_kernels.hip wgrad_kernels.hip -- to /tmp/iwae_k_<file>.s once per call)"""
+(compiles the given files of iwae_amd/csrc -- default: kernels.hip row_kernels.hip wgrad_kernels.hip update_kernels.hip -- to /tmp/iwae_k_<file>.s once per call)"""
 import collections, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pat, minm = sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 1
 s = ""
-for f in sys.argv[3:] or ["kernels.hip", "row_kernels.hip", "wgrad_kernels.hip"]:
+for f in sys.argv[3:] or ["kernels.hip", "row_kernels.hip", "wgrad_kernels.hip", "update_kernels.hip"]:
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-S", "--cuda-device-only",
                            "-o", "/tmp/iwae_k_%s.s" % f, os.path.join(root, "iwae_amd", "csrc", f)], stderr=subprocess.DEVNULL)
     s += open("/tmp/iwae_k_%s.s" % f).read()

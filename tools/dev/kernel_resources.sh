@@ -1,11 +1,11 @@
 #!/bin/bash
 # Developer script (no GPU needed): registers / spills / scratch / occupancy of every kernel in the given files of iwae_amd/csrc (default:
-# kernels.hip row_kernels.hip wgrad_kernels.hip), from hipcc's -Rpass-analysis=kernel-resource-usage remarks.
+# kernels.hip row_kernels.hip wgrad_kernels.hip update_kernels.hip), from hipcc's -Rpass-analysis=kernel-resource-usage remarks.
 # usage: tools/dev/kernel_resources.sh [grep pattern] [file.hip ...]
 cd "$(dirname "$0")/../../iwae_amd/csrc"
 PAT="${1:-.}"
 [ $# -gt 0 ] && shift
-FILES=("$@"); [ ${#FILES[@]} -eq 0 ] && FILES=(kernels.hip row_kernels.hip wgrad_kernels.hip)
+FILES=("$@"); [ ${#FILES[@]} -eq 0 ] && FILES=(kernels.hip row_kernels.hip wgrad_kernels.hip update_kernels.hip)
 for f in "${FILES[@]}"; do /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -c "$f" -o "/tmp/kres_$(basename "$f").o" -Rpass-analysis=kernel-resource-usage 2>&1; done | python3 -c "
 import sys, re, subprocess
 cur = None; rows = []
