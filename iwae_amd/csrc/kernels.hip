@@ -692,7 +692,9 @@ __device__ __forceinline__ void latent_image_part(const LatentBwdArgs& a, const 
                 for (int i = 0; i < 4; ++i) {
                     if (f0 + i < a.D) {
                         const float z = mu[i] + sgm[i] * e[u][i];
-                        const float t = cf[u].x * dzv[i] + cf[u].y * z + cf[u].z * (z - mu[i]) * rs2[i];      // (N(0,1) prior: up = z, 1/sigma_p = 1)
+                        // DReG's score term (tasks/task02.py:63-65): z - mu IS sigma eps; taken back out of the rounded z it loses ulp(mu) / (sigma |eps|)
+                        // -- 0.2 % on a unit at the sigma floor, the unit whose 1 / (sigma + 1e-6)^2 dominates the encoder's gradient
+                        const float t = cf[u].x * dzv[i] + cf[u].y * z + cf[u].z * (sgm[i] * e[u][i]) * rs2[i];      // (N(0,1) prior: up = z, 1/sigma_p = 1)
                         dmu[i] += t;
                         dsg[i] += t * e[u][i] + cf[u].w * rsg[i];
                     }
@@ -2912,7 +2914,7 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentBwdArgs a) {
                     if (f0 + i < a.D) {
                         const float z = mu[i] + sgm[i] * e[u][i];
                         const float up = (z - pmu[i]) * prs[i];                 // (z - mu_p)/sigma_p; = z for the N(0,1) prior
-                        const float t = cf[u].x * dzv[i] + cf[u].y * up * prs[i] + cf[u].z * (z - mu[i]) * rs2[i];
+                        const float t = cf[u].x * dzv[i] + cf[u].y * up * prs[i] + cf[u].z * (sgm[i] * e[u][i]) * rs2[i];      // (z - mu = sigma eps, exactly: latent_image_part)
                         dmu[i] += t;
                         dsg[i] += t * e[u][i] + cf[u].w * rsg[i];
                         // cf.y = -dLoss/dlpz: gradient of the prior head (task04.py:124-130), summed over the image's samples

@@ -1,7 +1,8 @@
-"""Shared by the GPU parity modules (test_gpu_parity.py, test_gpu_ragged_widths.py, test_gpu_sample_axis.py) and the host module
-test_sample_axis_host.py: the tolerance constants, the helpers that compare the device's flat gradient with the oracle's tensors and
-its per-row densities with the oracle at the DEVICE's own heads, and the inputs / checks of the sample axis (spread_params,
-ess_fraction, softmax_over_k, al_excess).
+"""Shared by the GPU parity modules (test_gpu_parity.py, test_gpu_ragged_widths.py, test_gpu_sample_axis.py, test_gpu_offinit.py) and the
+host modules test_sample_axis_host.py and test_offinit_host.py: the tolerance constants, the helpers that compare the device's flat
+gradient with the oracle's tensors and its per-row densities with the oracle at the DEVICE's own heads, the inputs / checks of the sample
+axis (spread_params, ess_fraction, softmax_over_k, al_excess) and the parameter constructors off the initialisation (sharp_params,
+saturated_params).
 
 Tolerances (the GEMM operands are bf16 with fp32 accumulation, BASELINE.json configs[1]):
   * against the oracle run with the SAME bf16 rounding points ("emu"): per-sample log densities |d| <= 0.03 nat, scalars
@@ -59,13 +60,75 @@ def spread_params(P, layers, head=0.1, dec_in=0.1):
         2-layer: P[2], P[3], P[6], P[7], P[10], P[11] -- so each q / p is close to N(0, 1) and log p(z) - log q nearly cancels;
       * the WEIGHT of the decoder's first layer is scaled by `dec_in` -- 1-layer: P[4][0]; 2-layer: P[12][0] -- so log p(x|z) varies
         little with z (its bias, and every other tensor, is untouched).
-    Nothing is pushed to an extreme: no logit saturates and sigma ~ 1 stays far from its floor."""
+    Nothing is pushed to an extreme: no logit saturates and sigma ~ 1 stays far from its floor.  (sharp_params and saturated_params below
+    are the constructors that DO push: a few posterior units down to the sigma floor, and the logits / tanh pre-activations into saturation.)"""
     out = [(np.array(W, dtype=np.float64), np.array(b, dtype=np.float64)) for W, b in P]
     heads, dec = ((2, 3), 4) if layers == 1 else ((2, 3, 6, 7, 10, 11), 12)
     for i in heads:
         out[i] = (out[i][0] * head, out[i][1] * head)
     out[dec] = (out[dec][0] * dec_in, out[dec][1])
     return out
+
+
+def sharp_units(D, n):
+    """The n units of a head of width D that sharp_params sharpens: spread evenly over the width, the first unit and the LAST unit D - 1
+    always among them (the last quad of a ragged width is cut: its tail lanes must see a sharp unit too)."""
+    if not 2 <= n <= D:
+        raise ValueError("sharp_params: %d units do not fit a head of width %d" % (n, D))
+    u = [int(round(j * (D - 1) / (n - 1))) for j in range(n)]
+    assert len(set(u)) == n and u[-1] == D - 1
+    return u
+
+
+def sharp_params(P, layers, shifts, heads):
+    """SHARP posteriors: in every named log-sigma layer (`heads`, indices into P: 3 = q(z|x) / q(z1|x) of either model, 7 = q(z2|z1) of the
+    2-layer model) shifts[j] is subtracted from the BIAS of unit sharp_units(D, len(shifts))[j]; everything else is untouched.  Returns a
+    NEW list, float64 in and out.  On spread_params the pre-activation a of every unit is ~0 (sigma ~ 1), so the sharpened unit has
+    exp(a) ~ exp(-shift): shifts (4.6, 9.2, 12.5, 16) give sigma = exp(a) + 1e-6 of ~1e-2, ~1e-4, ~4.7e-6 and ~1.1e-6 -- the floor is 1 %,
+    21 % and 90 % of the last three.  P[11], the head of p(z1|z2), is rejected: log p(z1|z2) divides by sigma_p^2, and at sigma_p ~ 1e-6
+    one bf16 rounding of z1 moves a row by ~1e8 nat (oracle: 8e8) -- no comparison in bf16 arithmetic says anything there.
+
+    What this makes visible (sigma = exp(a) + 1e-6: src/iwae1.py:34,42, iwae2.py:43,45) and spread_params cannot:
+      * the floor in the forward sigma of every head epilogue: at sigma ~ 1 dropping it moves the worst gradient tensor by 7e-6 and
+        iwae_elbo by 4e-6 nat (float64 oracle, (200, 100, 784), B = 5, k = 8) -- 14 times below even float32 mode's gradient bound.  At
+        four sharp units it moves the gradient by 0.21 .. 0.54 (DReG: 35) and iwae_elbo by 1.8 .. 2.6 nat;
+      * the derivative through exp, da = dsigma * exp(a) = dsigma * (sigma - 1e-6): taken as dsigma * sigma it moves the gradient by
+        0.21 .. 0.54 at four sharp units, by ~1e-6 at sigma ~ 1;
+      * DReG's second floor (tasks/task02.py:63: sigma + 1e-6 on a sigma that already holds one).
+    The comparison stays well conditioned in BOTH arithmetics (tests/test_offinit_host.py holds every case to it): a sharp unit pins z_u
+    to mu_u for every sample, so the weights over k stay spread (median ESS/k 0.16 .. 0.45 over the 1-layer cases of tests/_offinit_cases.py
+    with four sharp units), the rounding-aware oracle's rows stay within 0.003 .. 0.012 nat of the exact oracle's and its gradient within
+    0.0041 .. 0.0072 per tensor.  At k >= 50 four sharp units thin the weights too far (B = 3, k = 70: median ESS/k 0.048): two units,
+    shifts (9.2, 13.8), are used there (0.11 .. 0.16; rows within 0.015, gradient within 0.0096)."""
+    allowed = (3,) if layers == 1 else (3, 7)
+    out = [(np.array(W, dtype=np.float64), np.array(b, dtype=np.float64)) for W, b in P]
+    for h in heads:
+        if h not in allowed:
+            raise ValueError("sharp_params: P[%d] is not a log-sigma layer of an approximate posterior of the %d-layer model" % (h, layers))
+        W, b = out[h]
+        for u, s in zip(sharp_units(b.size, len(shifts)), shifts):
+            b[u] -= float(s)
+    return out
+
+
+def saturated_params(P, layers, out, hidden):
+    """SATURATED logits and tanh units: the WEIGHT of the output layer (1-layer: P[6]; 2-layer: P[14]) is multiplied by `out`, the weights
+    of the tanh layers of every encoder and decoder network (1-layer: P[0], P[1], P[4], P[5]; 2-layer: P[0], P[1], P[4], P[5], P[8], P[9],
+    P[12], P[13]) by `hidden`; biases are untouched.  Returns a NEW list, float64 in and out.
+
+    At (10, 3) on spread_params the largest |logit| is ~17 (50 at (30, 3), mean log p(x|z) -2600) where every other parity case stays
+    below ~6, and tanh units sit at |y| >= 0.999: the (x - 1/2) l - |l|/2 - log(1 + e^-|l|) form of the Bernoulli epilogues, the
+    copysign(rcp(1 + e) - 1/2, l) form of x - sigmoid(l), and 1 - y^2 at y -> +-1.  NOT an input for a bf16 comparison: the weights over k
+    become one-hot and one bf16 rounding of an operand moves the oracle's rows by 0.75 nat (bound 0.03; 3.5 nat at (30, 3)) -- the
+    float32-operand oracle stays within 9e-6 (3e-5) of the exact one, so these parameters go through float32 mode and the float32 row
+    evaluation only.  The case table (tests/_offinit_cases.py) runs (5, 8): under spread_params (10, 3) leaves NO unit of the decoder's second
+    layer at |y| >= 0.999, (5, 8) has 34 % there at max |logit| 16.6 and mean |log p(x|z)| 621.  The same holds for WIDE posteriors (log-sigma bias + 1.5 on every unit: 0.096 nat against 1.7e-6)."""
+    res = [(np.array(W, dtype=np.float64), np.array(b, dtype=np.float64)) for W, b in P]
+    last, tanh = (6, (0, 1, 4, 5)) if layers == 1 else (14, (0, 1, 4, 5, 8, 9, 12, 13))
+    res[last] = (res[last][0] * float(out), res[last][1])
+    for i in tanh:
+        res[i] = (res[i][0] * float(hidden), res[i][1])
+    return res
 
 
 def ess_fraction(al):
