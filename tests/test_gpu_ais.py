@@ -14,6 +14,7 @@ import pytest
 from oracle import iwae_np as O
 import make_golden as MG
 import _ais_ref as R
+import _row_eval_bodies as RB
 
 pytestmark = pytest.mark.gpu
 
@@ -35,14 +36,7 @@ def _net(nh, nl, xd):
     return _cache[key]
 
 
-def _tol(a32, a64, floor=1e-5):
-    return max(8.0 * float(np.max(np.abs(np.asarray(a32, dtype=np.float64) - np.asarray(a64, dtype=np.float64)))), floor)
-
-
-def _heads(r, init, N, D):
-    if init == "prior":
-        assert np.array_equal(r["q_mu"], np.zeros((N, D), np.float32)) and np.array_equal(r["q_sigma"], np.ones((N, D), np.float32))
-    return r["q_mu"], r["q_sigma"]
+_tol = RB._tol
 
 
 # ---------------------------------------------------------------- 1. one transition
@@ -52,26 +46,7 @@ def _heads(r, init, N, D):
 @pytest.mark.parametrize("nh,nl,xd", SHAPES)
 def test_single_transition_parity(gpu, nh, nl, xd, N, Cn, L, init):
     m, x, P = _net(nh, nl, xd)
-    x = x[:N]
-    betas, h = [0.3, 0.7], 0.3
-    eps0, mom, unif = R.noise(100 + 10 * N + Cn + L, 1, Cn, N, nl)
-    r = m.ais(x, n_chains=Cn, leapfrog=L, step_size=h, adapt=False, init=init, betas=betas, noise=(eps0, mom, unif), trace=True)
-    mu, sg = _heads(r, init, N, nl)
-    e64 = R.restate(P, x, mu, sg, betas, L, h, eps0, mom, unif, np.float64)
-    e32 = R.restate(P, x, mu, sg, betas, L, h, eps0, mom, unif, np.float32)
-    assert r["dH"].shape == (1, Cn, N) and r["z"].shape == (Cn, N, nl) and r["log_w"].shape == (Cn, N) and r["log_w"].dtype == np.float64
-    resolved = np.abs(e64["margin"][0]) > 1e-4                    # [C, N]: the decision does not hinge on float32 rounding
-    for key in ("dH", "log_w", "z"):
-        dev, w64, w32 = (np.asarray(a[key], dtype=np.float64) for a in (r, e64, e32))
-        if key == "z":
-            dev, w64, w32 = dev[resolved], w64[resolved], w32[resolved]
-        tol = _tol(w32, w64)
-        err = float(np.max(np.abs(dev - w64))) if dev.size else 0.0
-        print("%s: device error %.3g, float32 restatement %.3g, tolerance %.3g" % (key, err, tol / 8.0, tol))
-        assert err <= tol, (key, err, tol)
-    assert np.array_equal(r["accepted"][0][resolved], e64["accepted"][0][resolved])
-    assert np.array_equal(r["step_size"], np.full((Cn, N), h, np.float32))
-    np.testing.assert_allclose(r["log_px"], R.log_mean_exp(r["log_w"]), rtol=1e-12, atol=1e-12)
+    RB.ais_single_transition(m, x, P, nl, N, Cn, L, init)
 
 
 # ---------------------------------------------------------------- 2. trajectories
@@ -178,32 +153,10 @@ def test_device_noise_and_step_advance(gpu):
 
 
 # ---------------------------------------------------------------- 4. invariances, bitwise
-KEYS = ("log_w", "z", "step_size", "dH", "accepted", "log_px", "ess", "accept_rate")
-
-
 @pytest.mark.parametrize("nh,nl,xd", [(64, 8, 48), (200, 100, 784)])
 def test_chunking_position_and_repeat_are_bitwise(gpu, nh, nl, xd):
     m, x, P = _net(nh, nl, xd)
-    N, Cn, T = 5, 13, 5
-    kw = dict(n_chains=Cn, leapfrog=2, step_size=0.35, adapt=True, betas=np.linspace(0, 1, T + 1), trace=True)
-    runs = []
-    for chunk in (0, 1, 2, 0):                                    # default, 1, 2, and the default again (a repeat of the same call)
-        m.set_option("ais_t_chunk", chunk)
-        m.set_step(3, 20)
-        runs.append(m.ais(x, **kw))
-    m.set_option("ais_t_chunk", 0)
-    for other in runs[1:]:
-        for key in KEYS:
-            assert np.array_equal(runs[0][key], other[key]), key
-    assert 0 < runs[0]["accepted"].mean() and len(np.unique(runs[0]["step_size"])) > 1
-    # image 2 alone, told its global index, against the same image inside N = 5
-    m.set_step(3, 22)
-    one = m.ais(x[2:3], **kw)
-    for key in ("log_w", "step_size", "log_px", "ess"):
-        assert np.array_equal(one[key].reshape(one[key].shape[:-1]), runs[0][key][..., 2]), key
-    for key in ("dH", "accepted"):
-        assert np.array_equal(one[key][..., 0], runs[0][key][..., 2]), key
-    assert np.array_equal(one["z"][:, 0], runs[0]["z"][:, 2])
+    RB.ais_chunking_position_and_repeat_are_bitwise(m, x)
 
 
 # ---------------------------------------------------------------- 5. ground truth on the device

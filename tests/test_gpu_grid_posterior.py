@@ -13,74 +13,17 @@ import pytest
 
 from oracle import iwae_np as O
 import make_golden as MG
+import _grid_common as GC
+from _grid_common import _model, _lse, reference, _grid_case      # (shared with tests/test_gpu_aspect.py)
 
 pytestmark = pytest.mark.gpu
 
 EMU_ROW_ATOL = 0.03          # tests/test_gpu_parity.py: bf16 operands against the rounding-aware oracle
 
 
-def _model(nh, nl, x_dim=784, **kw):
-    from iwae_amd.native import NativeModel
-    return NativeModel(1, nh, nl, x_dim=x_dim, seed=123, **kw)
-
-
-def _lse(a, axis):
-    m = np.max(a, axis=axis, keepdims=True)
-    return np.squeeze(m, axis) + np.log(np.sum(np.exp(a - m), axis=axis))
-
-
-def reference(P, x, z, lw, rnd=None):
-    """float64 restatement (rnd = O.bf16_round: the bf16 eval precision's rounding points)."""
-    rnd = rnd or (lambda a: np.asarray(a, dtype=np.float64))
-    (W1, b1), (W2, b2), (Wm, bm), (Ws, bs), (V1, c1), (V2, c2), (V3, c3) = P
-    x = np.asarray(x, dtype=np.float64)
-    z = np.asarray(z, dtype=np.float64)
-    h = rnd(np.tanh(rnd(x) @ rnd(W1) + b1))
-    h = rnd(np.tanh(h @ rnd(W2) + b2))
-    mu, sigma = h @ rnd(Wm) + bm, np.exp(h @ rnd(Ws) + bs) + 1e-6                      # src/iwae1.py:39-42
-    g = rnd(np.tanh(rnd(z) @ rnd(V1) + c1))
-    g = rnd(np.tanh(g @ rnd(V2) + c2))
-    logits = g @ rnd(V3) + c3                                                           # src/iwae1.py:72-75
-    lpxz = x @ logits.T - np.sum(O.softplus(logits), axis=1)[None, :]                  # = sum_j bernoulli_log_prob
-    lj = lpxz + np.sum(O.normal_log_prob(z, 0.0, 1.0), axis=1)[None, :]
-    lw = np.zeros(z.shape[0]) if lw is None else np.asarray(lw, dtype=np.float64)
-    lpx = _lse(lj + lw[None, :], 1)
-    pi = np.exp(lj + lw[None, :] - lpx[:, None])
-    mean = pi @ z
-    dz = z[None, :, :] - mean[:, None, :]
-    cov = np.einsum("ng,ngd,nge->nde", pi, dz, dz)
-    lq = np.sum(O.normal_log_prob(z[None, :, :], mu[:, None, :], sigma[:, None, :]), axis=-1)
-    qw = np.exp(lq + lw[None, :])
-    return {"log_px": lpx, "post_mean": mean, "post_cov": cov, "q_mu": mu, "q_sigma": sigma, "q_mass": qw.sum(1),
-            "kl_q_post": np.sum(qw * (lq - lj + lpx[:, None]), axis=1), "log_joint": lj}
-
-
-def _grid_case(N, G, D, seed):
-    rng = np.random.default_rng(seed)
-    z = rng.uniform(-3.0, 3.0, (G, D)).astype(np.float32)
-    lw = np.log(rng.uniform(0.5, 1.5, G) * 6.0 ** D / G).astype(np.float32)        # non-uniform weights
-    return z, lw
-
-
 @pytest.mark.parametrize("nh,nl,xd", [(200, 2, 784), (64, 1, 784), (64, 4, 784), (64, 2, 48)])
 def test_float32_matches_float64(gpu, nh, nl, xd):
-    N, G = 37, 1531
-    x, P, _ = MG.inputs(1, nh, nl, xd, N, 1, 700 + nl + xd)
-    z, lw = _grid_case(N, G, nl, 11 + nl)
-    m = _model(nh, nl, xd)
-    m.set_params(O.flatten_params(P))
-    r = m.grid_posterior(x, z, lw, log_joint=True)
-    e = reference(P, x, z, lw)
-    assert r["log_px"].dtype == np.float64
-    assert np.max(np.abs(r["log_px"] - e["log_px"])) <= 2e-3
-    assert np.max(np.abs(r["kl_q_post"] - e["kl_q_post"])) <= 2e-3
-    assert np.max(np.abs(r["log_joint"] - e["log_joint"])) <= 2e-3
-    assert np.max(np.abs(r["post_mean"] - e["post_mean"])) <= 1e-3
-    assert np.max(np.abs(r["post_cov"] - e["post_cov"])) <= 1e-3
-    assert np.max(np.abs(r["q_mass"] - e["q_mass"])) <= 1e-4
-    np.testing.assert_allclose(r["q_mu"], e["q_mu"], atol=1e-4)
-    np.testing.assert_allclose(r["q_sigma"], e["q_sigma"], rtol=1e-4, atol=1e-6)
-    m.close()
+    GC.float32_matches_float64(nh, nl, xd)
 
 
 def test_bf16_eval_precision_matches_rounding_aware_restatement(gpu):

@@ -14,6 +14,7 @@ import pytest
 
 from oracle import iwae_np as O
 import _impute_ref as IM
+import _row_eval_bodies as RB
 
 pytestmark = pytest.mark.gpu
 
@@ -42,47 +43,22 @@ def _run(nh, nl, xd, N, k):
     key = (nh, nl, xd, N, k)
     if key not in _runs:
         m, x, P, mask = _net(nh, nl, xd)
-        x, mask = x[:N], mask[:N]
-        eps = IM.draws(N, k, nl)
-        r = m.impute(x, mask=mask, n_samples=k, noise=eps)
-        e64 = IM.restate(P, x, mask, r["q_mu"], r["q_sigma"], eps, np.float64)
-        e32 = IM.restate(P, x, mask, r["q_mu"], r["q_sigma"], eps, np.float32)
-        _runs[key] = (r, e64, e32)
+        _runs[key] = RB.impute_run(m, x, P, mask, nl, N, k)
     return _runs[key]
 
 
-def _tol(a32, a64, floor=1e-5):
-    return max(8.0 * float(np.max(np.abs(np.asarray(a32, dtype=np.float64) - np.asarray(a64, dtype=np.float64)))), floor)
-
-
-def _close(name, dev, w64, w32):
-    dev, w64 = np.asarray(dev, dtype=np.float64), np.asarray(w64, dtype=np.float64)
-    assert dev.shape == w64.shape, (name, dev.shape, w64.shape)
-    tol = _tol(w32, w64)
-    err = float(np.max(np.abs(dev - w64)))
-    print("%s: device error %.3g, float32 restatement %.3g, tolerance %.3g" % (name, err, tol / 8.0, tol))
-    assert err <= tol, (name, err, tol)
+_close = RB._close
 
 
 def _same(a, b, keys=KEYS):
-    for key in keys:
-        assert np.array_equal(a[key], b[key]), key
+    RB.same(a, b, keys)
 
 
 # ---------------------------------------------------------------- 1. parity of the weights
 @pytest.mark.parametrize("N,k", IM.CASES, ids=IM.CASE_IDS)
 @pytest.mark.parametrize("nh,nl,xd", IM.SHAPES)
 def test_weight_parity(gpu, nh, nl, xd, N, k):
-    r, e64, e32 = _run(nh, nl, xd, N, k)
-    assert r["log_w"].shape == (k, N) and r["log_px"].dtype == np.float64 and r["xhat"].shape == (N, xd) and r["ess"].shape == (N,)
-    for key in ("log_w", "log_px", "ess"):
-        _close(key, r[key], e64[key], e32[key])
-    # log_px and ess are what the device's own log_w says they are
-    lw = r["log_w"].astype(np.float64)
-    al = np.exp(lw - lw.max(axis=0)[None])
-    al /= al.sum(axis=0)[None]
-    np.testing.assert_allclose(r["log_px"], lw.max(axis=0) + np.log(np.mean(np.exp(lw - lw.max(axis=0)[None]), axis=0)), rtol=1e-12, atol=1e-12)
-    np.testing.assert_allclose(r["ess"], 1.0 / np.sum(al * al, axis=0), rtol=1e-6)
+    RB.impute_weight_parity(_run(nh, nl, xd, N, k), N, k, xd)
 
 
 # ---------------------------------------------------------------- 2. parity of the imputation
@@ -90,39 +66,14 @@ def test_weight_parity(gpu, nh, nl, xd, N, k):
 @pytest.mark.parametrize("nh,nl,xd", IM.SHAPES)
 def test_imputation_parity(gpu, nh, nl, xd, N, k):
     """xhat against sum_s softmax(DEVICE log_w)_s p64_s: the error of log_w (bounded above) is not charged to xhat."""
-    r, e64, e32 = _run(nh, nl, xd, N, k)
-    lw = r["log_w"].astype(np.float64)
-    al = np.exp(lw - lw.max(axis=0)[None])
-    al /= al.sum(axis=0)[None]
-    want = np.sum(al[:, :, None] * e64["p"], axis=0)
-    tol = _tol(e32["xhat"], e64["xhat"])
-    err = float(np.max(np.abs(r["xhat"].astype(np.float64) - want)))
-    print("xhat: device error %.3g, float32 restatement %.3g, tolerance %.3g; off the unweighted mean %.3g"
-          % (err, tol / 8.0, tol, float(np.max(np.abs(want - e64["p"].mean(axis=0))))))
-    assert err <= tol, (err, tol)
-    assert np.all(r["xhat"] >= 0.0) and np.all(r["xhat"] <= 1.0)
+    RB.impute_imputation_parity(_run(nh, nl, xd, N, k))
 
 
 def test_nothing_is_written_past_the_last_pixel(gpu):
     """x_dim = 53 (no multiple of the 16-pixel tile, nor of the 64-pixel pass): xhat into a device array with a guard row of sentinels behind
     it and a sentinel column range inside the padded width -- through the raw binding, both chunkings of the sum."""
-    import torch
-    from iwae_amd import _capi
     m, x, P, mask = _net(37, 5, 53)
-    for N, k in ((5, 13), (2, 65)):
-        xs, mk = np.ascontiguousarray(x[:N]), np.ascontiguousarray(mask[:N], dtype=np.uint8)
-        eps = IM.draws(N, k, 5)
-        guard = torch.full((N + 1, 53), -7.0, dtype=torch.float32, device="cuda")
-        lpx = np.zeros(N, dtype=np.float64)
-        o = _capi.ImputeOptions()
-        o.k, o.mask, o.eps = k, mk.ctypes.data, eps.ctypes.data
-        outs = _capi.ImputeOutputs()
-        outs.log_px, outs.xhat = lpx.ctypes.data, guard.data_ptr()
-        assert m.lib.iwae_impute(m.h, xs.ctypes.data, N, C.byref(o), C.byref(outs)) == 0
-        torch.cuda.synchronize()
-        g = guard.cpu().numpy()
-        assert np.all(g[N] == -7.0)
-        assert np.array_equal(g[:N], _run(37, 5, 53, N, k)[0]["xhat"])
+    RB.impute_nothing_past_the_last_pixel(m, x, mask, 5, 53, lambda N, k: _run(37, 5, 53, N, k)[0])
 
 
 # ---------------------------------------------------------------- 3. mask semantics
@@ -203,22 +154,7 @@ def test_device_noise_and_step_advance(gpu):
 @pytest.mark.parametrize("nh,nl,xd", [(64, 8, 48), (200, 100, 784)])
 def test_position_chunking_and_repeat_are_bitwise(gpu, nh, nl, xd, k):
     m, x, P, mask = _net(nh, nl, xd)
-    N = 5
-    eps = IM.draws(N, k, nl)
-    base = _run(nh, nl, xd, N, k)[0] if (N, k) in IM.CASES else m.impute(x, mask=mask, n_samples=k, noise=eps)
-    _same(base, m.impute(x, mask=mask, n_samples=k, noise=eps))                       # a repeat
-    m.set_option("impute_rows", k)                                                    # one image per launch
-    one_per_launch = m.impute(x, mask=mask, n_samples=k, noise=eps)
-    m.set_option("impute_rows", 0)
-    _same(base, one_per_launch)
-    for n in range(N):                                                                # every image alone, with its own draws
-        one = m.impute(x[n:n + 1], mask=mask[n:n + 1], n_samples=k, noise=np.ascontiguousarray(eps[:, n:n + 1]))
-        for key in ("xhat", "ess", "log_px", "q_mu", "q_sigma"):
-            assert np.array_equal(one[key][0], base[key][n]), (key, n)
-        assert np.array_equal(one["log_w"][:, 0], base["log_w"][:, n]), n
-    no_xhat = m.impute(x, mask=mask, n_samples=k, noise=eps, outputs=("log_px", "ess", "log_w", "q_mu", "q_sigma"))
-    assert "xhat" not in no_xhat
-    _same(base, no_xhat, keys=("log_px", "ess", "log_w", "q_mu", "q_sigma"))
+    RB.impute_position_chunking_and_repeat_are_bitwise(m, x, mask, nl, k, base=_run(nh, nl, xd, 5, k)[0] if (5, k) in IM.CASES else None)
 
 
 # ---------------------------------------------------------------- 6. rejections

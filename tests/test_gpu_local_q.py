@@ -15,6 +15,7 @@ from oracle import iwae_np as O
 import make_golden as MG
 import _ais_ref as R
 import _local_q_ref as LQ
+import _row_eval_bodies as RB
 
 pytestmark = pytest.mark.gpu
 
@@ -36,21 +37,11 @@ def _net(nh, nl, xd, precision="bf16"):
     return _cache[key]
 
 
-def _tol(a32, a64, floor=1e-5):
-    return max(8.0 * float(np.max(np.abs(np.asarray(a32, dtype=np.float64) - np.asarray(a64, dtype=np.float64)))), floor)
+_tol = RB._tol
 
 
-KEYS = ("grad", "bound", "mu", "sigma", "elbo", "iwae", "log_w")
-
-
-def _compare(r, e64, e32, keys=KEYS):
-    for key in keys:
-        dev, w64, w32 = (np.asarray(a[key], dtype=np.float64) for a in (r, e64, e32))
-        assert dev.shape == w64.shape, (key, dev.shape, w64.shape)
-        tol = _tol(w32, w64)
-        err = float(np.max(np.abs(dev - w64)))
-        print("%s: device error %.3g, float32 restatement %.3g, tolerance %.3g" % (key, err, tol / 8.0, tol))
-        assert err <= tol, (key, err, tol)
+KEYS = RB.LOCAL_KEYS
+_compare = RB.local_compare
 
 
 # ---------------------------------------------------------------- 1. per-iteration parity
@@ -60,18 +51,7 @@ def _compare(r, e64, e32, keys=KEYS):
 @pytest.mark.parametrize("nh,nl,xd", SHAPES)
 def test_iteration_parity(gpu, nh, nl, xd, N, S, T, objective):
     m, x, P = _net(nh, nl, xd)
-    x = x[:N]
-    E = 2
-    noise = np.random.default_rng(100 + 10 * N + S + T).standard_normal((T + E, S, N, nl)).astype(np.float32)
-    r = m.local_posterior(x, n_samples=S, n_iters=T, n_eval=E, objective=objective, lr=0.05, noise=noise, trace=True)
-    assert r["bound"].shape == (T, N) and r["grad"].shape == (N, 2 * nl) and r["log_w"].shape == (E * S, N) and r["elbo"].dtype == np.float64
-    e64 = LQ.restate(P, x, r["q_mu"], r["q_sigma"], noise, T, objective, lr=0.05, dtype=np.float64)
-    e32 = LQ.restate(P, x, r["q_mu"], r["q_sigma"], noise, T, objective, lr=0.05, dtype=np.float32)
-    _compare(r, e64, e32)
-    # the two outputs of the evaluation are what log_w says they are
-    lw = r["log_w"].astype(np.float64)
-    np.testing.assert_allclose(r["elbo"], lw.mean(axis=0), rtol=1e-12, atol=1e-12)
-    np.testing.assert_allclose(r["iwae"], R.log_mean_exp(lw), rtol=1e-12, atol=1e-12)
+    RB.local_iteration_parity(m, x, P, nl, N, S, T, objective)
 
 
 @pytest.mark.parametrize("objective", LQ.OBJECTIVES)
@@ -95,25 +75,7 @@ def test_iteration_parity_from_the_callers_start(gpu, objective):
 @pytest.mark.parametrize("nh,nl,xd", [(64, 8, 48), (200, 100, 784)])
 def test_chunking_position_and_repeat_are_bitwise(gpu, nh, nl, xd):
     m, x, P = _net(nh, nl, xd)
-    N, S, T = 5, 13, 10
-    kw = dict(n_samples=S, n_iters=T, n_eval=2, objective="iwae", lr=0.05, trace=True)
-    runs = []
-    for chunk in (0, 1, 3, 0):                                    # default, 1, 3, and the default again (a repeat of the same call)
-        m.set_option("local_t_chunk", chunk)
-        m.set_step(3, 20)
-        runs.append(m.local_posterior(x, **kw))
-    m.set_option("local_t_chunk", 0)
-    for other in runs[1:]:
-        for key in KEYS + ("q_mu", "q_sigma"):
-            assert np.array_equal(runs[0][key], other[key]), key
-    assert not np.array_equal(runs[0]["mu"], runs[0]["q_mu"])
-    # image 2 alone, told its global index, against the same image inside N = 5
-    m.set_step(3, 22)
-    one = m.local_posterior(x[2:3], **kw)
-    for key in ("mu", "sigma", "q_mu", "q_sigma", "grad", "elbo", "iwae"):
-        assert np.array_equal(one[key][0], runs[0][key][2]), key
-    for key in ("bound", "log_w"):
-        assert np.array_equal(one[key][:, 0], runs[0][key][:, 2]), key
+    RB.local_chunking_position_and_repeat_are_bitwise(m, x)
 
 
 # ---------------------------------------------------------------- 3. anchors

@@ -249,39 +249,8 @@ def test_two_layer_kernel_variants_agree(gpu, B, k):
     layer of q(z2|z1) and p(z1|z2), the z2 sampling, the three log-densities and their gradients without a round trip through HBM)
     against the same mathematics as separate launches (dense_kernel x 6, sample_kernel, gauss_lp_kernel, gauss_bwd_kernel x 2,
     dense_kernel<EPI_DX> x 6): values, per-row densities and all 26 gradient tensors, on host noise and on the device's own."""
-    nh, nl = [200, 100], [100, 50]
-    x, P, eps = MG.inputs(2, nh, nl, 784, B, k, 5150 + B)
-
-    def run(opts, e):
-        m = _model(2, nh, nl, options=opts)
-        m.set_params(O.flatten_params(P))
-        m.set_step(9, 2)
-        r = m.forward_backward(x, k, 1.0, "iwae_elbo", eps=e, want=("lpz", "lpz2", "lqzx", "lqzx2", "z2"))
-        # round 4: every variant's per-row densities against the oracle evaluated at THAT run's own Gaussian heads -- no window for outliers
-        e1, e2 = e if e is not None else (philox_np.device_eps(123, 9, B, k, nl[0], stream=0, batch_offset=2),
-                                          philox_np.device_eps(123, 9, B, k, nl[1], stream=1, batch_offset=2))
-        at = _densities_at_device_heads_2layer(m, e1, e2, B, k, nl)
-        for a, b in (("lpz", "lpz1z2"), ("lpz2", "lpz2"), ("lqzx", "lqz1x"), ("lqzx2", "lqz2z1")):
-            err = np.abs(r[a] - at[b])
-            assert err.max() < (5e-3 if e is not None else 2e-2), (opts, b, err.max())      # (device noise: the host restates the float32 draws in float64, d eps ~ 1e-7, divided by sigma_p)
-        g = m.get_grads().astype(np.float64)
-        m.close()
-        return r, g
-
-    for e, ref_opts in ((eps, {"no_chain2": 1}), (None, {"no_chain2": 1}), (eps, {"no_chain2_bwd": 1})):
-        r0, g0 = run(ref_opts, e)
-        r1, g1 = run({}, e)
-        # the fused kernels start their accumulators from the bias, the separate launches add it at the end: float32 sums in another
-        # order, so a bf16 activation flips by an ulp here and there and moves the densities of THAT row (log p(z1|z2) of a row with a small
-        # sigma_p by several 0.1 nat at random init, |lpz| ~ 200-400) -- the typical row agrees to float32 rounding; the rows that do not are
-        # accounted for inside run(): each variant matches the oracle at its own heads on every row
-        for key in ("lpz", "lpz2", "lqzx2"):
-            err = np.abs(r1[key] - r0[key])
-            assert np.quantile(err, 0.9) < 2e-3 and err.max() < 1.0, (key, np.quantile(err, 0.9), err.max())
-        errz = np.abs(r1["z2"] - r0["z2"])
-        assert np.quantile(errz, 0.98) < 2e-3 and errz.max() < 0.05
-        assert abs(r1["iwae_elbo"] - r0["iwae_elbo"]) < 2e-2
-        assert np.linalg.norm(g1 - g0) / np.linalg.norm(g0) < 5e-3
+    import _width_bodies as WB      # (the body is shared with tests/test_gpu_aspect.py)
+    WB.two_layer_kernel_variants_agree([200, 100], [100, 50], 784, B, k, 5150 + B)
 
 
 @pytest.mark.parametrize("layers,B,k,obj", [(1, 120, 50, "iwae_elbo"), (1, 120, 50, "dreg"), (1, 90, 50, "iwae_eq14"), (1, 2000, 5, "iwae_elbo"),

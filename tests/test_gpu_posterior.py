@@ -17,6 +17,7 @@ import make_golden as MG
 import _parity_common as PC
 import _impute_ref as IM
 import _posterior_ref as PR
+import _row_eval_bodies as RB
 
 pytestmark = pytest.mark.gpu
 
@@ -39,9 +40,7 @@ def _net(nh, nl, xd):
     return _cache[key]
 
 
-def unif(R, N, k=0):
-    return np.random.default_rng(500 + 10 * N + R + k).random((R, N)).astype(np.float32)
-
+unif = RB.unif
 
 _runs = {}
 
@@ -52,22 +51,12 @@ def _run(nh, nl, xd, N, k):
     key = (nh, nl, xd, N, k)
     if key not in _runs:
         m, x, P, mask = _net(nh, nl, xd)
-        x, mask = x[:N], mask[:N]
-        eps = IM.draws(N, k, nl)
-        r = m.posterior(x, mask=mask, n_samples=k, n_draws=R0, noise=eps, uniforms=unif(R0, N))
-        e64 = PR.restate(P, x, mask, r["q_mu"], r["q_sigma"], eps, np.float64)
-        e32 = PR.restate(P, x, mask, r["q_mu"], r["q_sigma"], eps, np.float32)
-        _runs[key] = (r, e64, e32)
+        _runs[key] = RB.posterior_run(m, x, P, mask, nl, N, k)
     return _runs[key]
 
 
-def _tol(a32, a64, floor=1e-5):
-    return max(8.0 * float(np.max(np.abs(np.asarray(a32, dtype=np.float64) - np.asarray(a64, dtype=np.float64)))), floor)
-
-
 def _same(a, b, keys=KEYS):
-    for key in keys:
-        assert a[key].shape == b[key].shape and np.array_equal(a[key], b[key]), key
+    RB.same(a, b, keys)
 
 
 # ---------------------------------------------------------------- 1. the outputs shared with iwae_impute
@@ -88,47 +77,16 @@ def test_shared_outputs_are_imputes_bitwise(gpu, nh, nl, xd, N, k):
 @pytest.mark.parametrize("N,k", IM.CASES, ids=IM.CASE_IDS)
 @pytest.mark.parametrize("nh,nl,xd", IM.SHAPES)
 def test_moment_parity(gpu, nh, nl, xd, N, k):
-    r, e64, e32 = _run(nh, nl, xd, N, k)
     m, x, P, mask = _net(nh, nl, xd)
-    assert r["mean"].shape == (N, nl) and r["cov"].shape == (N, nl, nl) and r["mean"].dtype == np.float32 and r["cov"].dtype == np.float32
-    want = PR.moments(PR.weights(r["log_w"], np.float64), r["q_mu"], r["q_sigma"], IM.draws(N, k, nl), np.float64)
-    for key in ("mean", "cov"):
-        tol = _tol(e32[key], e64[key])
-        err = float(np.max(np.abs(r[key].astype(np.float64) - want[key])))
-        print("%s: device error %.3g, float32 restatement %.3g, tolerance %.3g" % (key, err, tol / 8.0, tol))
-        assert err <= tol, (key, err, tol)
-    assert np.array_equal(r["cov"], np.swapaxes(r["cov"], 1, 2))
-    assert np.all(np.diagonal(r["cov"], axis1=1, axis2=2) >= 0.0)
-    no_cov = m.posterior(x[:N], mask=mask[:N], n_samples=k, noise=IM.draws(N, k, nl), outputs=("mean",))
-    assert "cov" not in no_cov and np.array_equal(no_cov["mean"], r["mean"])
+    RB.posterior_moment_parity(m, x, mask, nl, N, k, _run(nh, nl, xd, N, k))
 
 
 # ---------------------------------------------------------------- 3. ragged widths
 def test_nothing_is_written_past_the_last_feature(gpu):
     """D = 5, x_dim = 53: cov [N, 5, 5], z [R, N, 5] and idx [R, N] into device arrays with a guard row of sentinels behind them, through
     the raw binding, one chunk per image and two."""
-    import torch
-    from iwae_amd import _capi
     m, x, P, mask = _net(37, 5, 53)
-    for N, k in ((5, 13), (2, 65)):
-        xs, mk = np.ascontiguousarray(x[:N]), np.ascontiguousarray(mask[:N], dtype=np.uint8)
-        eps, u = IM.draws(N, k, 5), unif(R0, N)
-        cov = torch.full((N + 1, 5, 5), -7.0, dtype=torch.float32, device="cuda")
-        mean = torch.full((N + 1, 5), -7.0, dtype=torch.float32, device="cuda")
-        z = torch.full((R0 * N + 1, 5), -7.0, dtype=torch.float32, device="cuda")
-        idx = torch.full((R0 * N + 1,), -7, dtype=torch.int32, device="cuda")
-        lpx = np.zeros(N, dtype=np.float64)
-        o = _capi.PosteriorOptions()
-        o.k, o.R, o.mask, o.eps, o.unif = k, R0, mk.ctypes.data, eps.ctypes.data, u.ctypes.data
-        outs = _capi.PosteriorOutputs()
-        outs.log_px, outs.cov, outs.mean, outs.z, outs.idx = lpx.ctypes.data, cov.data_ptr(), mean.data_ptr(), z.data_ptr(), idx.data_ptr()
-        assert m.lib.iwae_posterior(m.h, xs.ctypes.data, N, C.byref(o), C.byref(outs)) == 0
-        torch.cuda.synchronize()
-        base = _run(37, 5, 53, N, k)[0]
-        for name, got, rows in (("cov", cov, N), ("mean", mean, N), ("z", z, R0 * N), ("idx", idx, R0 * N)):
-            g = got.cpu().numpy()
-            assert np.all(g[rows] == -7), name
-            assert np.array_equal(g[:rows].reshape(base[name].shape), base[name]), name
+    RB.posterior_nothing_past_the_last_feature(m, x, mask, 5, lambda N, k: _run(37, 5, 53, N, k)[0])
 
 
 # ---------------------------------------------------------------- 4. resampling
@@ -150,19 +108,7 @@ def test_indices_and_draws(gpu, k, R):
     m, x, P, mask = _net(64, 8, 48)
     N = 3
     eps, w = _weights_run(k)
-    u = unif(R, N, k)
-    r = m.posterior(x[:N], mask=mask[:N], n_samples=k, n_draws=R, noise=eps, uniforms=u)
-    assert np.array_equal(r["log_w"], w["log_w"])
-    assert r["idx"].dtype == np.int32 and r["idx"].shape == (R, N) and r["z"].shape == (R, N, 8)
-    assert np.array_equal(r["idx"], PR.indices(r["log_w"], u))
-    assert np.array_equal(r["u"], u)
-    want = r["q_mu"].astype(np.float64)[None] + r["q_sigma"].astype(np.float64)[None] * eps.astype(np.float64)[r["idx"], np.arange(N)[None]]
-    np.testing.assert_allclose(r["z"], want, rtol=1e-6, atol=1e-6)
-    flat_idx, flat_z = r["idx"].T.reshape(N, R), np.swapaxes(r["z"], 0, 1)
-    for n in range(N):                                             # rows with equal idx are bitwise equal
-        first = {}
-        for j, s in enumerate(flat_idx[n]):
-            assert np.array_equal(flat_z[n, j], flat_z[n, first.setdefault(int(s), j)]), (n, j)
+    RB.posterior_indices_and_draws(m, x, mask, 8, N, k, R, eps, w)
 
 
 def test_edge_uniforms_take_the_first_and_the_last_weighted_draw(gpu):
@@ -211,25 +157,7 @@ def test_device_noise_step_and_offset(gpu):
 @pytest.mark.parametrize("nh,nl,xd", [(64, 8, 48), (200, 100, 784)])
 def test_position_chunking_and_repeat_are_bitwise(gpu, nh, nl, xd, k):
     m, x, P, mask = _net(nh, nl, xd)
-    N = 5
-    eps, u = IM.draws(N, k, nl), unif(R0, N)
-    base = _run(nh, nl, xd, N, k)[0]
-    call = lambda xs: m.posterior(xs, mask=mask, n_samples=k, n_draws=R0, noise=eps, uniforms=u)      # noqa: E731
-    _same(base, call(x))                                                              # a repeat
-    m.set_option("impute_rows", k)                                                    # one image per launch
-    one_per_launch = call(x)
-    m.set_option("impute_rows", 0)
-    _same(base, one_per_launch)
-    for n in range(N):                                                                # every image alone, with its own draws and uniforms
-        one = m.posterior(x[n:n + 1], mask=mask[n:n + 1], n_samples=k, n_draws=R0, noise=np.ascontiguousarray(eps[:, n:n + 1]),
-                          uniforms=np.ascontiguousarray(u[:, n:n + 1]))
-        for key in ("log_px", "ess", "mean", "cov", "q_mu", "q_sigma"):
-            assert np.array_equal(one[key][0], base[key][n]), (key, n)
-        for key in ("log_w", "idx", "z", "u"):
-            assert np.array_equal(one[key][:, 0], base[key][:, n]), (key, n)
-    xn = np.where(mask, x, np.float32(np.nan)).astype(np.float32)                     # what x holds at an unobserved pixel reaches nothing
-    assert np.isnan(xn).any()
-    _same(base, call(xn))
+    RB.posterior_position_chunking_and_repeat_are_bitwise(m, x, mask, nl, k, _run(nh, nl, xd, 5, k)[0])
 
 
 # ---------------------------------------------------------------- 7. ground truth on the device
