@@ -156,6 +156,28 @@ int iwae_grad_devptr(iwae_handle h, void** dev_ptr, size_t* n);
 int iwae_forward_backward_split(iwae_handle h, const float* x, int32_t B, int32_t k, float beta, int32_t objective,
                                 const float* eps, void** side_stream, size_t* side_offset);
 int iwae_adam_step(iwae_handle h, float lr, float grad_scale);      /* keras Adam(lr, epsilon=1e-4), main.py:93 */
+
+/* Training on incomplete images (Mattei & Frellsen 2019, MIWAE, arXiv 1902.02102): iwae_forward / iwae_forward_backward /
+ * iwae_train_step with a per-pixel mask.  No reference counterpart.  DESIGN.md section 19.
+ * mask [B, x_dim], host or device, non-zero = observed: exactly iwae_impute_options.mask.  mask == NULL delegates to the unmasked
+ * call, bitwise.  With a mask the step differs in three places: the encoder reads xin = m ? x : 0 (iwae_impute's convention),
+ * log p(x|z) sums the Bernoulli terms of the observed pixels only, and the backward pass starts from s = m ? x - sigmoid(l) : 0
+ * (the encoder's first-layer weight gradient is taken against xin).  Unobserved pixels are SELECTED out, never multiplied out:
+ * what x holds where m = 0 (NaN, garbage) reaches no scalar, tensor, gradient, parameter or Adam moment, bitwise -- iwae_impute's
+ * contract.  An image with nothing observed has log p(x_obs|z) = 0 exactly, log_w = log p(z) - log q(z|x).
+ * iwae_scalars.mean_lpxz and want->lpxz / log_w / al / z / snis_z / lpz / lqzx are those of the masked weights; IWAE_OBJ_VAE_ELBO_KL
+ * uses the masked mean_lpxz.  Noise (eps, the handle's step) and the step's semantics are the unmasked calls'.  Bitwise repeatable.
+ * Models: the 1-layer unconditional model on a handle created with precision = IWAE_PREC_FP32, all five 1-layer objectives.
+ * A bf16 handle, a 2-layer handle, cond_dim > 0, a handle with communicators (iwae_comm_init), want->logits != NULL (the fast route
+ * never materialises logits), B <= 0, k <= 0 or x NULL: IWAE_ERR_ARG before any launch; the noise step, parameters, gradient
+ * buffer and Adam state are unchanged.  Options no_masked_out_fused / masked_out_min_rows (tools/README.md) pick between the two
+ * routes of the output layer. */
+int iwae_forward_masked(iwae_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta, const float* eps,
+                        iwae_scalars* scalars, const iwae_tensors* want);
+int iwae_forward_backward_masked(iwae_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta,
+                                 int32_t objective, const float* eps, iwae_scalars* scalars, const iwae_tensors* want);
+int iwae_train_step_masked(iwae_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta, float lr,
+                           int32_t objective, const float* eps, iwae_scalars* scalars, const iwae_tensors* want);
 /* keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon) hyper-parameters of this handle's optimizer; the default
  * is what the reference trains with: Adam(lr, epsilon=1e-4) = (0.9, 0.999, 1e-4), main.py:93.  Keras form: epsilon is
  * added to sqrt(v) outside the bias correction.  They take effect with the next update and are NOT part of the saved
@@ -554,7 +576,7 @@ int iwae_train_step_dataset(iwae_handle h, int32_t start, int32_t B, int32_t k, 
  * step (an event record costs a few us of stream bubble, so bench.py samples rather than timing every launch); 0 switches
  * it off.  name: "decoder_fwd" (whole decoder forward + log-likelihood), "out_bwd" (output-layer backward), "decoder_bwd" (the decoder's whole dX chain where it is one launch), "wgrad_out",
  * "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent" (the decoder's other backward kernels), "latent_bwd",
- * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel), "impute" (likewise both passes of iwae_impute's impute_rows_kernel, and pass (a) of iwae_posterior), "posterior" (likewise iwae_posterior's moments and merge launches).  A kernel a configuration does not launch reports 0 launches. */
+ * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel), "impute" (likewise both passes of iwae_impute's impute_rows_kernel, and pass (a) of iwae_posterior), "posterior" (likewise iwae_posterior's moments and merge launches), "masked_out" (likewise the masked float32 step's masked_out_f32_kernel).  A kernel a configuration does not launch reports 0 launches. */
 int iwae_enable_timing(iwae_handle h, int32_t enable);
 int iwae_kernel_time(iwae_handle h, const char* name, double* avg_us, int64_t* launches);
 

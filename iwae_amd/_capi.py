@@ -124,6 +124,9 @@ SYMBOLS = {
     "iwae_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, C.POINTER(Scalars), C.POINTER(Tensors)]),
     "iwae_train_step": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _P, C.POINTER(Scalars), C.POINTER(Tensors)]),
     "iwae_forward_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, C.POINTER(Scalars), C.POINTER(Tensors)]),
+    "iwae_forward_masked": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, _P, C.POINTER(Scalars), C.POINTER(Tensors)]),
+    "iwae_train_step_masked": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _P, C.POINTER(Scalars), C.POINTER(Tensors)]),
+    "iwae_forward_backward_masked": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, C.POINTER(Scalars), C.POINTER(Tensors)]),
     "iwae_forward_backward_split": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "iwae_grad_devptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "iwae_adam_step": (C.c_int, [_P, C.c_float, C.c_float]),
@@ -161,7 +164,7 @@ SYMBOLS = {
 
 _lib = None
 
-_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "device_helpers.h", "fp32_kernels.hip", "grid_kernels.hip", "impute_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "local_kernels.hip", "model.h", "model.hip", "moments_kernels.hip", "posterior_kernels.hip", "row_kernels.hip", "step_f32.hip", "step_helpers.h", "update_kernels.hip", "wgrad_kernels.hip",
+_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "device_helpers.h", "fp32_kernels.hip", "grid_kernels.hip", "impute_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "local_kernels.hip", "masked_kernels.hip", "model.h", "model.hip", "moments_kernels.hip", "posterior_kernels.hip", "row_kernels.hip", "step_f32.hip", "step_helpers.h", "update_kernels.hip", "wgrad_kernels.hip",
                os.path.join("..", "..", "include", "iwae_amd.h"))
 
 

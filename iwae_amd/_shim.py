@@ -110,14 +110,20 @@ class BaseIWAE:
                 res[_RENAME_2L[k] if self.n_layers == 2 else k] = as_tensor(v)
         return res
 
-    def call(self, x, n_samples, beta=1.0, outputs=None, eps=None):
-        raw = self._net.forward(np.asarray(x, dtype=np.float32), int(n_samples), float(beta), eps=eps, want=self._want(outputs))
+    def _check_mask(self, mask):
+        """mask [B, x_dim], non-zero = observed (training on incomplete images, Mattei & Frellsen 2019): float32 handles of the 1-layer
+        unconditional model; None: every pixel observed (the reference's call)."""
+
+    def call(self, x, n_samples, beta=1.0, outputs=None, eps=None, mask=None):
+        if mask is not None:
+            self._check_mask(mask)
+        raw = self._net.forward(np.asarray(x, dtype=np.float32), int(n_samples), float(beta), eps=eps, want=self._want(outputs), mask=mask)
         return self._result(raw)
 
     __call__ = call
 
-    def val_step(self, x, n_samples, beta, outputs=None):
-        return self.call(x, n_samples, beta, outputs=outputs)
+    def val_step(self, x, n_samples, beta, outputs=None, mask=None):
+        return self.call(x, n_samples, beta, outputs=outputs, mask=mask)
 
     def _bind_optimizer(self, optimizer):
         """Hand the Keras-style optimizer's (beta_1, beta_2, epsilon) to the device optimizer when they change."""
@@ -126,12 +132,14 @@ class BaseIWAE:
             self._net.set_adam(*hyper)
             self._adam_hyper = hyper
 
-    def train_step(self, x, n_samples, beta, optimizer, objective="vae_elbo", outputs=None, eps=None):
+    def train_step(self, x, n_samples, beta, optimizer, objective="vae_elbo", outputs=None, eps=None, mask=None):
         if objective not in self.scalar_keys:
             raise KeyError(objective)          # res[objective] in the reference (src/iwae1.py:157)
+        if mask is not None:
+            self._check_mask(mask)
         self._bind_optimizer(optimizer)
         raw = self._net.train_step(np.asarray(x, dtype=np.float32), int(n_samples), float(beta),
-                                   float(optimizer.learning_rate), objective, eps=eps, want=self._want(outputs))
+                                   float(optimizer.learning_rate), objective, eps=eps, want=self._want(outputs), mask=mask)
         optimizer.iterations += 1
         return self._result(raw)
 

@@ -405,6 +405,23 @@ struct ReduceSlabsJobs { ReduceSlabsJob job[REDUCE_SLABS_MAX_JOBS]; int n; };
 void launch_reduce_slabs_multi_f32(ReduceSlabsJobs& jobs, hipStream_t st);
 void launch_bern_f32(const float* logits, size_t ld, const float* x, int X, int M, int k, float* lpxz, hipStream_t st);
 void launch_dl_f32(float* logits, size_t ld, const float* x, int X, int M, int k, const float* gx, hipStream_t st);
+// ---- the masked float32 step (masked_kernels.hip): mask [B][X] uint8, non-zero = observed; what x holds elsewhere is never an operand
+void launch_masked_bern_f32(const float* logits, size_t ld, const float* x, const uint8_t* mask, int X, int M, int k, float* lpxz, hipStream_t st);      // log p(x_obs|z) per row
+void launch_masked_s_f32(float* logits, size_t ld, const float* x, const uint8_t* mask, int X, int M, int k, hipStream_t st);      // in place: s = m ? x - sigmoid(l) : 0
+void launch_masked_code(const float* x, const uint8_t* mask, long n, float* xc, hipStream_t st);      // xc = m ? x : the hole code masked_out_f32_kernel compares against
+// masked_out_f32_kernel: the output layer g2 W3 + b3 with the masked likelihood [+ s] in its epilogue, rows stationary; no logits in memory
+struct MaskedOutF32Args {
+    const float* G2; int ldg;              // the second tanh layer's activations [M][ldg]
+    int M, H, X;                           // data rows, hidden width, pixels
+    const float *W3, *b3;                  // the Keras kernel [H][X] and bias inside the float32 master parameters
+    const float* XC; int k;                // launch_masked_code's [B][X]; row m belongs to image m / k
+    float* S; int ldS;                     // s = m ? x - sigmoid(l) : 0 [M][ldS] for the backward pass, or null (forward only)
+    float* lpxz;                           // [M] log p(x_obs|z) per row
+    const char* zero;                      // >= 1 KiB of zeros
+    int kslabs;                            // > 0: the general route's output-layer GEMM splits K into chunks of 16 kslabs in-features (launch_gemm_f32_fewrows); the kernel adds its partial chains the same way
+};
+bool masked_out_f32_ok(const MaskedOutF32Args& a);      // reads H, X, k, W3, b3
+void launch_masked_out_f32(const MaskedOutF32Args& a, hipStream_t st);
 void launch_sigmoid_f32(float* v, size_t n, hipStream_t st);
 void launch_export_mat(const float* in, int B, int k, int X, float* out, hipStream_t st);
 void launch_concat_f32(const float* a, int na, const float* b, int nb, int rows, float* out, hipStream_t st);

@@ -54,7 +54,7 @@ template <class Ws> void free_all(Ws& ws) {
 }
 
 // kernels iwae_enable_timing brackets with HIP events (on the stream each is launched on); names: iwae_kernel_time
-enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_IMPUTE, T_POSTERIOR, T_COUNT };
+enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_IMPUTE, T_POSTERIOR, T_MASKED_OUT, T_COUNT };
 
 // What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
 // images and samples in chunks and needs log_w only.
@@ -64,6 +64,7 @@ struct FwdCall {
     int k_total = 0, s_off = 0;       // k_total > 0: the call holds samples [s_off, s_off + k) of k_total per image and draws the unchunked call's Philox rows
     bool log_w_only = false;          // forward-only call: no second (DReG) density per sample (round 5: ~14 % of the sampling pass); the log-mean-exp alone when no tensor is wanted
     bool no_ksplit = false;           // float32: no K split of few-row products (an image's result must not depend on how many images share the launch)
+    const uint8_t* mask = nullptr;    // the masked float32 step (iwae_*_masked): the caller's [B, x_dim] mask, host or device, non-zero = observed; null: every pixel observed
 };
 
 // Every switch and tuning value iwae_set_option writes (defaults: the measured best).  plan_step reads the switches that choose kernels and streams; the
@@ -144,6 +145,10 @@ struct StepOptions {
     int grid_chunk = 0;                       // iwae_grid_posterior: grid points per chunk (option grid_chunk; 0 = GRID_CHUNK_DEFAULT)
     int ais_t_chunk = 0;                      // iwae_ais: transitions per launch of ais_chain_kernel (option ais_t_chunk; 0 = AIS_T_CHUNK_DEFAULT)
     int local_t_chunk = 0;                    // iwae_local_posterior: passes per launch of local_q_kernel (option local_t_chunk; 0 = LOCAL_T_CHUNK_DEFAULT)
+    bool allow_masked_out_fused = true;       // masked float32 step: the output layer + masked likelihood as masked_out_f32_kernel where its predicate holds (option no_masked_out_fused)
+    int masked_out_min_rows = 25600;          // ... from this many data rows on (option masked_out_min_rows; 1: wherever the predicate holds).  Measured at 784 / 200 / 100, k = 50,
+                                              // masked step / unmasked step, general | fast: 8 200 rows 1.006 | 1.178, 16 400 1.140 | 1.254, 25 600 1.156 | 1.128, 40 000 1.179 | 1.172,
+                                              // 51 200 1.184 | 1.182, 102 400 1.247 | 1.144 (profiles/masked_step_time.txt): from 25 600 rows on the kernel never loses
     int impute_rows = 0;                      // iwae_impute: rows (images x draws, whole images) per launch of impute_rows_kernel (option impute_rows; 0 = IMPUTE_ROWS_DEFAULT)
 };
 
@@ -197,7 +202,8 @@ struct StepPlan {
 // backward_f32 and f32_dw read it and decide nothing themselves.  Every float32 forward writes m->f32_plan anew (fwd_was_f32 says which of the
 // two plans is the valid one); the backward half is valid only from a training forward to the backward_f32 of that same step.
 enum F32DecFwd { F32_DEC_GEMMS = 0, F32_DEC_ONE_LAUNCH };                    // the decoder forward: three GEMM launches | dec_fwd_f32_kernel
-enum F32PxFrom { F32_PX_BERN_PASS = 0, F32_PX_GEMM_EPILOGUE, F32_PX_DEC_KERNEL };      // log p(x|z): bern_f32_kernel over the stored logits | the output layer's GEMM epilogue (px_parts partial sums per row) | dec_fwd_f32_kernel (whole)
+enum F32PxFrom { F32_PX_BERN_PASS = 0, F32_PX_GEMM_EPILOGUE, F32_PX_DEC_KERNEL, F32_PX_MASKED_PASS, F32_PX_MASKED_OUT };      // log p(x|z): bern_f32_kernel over the stored logits | the output layer's GEMM epilogue (px_parts partial sums per row) | dec_fwd_f32_kernel (whole)
+// (a masked call, F32Plan::mask: masked_bern_f32_kernel over the stored logits [+ masked_s_f32_kernel] | masked_out_f32_kernel in place of the output layer's GEMM)
 // the host enqueue order of the decoder's three weight gradients among its dX products (backward_f32)
 enum F32DwOrder {
     F32_DW_ONE_STREAM = 0,      // each in front of its layer's dX product, on the main stream
@@ -206,7 +212,8 @@ enum F32DwOrder {
     F32_DW_BEHIND_DX            // ... all three behind the whole dX chain, first layer first (option f32_dw_last)
 };
 struct F32Plan {
-    const float* x = nullptr;   // device x [B][X] of the call (stage_input): the backward pass reads it again
+    const float* x = nullptr;   // device x [B][X] of the call (stage_input): the backward pass reads it again.  A masked call: xin = m ? x : 0
+    const uint8_t* mask = nullptr;      // device mask [B][X] of a masked call (iwae_*_masked), else null
     // ---- forward
     F32DecFwd dec_fwd = F32_DEC_GEMMS;
     F32PxFrom px_from = F32_PX_BERN_PASS;
@@ -285,7 +292,7 @@ struct iwae_model {
     int64_t adam_t = 0;
     // float32 mode (iwae_config.precision / iwae_set_eval_precision): row-major float32 activations, GEMMs on v_mfma_f32_16x16x4_f32
     struct F32Block { DevBuf h1, h2, dhead, d2, d1, dx; };
-    struct F32State { F32Block enc1, enc2, dec2, prior; DevBuf z[2], g1, g2, logits, d2, d1, slab, bpart, xcat, kslab; } f32;
+    struct F32State { F32Block enc1, enc2, dec2, prior; DevBuf z[2], g1, g2, logits, d2, d1, slab, bpart, xcat, kslab, xmask, mask, xcode; } f32;
     // float32 weight gradients of a step keep their row-split slabs (each in its own region of f32.slab) and are summed by ONE launch at the end of
     // backward_f32 (reduce_slabs_multi_f32_kernel): jobs queued by f32_dw, slab offsets in floats (the buffer may still grow while they queue)
     struct F32Pending { size_t off; size_t stride; size_t n; float* out; int nsplit; int seg; };

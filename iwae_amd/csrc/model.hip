@@ -75,7 +75,8 @@ static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgra
                                                  "ais_chain",                            // (iwae_ais: every launch of ais_chain_kernel while timing is enabled)
                                                  "local_q",                              // (iwae_local_posterior: likewise local_q_kernel)
                                                  "impute",                               // (iwae_impute: likewise both passes of impute_rows_kernel)
-                                                 "posterior"};                           // (iwae_posterior: likewise its moments and merge launches)
+                                                 "posterior",                            // (iwae_posterior: likewise its moments and merge launches)
+                                                 "masked_out"};                          // (the masked float32 step: likewise masked_out_f32_kernel)
 
 namespace {      // (closed and reopened around each helper that model.h declares for step_f32.hip; what is added in between stays internal)
 
@@ -1991,6 +1992,8 @@ int iwae_set_option(iwae_handle m, const char* name, int64_t value) {
     else if (n == "grid_chunk") m->opt.grid_chunk = iv > 0 ? std::max(16, iv) : 0;      // iwae_grid_posterior: grid points per chunk (0: the default)
     else if (n == "ais_t_chunk") m->opt.ais_t_chunk = iv > 0 ? iv : 0;                 // iwae_ais: transitions per launch (0: the default)
     else if (n == "local_t_chunk") m->opt.local_t_chunk = iv > 0 ? iv : 0;             // iwae_local_posterior: passes per launch (0: the default)
+    else if (n == "no_masked_out_fused") m->opt.allow_masked_out_fused = !on;          // masked float32 step: always the general route (logits to memory, masked_bern_f32_kernel / masked_s_f32_kernel)
+    else if (n == "masked_out_min_rows") m->opt.masked_out_min_rows = std::max(1, iv); // ... masked_out_f32_kernel from this many data rows on (1: wherever masked_out_f32_ok holds)
     else if (n == "impute_rows") m->opt.impute_rows = iv > 0 ? iv : 0;                 // iwae_impute: rows per launch, whole images (0: the default)
     else if (n == "eval_rows") m->opt.eval_rows = iv > 0 ? std::max(64, iv) : 0;       // data rows per evaluator launch
     else if (n == "no_bern_pipe") m->opt.allow_bern_pipe = !on;           // the Bernoulli forward on dense_kernel<EPI_BERN>
@@ -2067,6 +2070,74 @@ int iwae_train_step(iwae_handle m, const float* x, int32_t B, int32_t k, float b
         CHK(adam_impl(m, lr, 1.0f));
     } else {
         CHK(backward_impl(m, objective, END_UPDATE, lr));   // Adam fused into the gradient reduction
+    }
+    CHK(fetch_outputs(m, scalars, nullptr));
+    m->noise_step += 1;
+    return IWAE_OK;
+}
+
+// ---- the masked float32 step: the unmasked entry points' float32 branches with FwdCall::mask set
+namespace {
+// what a masked call takes; refused before anything of the handle changes
+int masked_scope(iwae_model* m, const char* who, const float* x, int B, int k, const iwae_tensors* want) {
+    const std::string w(who);
+    if (m->cfg.precision != IWAE_PREC_FP32) return fail(IWAE_ERR_ARG, w + ": the masked step needs a handle created with precision = IWAE_PREC_FP32");
+    if (m->cfg.n_layers != 1 || m->C > 0 || m->has_prior) return fail(IWAE_ERR_ARG, w + ": the masked step takes the 1-layer unconditional model only");
+    if (m->comm_main) return fail(IWAE_ERR_ARG, w + ": the masked step is single-device (the handle has communicators)");
+    if (want && want->logits) return fail(IWAE_ERR_ARG, w + ": the masked step hands out no logits");
+    if (!x || B <= 0 || k <= 0) return fail(IWAE_ERR_ARG, w + ": need x, B > 0, k > 0");
+    if ((int64_t)B * k > (int64_t)1 << 30) return fail(IWAE_ERR_ARG, w + ": B*k too large");
+    return IWAE_OK;
+}
+}  // namespace
+
+int iwae_forward_masked(iwae_handle m, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta, const float* eps, iwae_scalars* scalars,
+                        const iwae_tensors* want) {
+    if (!m) return fail(IWAE_ERR_ARG, "null handle");
+    if (!mask) return iwae_forward(m, x, B, k, beta, eps, scalars, want);
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CHK(masked_scope(m, "forward_masked", x, B, k, want));
+    FwdCall call{m->batch_offset};
+    call.mask = mask;
+    CHK(forward_f32(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want, call));
+    CHK(fetch_outputs(m, scalars, want));
+    m->noise_step += 1;
+    return IWAE_OK;
+}
+
+int iwae_forward_backward_masked(iwae_handle m, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta, int32_t objective, const float* eps,
+                                 iwae_scalars* scalars, const iwae_tensors* want) {
+    if (!m) return fail(IWAE_ERR_ARG, "null handle");
+    if (!mask) return iwae_forward_backward(m, x, B, k, beta, objective, eps, scalars, want);
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CHK(masked_scope(m, "forward_backward_masked", x, B, k, want));
+    CHK(check_objective(m, objective));
+    FwdCall call{m->batch_offset};
+    call.mask = mask;
+    CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, call));
+    CHK(backward_f32(m, objective, END_GRAD));
+    CHK(fetch_outputs(m, scalars, want));
+    m->noise_step += 1;
+    return IWAE_OK;
+}
+
+int iwae_train_step_masked(iwae_handle m, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta, float lr, int32_t objective,
+                           const float* eps, iwae_scalars* scalars, const iwae_tensors* want) {
+    if (!m) return fail(IWAE_ERR_ARG, "null handle");
+    if (!mask) return iwae_train_step(m, x, B, k, beta, lr, objective, eps, scalars, want);
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CHK(masked_scope(m, "train_step_masked", x, B, k, want));
+    CHK(check_objective(m, objective));
+    FwdCall call{m->batch_offset};
+    call.mask = mask;
+    CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, call));
+    if (want) {
+        CHK(backward_f32(m, objective, END_GRAD));
+        CHK(fetch_outputs(m, nullptr, want));      // tensors refer to the pre-update forward (src/iwae1.py:162)
+        CHK(join_side(m));
+        CHK(adam_impl(m, lr, 1.0f));
+    } else {
+        CHK(backward_f32(m, objective, END_UPDATE, lr));
     }
     CHK(fetch_outputs(m, scalars, nullptr));
     m->noise_step += 1;

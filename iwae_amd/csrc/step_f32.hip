@@ -150,7 +150,9 @@ int f32_block_bwd(iwae_model* m, int base, iwae_model::F32Block& w, const float*
 // Which kernels a float32 call launches and on which streams, decided once from the options, the layer tables, the call's shape and the staged
 // input xd.  As pure as plan_step: it touches no buffer, stream or event and fills p in place.  forward_f32 calls it behind stage_input:
 // dec_fwd_f32_ok also asks for the alignment of x, and a caller's device pointer is read in place.
-void plan_step_f32(const iwae_model* m, int B, int k, int objective, bool bwd, const FwdCall& call, const iwae_tensors* want, const float* xd, F32Plan& p) {
+// A masked call (maskd: the staged mask; xd is then xin = m ? x : 0): always the three GEMM launches for the tanh layers and a stored s; the
+// output layer is masked_out_f32_kernel where the options and its predicate allow (the fast route), else the logits GEMM + the masked passes.
+void plan_step_f32(const iwae_model* m, int B, int k, int objective, bool bwd, const FwdCall& call, const iwae_tensors* want, const float* xd, const uint8_t* maskd, F32Plan& p) {
     const StepOptions& o = m->opt;
     const bool two = m->cfg.n_layers == 2, want_logits = want && want->logits;
     const int M = B * k, X = m->X;
@@ -158,6 +160,7 @@ void plan_step_f32(const iwae_model* m, int B, int k, int objective, bool bwd, c
     const KerasLayer *d1 = &m->klayers[b_dec1], *d2 = d1 + 1, *d3 = d1 + 2;
     p = F32Plan();
     p.x = xd;
+    p.mask = maskd;
     p.want_dreg = !two && (objective == OBJ_DREG || (!bwd && !call.log_w_only));
     p.lme_only = !bwd && call.log_w_only && !want;
     // ---- the decoder forward
@@ -181,6 +184,16 @@ void plan_step_f32(const iwae_model* m, int B, int k, int objective, bool bwd, c
     p.px_from = fused_dec ? F32_PX_DEC_KERNEL : fuse_bern ? F32_PX_GEMM_EPILOGUE : F32_PX_BERN_PASS;
     if (fuse_bern) p.px_parts = 2 * ((X + 127) / 128);
     p.keeps_s = bwd && (fused_dec || fuse_bern);
+    if (maskd) {      // (never F32_DEC_ONE_LAUNCH / F32_PX_GEMM_EPILOGUE: neither kernel knows the mask; never dl_f32_kernel: it reads x at every pixel)
+        MaskedOutF32Args mo;
+        memset(&mo, 0, sizeof(mo));
+        mo.H = d3->Kin; mo.X = X; mo.k = k; mo.W3 = m->param + d3->offW; mo.b3 = m->param + d3->offb;
+        const bool fast = o.allow_masked_out_fused && M >= o.masked_out_min_rows && masked_out_f32_ok(mo);
+        p.dec_fwd = F32_DEC_GEMMS;
+        p.px_from = fast ? F32_PX_MASKED_OUT : F32_PX_MASKED_PASS;
+        p.px_parts = 1;
+        p.keeps_s = bwd;
+    }
     if (!bwd) return;
     // ---- the backward pass: where and in which order the decoder's three weight gradients are enqueued
     // (the conditional prior's block sits BEHIND the decoder in the flat parameters: its gradient is made on the main stream -- one stream for that model)
@@ -237,7 +250,14 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
     }
     const float* xd;
     CHK(stage_input(m, x, B, true, &xd));
-    plan_step_f32(m, B, k, objective, bwd, call, want, xd, m->f32_plan);
+    const uint8_t* maskd = nullptr;
+    if (call.mask) {      // the masked step: xin = m ? x : 0 is the call's x from here on (the encoder, and the backward pass's encoder weight gradient)
+        CHK(staged_in(m, call.mask, m->f32.mask, (size_t)B * m->X, &maskd));
+        CHK(ensure(m->f32.xmask, (size_t)B * m->X * 4, m->stream));
+        launch_impute_mask(xd, maskd, (long)B * m->X, ptr<float>(m->f32.xmask), m->stream);
+        xd = ptr<float>(m->f32.xmask);
+    }
+    plan_step_f32(m, B, k, objective, bwd, call, want, xd, maskd, m->f32_plan);
     const F32Plan& p = m->f32_plan;
     // ---- encoder on the images (conditional models: on concat(x, y), tasks/task05.py:113-118)
     const int b_enc1 = m->enc1[0].sub[0];
@@ -345,10 +365,35 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
         }
         ga.XB = xd; ga.bern_k = k; ga.bern_X = X; ga.part = ptr<float>(m->px_part); ga.part_stride = (size_t)Mp;
         launch_gemm_f32(m->opt.gemm_f32, ga, 1, st);
+    } else if (p.px_from == F32_PX_MASKED_OUT) {      // the masked step's fast route: no logits in memory, s stored once (training calls only)
+        CHK(ensure(m->f32.xcode, (size_t)B * X * 4, st));
+        launch_masked_code(xd, p.mask, (long)B * X, ptr<float>(m->f32.xcode), st);
+        MaskedOutF32Args mo;
+        memset(&mo, 0, sizeof(mo));
+        mo.G2 = ptr<float>(m->f32.g2); mo.ldg = H; mo.M = M; mo.H = H; mo.X = X;
+        mo.W3 = m->param + d3->offW; mo.b3 = m->param + d3->offb; mo.XC = ptr<float>(m->f32.xcode); mo.k = k;
+        mo.lpxz = lpxz; mo.zero = m->d_zero;
+        {   // (the K split f32_fwd would give the output layer's GEMM on the general route: the kernel's logits are that route's, bit for bit)
+            const int ns = nks ? 1 : gemm_f32_fewrows_split(m->opt.gemm_f32, M, X, H);
+            if (ns > 1) mo.kslabs = ((H + ns - 1) / ns + 15) / 16;
+        }
+        if (bwd) {      // (p.keeps_s)
+            CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
+            mo.S = ptr<float>(m->f32.logits); mo.ldS = X;
+        }
+        m->time_this = m->timing > 0;
+        {
+            ScopedTimer tm(m, T_MASKED_OUT, st);
+            launch_masked_out_f32(mo, st);
+        }
+        m->time_this = false;
     } else {
     CHK(ensure(m->f32.logits, (size_t)M * X * 4, st));
     CHK(f32_fwd(m, *d3, ptr<float>(m->f32.g2), H, M, ptr<float>(m->f32.logits), X, GEMM_EPI_NONE, nks));
-    launch_bern_f32(ptr<float>(m->f32.logits), X, xd, X, M, k, lpxz, st);
+    if (p.px_from == F32_PX_MASKED_PASS) {      // the masked step's general route
+        launch_masked_bern_f32(ptr<float>(m->f32.logits), X, xd, p.mask, X, M, k, lpxz, st);
+        if (bwd) launch_masked_s_f32(ptr<float>(m->f32.logits), X, xd, p.mask, X, M, k, st);      // (p.keeps_s: the logits become s in place)
+    } else launch_bern_f32(ptr<float>(m->f32.logits), X, xd, X, M, k, lpxz, st);
     }
     }      // (F32_DEC_GEMMS)
     if (want && want->logits) {      // reference [k,B,X] order

@@ -14,8 +14,11 @@ class IWAE(BaseIWAE):
         self.encoder = _Sub(self, 0, 16)     # encode_x_to_z1, encode_z1_to_z2   src/iwae2.py:55-56
         self.decoder = _Sub(self, 16, 30)    # decode_z2_to_z1, decode_z1_to_x   src/iwae2.py:77-87
 
-    def val_step(self, x, n_samples, beta, outputs=None):
-        return self.call(x, n_samples, beta, outputs=outputs)
+    def val_step(self, x, n_samples, beta, outputs=None, mask=None):
+        return self.call(x, n_samples, beta, outputs=outputs, mask=mask)
+
+    def _check_mask(self, mask):
+        raise ValueError("the masked step covers the 1-layer model only: the 2-layer encoder q(z2|z1) q(z1|x) has no masked form here")
 
     def sample(self, z2):
         """src/iwae2.py:184-196: z1 ~ p(z1|z2), probs = sigmoid(decoder(z1)), x_sample ~ Bernoulli(probs)."""

@@ -203,30 +203,48 @@ class NativeModel:
             setattr(t, name, bufs[name].ctypes.data)
         return t, bufs
 
+    def _mask_arg(self, who, mask, x):
+        """The [B, x_dim] uint8 mask of a masked call (non-zero = observed), kept alive by the caller for the call's duration."""
+        mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1, self.x_dim)
+        if x.ndim != 2 or mk.shape != x.shape:
+            raise ValueError("%s: mask must be [B, x_dim] = %s, got %s" % (who, x.shape, mk.shape))
+        return mk
+
     @staticmethod
     def _scalars_dict(s):
         return {n: float(getattr(s, n)) for n in _SCALAR_NAMES}
 
-    def forward(self, x, k, beta=1.0, eps=None, want=()):
+    def forward(self, x, k, beta=1.0, eps=None, want=(), mask=None):
+        """mask [B, x_dim], non-zero = observed (iwae_forward_masked: float32 handles, the 1-layer unconditional model); None: every pixel."""
         x = _f32(x)
         B = x.shape[0]
         keep, ep = self._eps_arg(eps, B, k)
         t, bufs = self._want(want, B, k)
         s = Scalars()
-        check(self.lib.iwae_forward(self.h, x.ctypes.data, B, int(k), float(beta), ep, C.byref(s),
-                                    C.byref(t) if t is not None else None))
+        if mask is not None:
+            mk = self._mask_arg("forward", mask, x)
+            check(self.lib.iwae_forward_masked(self.h, x.ctypes.data, mk.ctypes.data, B, int(k), float(beta), ep, C.byref(s),
+                                               C.byref(t) if t is not None else None))
+        else:
+            check(self.lib.iwae_forward(self.h, x.ctypes.data, B, int(k), float(beta), ep, C.byref(s),
+                                        C.byref(t) if t is not None else None))
         out = self._scalars_dict(s)
         out.update(bufs)
         return out
 
-    def forward_backward(self, x, k, beta=1.0, objective="iwae_elbo", eps=None, want=()):
+    def forward_backward(self, x, k, beta=1.0, objective="iwae_elbo", eps=None, want=(), mask=None):
         x = _f32(x)
         B = x.shape[0]
         keep, ep = self._eps_arg(eps, B, k)
         t, bufs = self._want(want, B, k)
         s = Scalars()
-        check(self.lib.iwae_forward_backward(self.h, x.ctypes.data, B, int(k), float(beta), OBJECTIVES[objective], ep,
-                                             C.byref(s), C.byref(t) if t is not None else None))
+        if mask is not None:      # (iwae_forward_backward_masked: as forward)
+            mk = self._mask_arg("forward_backward", mask, x)
+            check(self.lib.iwae_forward_backward_masked(self.h, x.ctypes.data, mk.ctypes.data, B, int(k), float(beta), OBJECTIVES[objective], ep,
+                                                        C.byref(s), C.byref(t) if t is not None else None))
+        else:
+            check(self.lib.iwae_forward_backward(self.h, x.ctypes.data, B, int(k), float(beta), OBJECTIVES[objective], ep,
+                                                 C.byref(s), C.byref(t) if t is not None else None))
         out = self._scalars_dict(s)
         out.update(bufs)
         return out
@@ -242,14 +260,19 @@ class NativeModel:
     def adam_step(self, lr, grad_scale=1.0):
         check(self.lib.iwae_adam_step(self.h, float(lr), float(grad_scale)))
 
-    def train_step(self, x, k, beta=1.0, lr=1e-3, objective="iwae_elbo", eps=None, want=(), scalars=True):
+    def train_step(self, x, k, beta=1.0, lr=1e-3, objective="iwae_elbo", eps=None, want=(), scalars=True, mask=None):
         x = _f32(x)
         B = x.shape[0]
         keep, ep = self._eps_arg(eps, B, k)
         t, bufs = self._want(want, B, k)
         s = Scalars()
-        check(self.lib.iwae_train_step(self.h, x.ctypes.data, B, int(k), float(beta), float(lr), OBJECTIVES[objective], ep,
-                                       C.byref(s) if scalars else None, C.byref(t) if t is not None else None))
+        if mask is not None:      # (iwae_train_step_masked: as forward)
+            mk = self._mask_arg("train_step", mask, x)
+            check(self.lib.iwae_train_step_masked(self.h, x.ctypes.data, mk.ctypes.data, B, int(k), float(beta), float(lr), OBJECTIVES[objective], ep,
+                                                  C.byref(s) if scalars else None, C.byref(t) if t is not None else None))
+        else:
+            check(self.lib.iwae_train_step(self.h, x.ctypes.data, B, int(k), float(beta), float(lr), OBJECTIVES[objective], ep,
+                                           C.byref(s) if scalars else None, C.byref(t) if t is not None else None))
         out = self._scalars_dict(s) if scalars else {}
         out.update(bufs)
         return out
@@ -258,6 +281,11 @@ class NativeModel:
         """Hot loop entry for benchmarks: x already resident in HBM, no host round trip."""
         check(self.lib.iwae_train_step(self.h, C.c_void_p(x_devptr), int(B), int(k), float(beta), float(lr), int(objective_id),
                                        None, None, None))
+
+    def train_step_masked_devptr(self, x_devptr, mask_devptr, B, k, beta, lr, objective_id):
+        """train_step_devptr with a resident uint8 mask [B, x_dim] (iwae_train_step_masked)."""
+        check(self.lib.iwae_train_step_masked(self.h, C.c_void_p(x_devptr), C.c_void_p(mask_devptr), int(B), int(k), float(beta), float(lr),
+                                              int(objective_id), None, None, None))
 
     def forward_backward_devptr(self, x_devptr, B, k, beta, objective_id):
         check(self.lib.iwae_forward_backward(self.h, C.c_void_p(x_devptr), int(B), int(k), float(beta), int(objective_id),
