@@ -111,21 +111,42 @@ def reference(nh, nl, xd, B, k, objective, beta=1.0):
     return masked_loss_grads(P, x, mask, eps, beta, objective)
 
 
-def sliced_oracle_grads(P, x, mask, eps, beta, objective):
+def masked_out_launches(m, call):
+    """(call(), launches of masked_out_f32_kernel while it ran): iwae_enable_timing(1) zeroes the counters, iwae_kernel_time(h, "masked_out")
+    reads the launch count -- the one witness of which route of the output layer a masked call took (plan_step_f32 falls back to the general
+    route silently where masked_out_f32_ok refuses).  Timing is switched off again; the events change no result."""
+    m.enable_timing(1)
+    try:
+        out = call()
+        launches = m.kernel_time("masked_out")[1]
+    finally:
+        m.enable_timing(0)
+    return out, launches
+
+
+def expected_on_fast_route(route, launches, rows=0):
+    """The witness against the route a test names: "fast..." > 0 launches, "general..." 0, "default" the fast route from 25 600 rows."""
+    fast = route.startswith("fast") or (route == "default" and rows >= 25600)
+    assert (launches > 0) == fast, "route %r at %d rows: %d launches of masked_out_f32_kernel" % (route, rows, launches)
+
+
+def sliced_oracle_grads(P, x, mask, eps, beta, objective, rnd=None):
     """The masked step through the committed NumPy oracle alone: image by image (B = 1), on the model whose encoder has lost the unobserved
     rows of its first kernel and whose decoder has lost the unobserved columns of W3 / b3; the gradients scattered back and averaged over
-    the images.  Returns ({objective value, lpxz [k, B]}, [(dW, db) ...])."""
+    the images.  rnd: the oracle's rounding hook (None: exact float64; _offinit_cases.f32_round: every operand rounded to float32).  Returns
+    ({objective value, lpxz / lpz / lqzx / al [k, B]}, [(dW, db) ...])."""
     B = x.shape[0]
     acc = [(np.zeros_like(W), np.zeros_like(b)) for W, b in P]
-    val, lpxz = 0.0, []
+    val, rows = 0.0, {key: [] for key in ("lpxz", "lpz", "lqzx", "al")}
     for b_ in range(B):
         obs = np.flatnonzero(mask[b_])
         Ps = [(np.array(W), np.array(b)) for W, b in P]
         Ps[0] = (P[0][0][obs, :], P[0][1])
         Ps[6] = (P[6][0][:, obs], P[6][1][obs])
-        res, g = O.loss_grads_1layer(Ps, x[b_:b_ + 1, obs], eps[:, b_:b_ + 1, :], beta, objective)
+        res, g = O.loss_grads_1layer(Ps, x[b_:b_ + 1, obs], eps[:, b_:b_ + 1, :], beta, objective, rnd=rnd)
         val += float(res["iwae_elbo" if objective == "dreg" else objective]) / B
-        lpxz.append(res["lpxz"][:, 0])
+        for key in rows:
+            rows[key].append(res[key][:, 0])
         for i, (dW, db) in enumerate(g):
             if i == 0:
                 acc[0][0][obs, :] += dW / B
@@ -136,4 +157,6 @@ def sliced_oracle_grads(P, x, mask, eps, beta, objective):
             else:
                 acc[i][0][:] += dW / B
                 acc[i][1][:] += db / B
-    return {"value": val, "lpxz": np.stack(lpxz, axis=1)}, acc
+    out = {key: np.stack(v, axis=1) for key, v in rows.items()}
+    out["value"] = val
+    return out, acc

@@ -7,6 +7,8 @@ densities F32_ROW_ATOL, scalars F32_SCALAR_REL (+ 2e-4), every gradient tensor F
 routes of the output layer against each other at the bounds of test_float32_mode_fused_output_layer_matches_exact_oracle (scalars 2e-6
 relative, gradient norm 1e-5).  Every (B, k) case runs on the general route (option no_masked_out_fused) and, where the shape lets it, on
 the fast route forced with masked_out_min_rows = 1.  One handle per (shape, route) for the whole module; every test resets what it reads.
+Which route a call took is read off the launch count of masked_out_f32_kernel (_witnessed: iwae_kernel_time "masked_out"): more than 0 on
+every "fast" call, 0 on every "general" one, and at the default options 0 below 25 600 rows.
 """
 import ctypes as C
 import functools
@@ -45,13 +47,20 @@ def _reset(m, P):
     m.set_step(0, 0)
 
 
+def _witnessed(m, route, rows, call):
+    """call() with the launch count of masked_out_f32_kernel held to what the route's name promises (MR.expected_on_fast_route)."""
+    out, launches = MR.masked_out_launches(m, call)
+    MR.expected_on_fast_route(route, launches, rows)
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def _run(shape, case, route, obj, beta=1.0):
     """(result dict, flat gradient) of iwae_forward_backward_masked on a case, once per (shape, case, route, objective)."""
     x, P, eps, mask = MR.case(*shape, *case)
     m = _model(shape, route)
     _reset(m, P)
-    r = m.forward_backward(x, case[1], beta, obj, eps=eps, want=ROWS, mask=mask)
+    r = _witnessed(m, route, case[0] * case[1], lambda: m.forward_backward(x, case[1], beta, obj, eps=eps, want=ROWS, mask=mask))
     return r, m.get_grads().copy()
 
 
@@ -89,10 +98,10 @@ def test_masked_step_matches_the_restatement(gpu, shape, route, case):
     m = _model(shape, route)
     _reset(m, P)
     obj = MR.OBJECTIVES[-1]
-    r0 = m.forward(x, case[1], 1.0, eps=eps, want=("lpxz",), mask=mask)
+    r0 = _witnessed(m, route, case[0] * case[1], lambda: m.forward(x, case[1], 1.0, eps=eps, want=("lpxz",), mask=mask))
     np.testing.assert_allclose(r0["lpxz"], r["lpxz"], rtol=1e-6, atol=1e-4)
     assert abs(r0["iwae_elbo"] - r["iwae_elbo"]) <= 1e-6 * abs(r["iwae_elbo"]) + 1e-5
-    m.train_step(x, case[1], 1.0, 1e-3, obj, eps=eps, mask=mask)
+    _witnessed(m, route, case[0] * case[1], lambda: m.train_step(x, case[1], 1.0, 1e-3, obj, eps=eps, mask=mask))
     g2 = m.get_grads().astype(np.float64)
     assert np.linalg.norm(g2 - flat) / np.linalg.norm(flat) < 1e-5
     ref, _, _ = O.adam_update(O.flatten_params(P), flat.astype(np.float64), 0.0, 0.0, 1, 1e-3)
@@ -108,7 +117,7 @@ def test_masked_vae_elbo_kl_at_beta(gpu, route):
 @pytest.mark.parametrize("case", MR.BIG_CASES, ids=lambda c: "B%d_k%d" % c)
 def test_masked_step_at_training_row_counts_default_options(gpu, case):
     """4 100, 10 000 and 25 600 rows at the default options (row-split weight gradients on the side stream, the route the defaults pick: the
-    general one at the first two, masked_out_f32_kernel at the third)."""
+    general one at the first two, masked_out_f32_kernel at the third: _run holds the launch count to 0, 0 and more than 0)."""
     _check_parity(MR.SHAPES[0], case, "default", "iwae_elbo")
 
 
@@ -134,9 +143,9 @@ def test_general_and_fast_route_agree(gpu, shape, case):
 
 
 # ---------------------------------------------------------------- 3. unobserved pixels are never read
-def _step_state(m, P, x, mask, eps, k, obj):
+def _step_state(m, P, x, mask, eps, k, obj, route):
     _reset(m, P)
-    r = m.train_step(x, k, 1.0, 1e-3, obj, eps=eps, want=("log_w", "lpxz"), mask=mask)
+    r = _witnessed(m, route, x.shape[0] * k, lambda: m.train_step(x, k, 1.0, 1e-3, obj, eps=eps, want=("log_w", "lpxz"), mask=mask))
     mo, ve, t = m.get_adam_state()
     return r, m.get_grads().copy(), m.get_params().copy(), mo, ve, t
 
@@ -149,7 +158,7 @@ def test_unobserved_pixels_are_never_read(gpu, shape, route, fill):
     assert (xf != x).any() or np.isnan(xf).any()
     m = _model(shape, route)
     for obj in ("iwae_elbo", "dreg"):
-        a, b = _step_state(m, P, x, mask, eps, 13, obj), _step_state(m, P, xf, mask, eps, 13, obj)
+        a, b = _step_state(m, P, x, mask, eps, 13, obj, route), _step_state(m, P, xf, mask, eps, 13, obj, route)
         for key in a[0]:
             np.testing.assert_array_equal(np.asarray(a[0][key]), np.asarray(b[0][key]), err_msg=key)
         for u, v in zip(a[1:5], b[1:5]):
@@ -185,7 +194,7 @@ def test_null_mask_is_the_unmasked_call_and_a_mask_of_ones_agrees_with_it(gpu, s
     np.testing.assert_array_equal(m.get_grads(), g_un)
     np.testing.assert_array_equal(m.get_params(), p_un)
     _reset(m, P)
-    r_one = m.train_step(x, 13, 1.0, 1e-3, "iwae_elbo", eps=eps, mask=np.ones(x.shape, np.uint8))
+    r_one = _witnessed(m, route, 65, lambda: m.train_step(x, 13, 1.0, 1e-3, "iwae_elbo", eps=eps, mask=np.ones(x.shape, np.uint8)))
     for key in SCALARS:
         assert abs(r_one[key] - r_un[key]) <= 2e-6 * abs(r_un[key]), (key, r_one[key], r_un[key])
     g1 = m.get_grads().astype(np.float64)
@@ -204,7 +213,7 @@ def test_log_w_gives_iwae_imputes_bound(gpu, shape, route):
     x, P, eps, mask = MR.case(*shape, B, k)
     m = _model(shape, route)
     _reset(m, P)
-    lw = m.forward(x, k, 1.0, eps=eps, want=("log_w",), mask=mask)["log_w"].astype(np.float64)
+    lw = _witnessed(m, route, B * k, lambda: m.forward(x, k, 1.0, eps=eps, want=("log_w",), mask=mask))["log_w"].astype(np.float64)
     mx = lw.max(axis=0)
     lpx = mx + np.log(np.mean(np.exp(lw - mx[None]), axis=0))
     got = m.impute(x, mask=mask, n_samples=k, noise=eps, outputs=("log_px",))["log_px"]
@@ -219,7 +228,7 @@ def test_three_masked_steps_on_device_noise_repeat_bitwise(gpu, shape, route):
     outs = []
     for _ in range(2):
         _reset(m, P)
-        rs = [m.train_step(x, 13, 1.0, 1e-3, "iwae_elbo", mask=mask)["iwae_elbo"] for _ in range(3)]
+        rs = _witnessed(m, route, 65, lambda: [m.train_step(x, 13, 1.0, 1e-3, "iwae_elbo", mask=mask)["iwae_elbo"] for _ in range(3)])
         outs.append((rs, m.get_params().copy(), m.get_adam_state(), m.get_grads().copy()))
     assert outs[0][0] == outs[1][0] and np.all(np.isfinite(outs[0][0])) and len(set(outs[0][0])) == 3
     np.testing.assert_array_equal(outs[0][1], outs[1][1])
