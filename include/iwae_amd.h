@@ -167,11 +167,16 @@ int iwae_adam_step(iwae_handle h, float lr, float grad_scale);      /* keras Ada
  * contract.  An image with nothing observed has log p(x_obs|z) = 0 exactly, log_w = log p(z) - log q(z|x).
  * iwae_scalars.mean_lpxz and want->lpxz / log_w / al / z / snis_z / lpz / lqzx are those of the masked weights; IWAE_OBJ_VAE_ELBO_KL
  * uses the masked mean_lpxz.  Noise (eps, the handle's step) and the step's semantics are the unmasked calls'.  Bitwise repeatable.
- * Models: the 1-layer unconditional model on a handle created with precision = IWAE_PREC_FP32, all five 1-layer objectives.
- * A bf16 handle, a 2-layer handle, cond_dim > 0, a handle with communicators (iwae_comm_init), want->logits != NULL (the fast route
- * never materialises logits), B <= 0, k <= 0 or x NULL: IWAE_ERR_ARG before any launch; the noise step, parameters, gradient
- * buffer and Adam state are unchanged.  Options no_masked_out_fused / masked_out_min_rows (tools/README.md) pick between the two
- * routes of the output layer. */
+ * Models: the 1-layer unconditional model, all five 1-layer objectives.  precision = IWAE_PREC_FP32: every width (DESIGN.md section 19;
+ * options no_masked_out_fused / masked_out_min_rows, tools/README.md, pick between the two routes of the output layer).
+ * precision = IWAE_PREC_BF16: handles whose hidden width pads to 64, 128 or 224 (n_hidden 33 .. 64, 97 .. 128,
+ * 193 .. 224: the widths with a stored-s backward pass), option out_recompute off; the mask rides in the bf16 pixel rows as a hole code
+ * (bits 0xFFFF) that the output layer's Bernoulli epilogue selects on, and the step is the unmasked bf16 step's plan under
+ * no_bern_pipe + no_out_in_block.  The two precisions compute DIFFERENT numbers -- bf16 operands with float32 accumulation against
+ * float32 throughout, as the unmasked calls do -- each bitwise repeatable; on one handle masked and unmasked calls may alternate freely.
+ * A bf16 handle of any other hidden width or with out_recompute set, a 2-layer handle, cond_dim > 0, a handle with communicators
+ * (iwae_comm_init), want->logits != NULL (no masked route materialises logits), B <= 0, k <= 0 or x NULL: IWAE_ERR_ARG before any
+ * launch; the noise step, parameters, gradient buffer and Adam state are unchanged. */
 int iwae_forward_masked(iwae_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta, const float* eps,
                         iwae_scalars* scalars, const iwae_tensors* want);
 int iwae_forward_backward_masked(iwae_handle h, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta,

@@ -111,8 +111,9 @@ class BaseIWAE:
         return res
 
     def _check_mask(self, mask):
-        """mask [B, x_dim], non-zero = observed (training on incomplete images, Mattei & Frellsen 2019): float32 handles of the 1-layer
-        unconditional model; None: every pixel observed (the reference's call)."""
+        """mask [B, x_dim], non-zero = observed (training on incomplete images, Mattei & Frellsen 2019): the 1-layer unconditional model, on
+        float32 handles of every width and on bf16 handles whose hidden width pads to 64, 128 or 224 (hidden 33 .. 64, 97 .. 128, 193 .. 224;
+        the library refuses the others); None: every pixel observed (the reference's call)."""
 
     def call(self, x, n_samples, beta=1.0, outputs=None, eps=None, mask=None):
         if mask is not None:

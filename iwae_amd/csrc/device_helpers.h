@@ -31,6 +31,14 @@ __device__ __forceinline__ float bf_at(const uint4& u, int j) {
     const uint32_t w = (j < 2) ? u.x : (j < 4) ? u.y : (j < 6) ? u.z : u.w;
     return (j & 1) ? bfhi(w) : bflo(w);
 }
+// the bits of that bf16 (the masked bf16 step compares them with the hole code, never the value)
+__device__ __forceinline__ uint32_t bf_bits_at(const uint4& u, int j) {
+    const uint32_t w = (j < 2) ? u.x : (j < 4) ? u.y : (j < 6) ? u.z : u.w;
+    return (j & 1) ? (w >> 16) : (w & 0xffffu);
+}
+// The code of an unobserved pixel in the bf16 pixel rows of a masked call (masked_code_bf16_kernel writes it, bern8<.., HOLES> compares against it):
+// all ones, a NaN no arithmetic produces -- the float32 step's MO_HOLE at bf16 width (DESIGN.md sections 19, 20)
+constexpr uint32_t BF16_HOLE = 0xFFFFu;
 __device__ __forceinline__ f32x4 mfma16(const uint4& a, const uint4& b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }

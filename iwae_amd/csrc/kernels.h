@@ -119,7 +119,9 @@ struct DenseArgs {
     uint16_t* G2W; int g2w_feat;
     int dbg;                          // DIAG builds only (option fake_s): 32 = the Bernoulli epilogue does not store s
 };
-void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done = nullptr);
+// holes (EPI_BERN of a masked call, pipe = 0, a hidden width with out_bwd_has_s_mode): a.XB carries launch_masked_code_bf16's hole codes and the
+// epilogue selects those pixels out (dense_kernel<EPI_BERN, .., HOLES>)
+void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done = nullptr, bool holes = false);
 bool bern_pipe_ok(const DenseArgs& a);  // shapes bern_pipe_kernel covers (launch_dense falls back to dense_kernel<EPI_BERN> otherwise)
 bool bern_lse_ok(const DenseArgs& a);   // ... and can take lse_kernel's work for its rows (DenseArgs.lse_on)
 
@@ -409,6 +411,8 @@ void launch_dl_f32(float* logits, size_t ld, const float* x, int X, int M, int k
 void launch_masked_bern_f32(const float* logits, size_t ld, const float* x, const uint8_t* mask, int X, int M, int k, float* lpxz, hipStream_t st);      // log p(x_obs|z) per row
 void launch_masked_s_f32(float* logits, size_t ld, const float* x, const uint8_t* mask, int X, int M, int k, hipStream_t st);      // in place: s = m ? x - sigmoid(l) : 0
 void launch_masked_code(const float* x, const uint8_t* mask, long n, float* xc, hipStream_t st);      // xc = m ? x : the hole code masked_out_f32_kernel compares against
+// the masked bf16 step: XC = bf16 P-layout rows [Bp][Xp] of m ? bf16(x) : BF16_HOLE (pad pixels and pad rows 0), what dense_kernel<EPI_BERN, .., HOLES> reads as XB
+void launch_masked_code_bf16(const float* x, const uint8_t* mask, int B, int X, int Xp, int Bp, uint16_t* XC, hipStream_t st);
 // masked_out_f32_kernel: the output layer g2 W3 + b3 with the masked likelihood [+ s] in its epilogue, rows stationary; no logits in memory
 struct MaskedOutF32Args {
     const float* G2; int ldg;              // the second tanh layer's activations [M][ldg]

@@ -28,18 +28,24 @@ namespace iwae {
 //   x*l - softplus(l) = (x - 1/2)*l - |l|/2 - ln2*log2(1+e),   sigmoid(l) - 1/2 = copysign(1/(1+e) - 1/2, l),
 // and sum_j log2(1+e_j) = log2(prod_j (1+e_j)): the factors lie in (1,2], so 8 logits cost seven multiplies and ONE
 // v_log instead of eight quarter-rate v_log.  MASKED: pixels >= Xdim (pads, l = 0 exactly) contribute nothing.
+// HOLES (a masked call): x carries the hole code of unobserved pixels; a pixel is live iff it is inside Xdim and its
+// bits are not BF16_HOLE, and a pixel that is not live contributes exactly nothing (a row with no live pixel sums to 0.0).  A live pixel
+// runs the instructions of the HOLES = false instantiation on the same operands.
 // Measured (phase stamps, ablations): ~80 issue cycles per logit with s kept, transcendentals at 16 each -- this
 // epilogue, not the MFMAs, the LDS stream or the stores, is what the Bernoulli kernel's time is made of.
 // ---------------------------------------------------------------------------------
-template <bool MASKED, bool KEEP>
+template <bool MASKED, bool KEEP, bool HOLES = false>
 __device__ __forceinline__ float bern8(const f32x4& a0, const f32x4& a1, const uint4& xb, int f0, int Xdim, uint4& sp) {
     float s_xl = 0.0f, s_al = 0.0f, prod = 1.0f, sv[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float l = (j < 4) ? a0[j & 3] : a1[j & 3];
-        const float xm = bf_at(xb, j) - 0.5f;
+        // HOLES (the masked step): a pixel whose bf16 bits are BF16_HOLE is unobserved.  It is SELECTED out like a pad
+        // pixel: its logit enters the sums as 0, its x - 1/2 as 0, its factor of prod as 1, its s as 0 -- no product with a mask value
+        const bool in = (!MASKED || (f0 + 16 * (j >> 2) + (j & 3) < Xdim)) && (!HOLES || bf_bits_at(xb, j) != BF16_HOLE);
+        const float lr = (j < 4) ? a0[j & 3] : a1[j & 3];
+        const float l = (HOLES && !in) ? 0.0f : lr;
+        const float xm = (HOLES && !in) ? 0.0f : bf_at(xb, j) - 0.5f;
         const float ope = 1.0f + exp2_raw(-fabsf(l * LOG2E_F));      // 1 + exp(-|l|)
-        const bool in = !MASKED || (f0 + 16 * (j >> 2) + (j & 3) < Xdim);
         prod *= in ? ope : 1.0f;
         s_al += fabsf(l);
         s_xl = fmaf(xm, l, s_xl);
@@ -72,7 +78,9 @@ __device__ __forceinline__ float bern8(const f32x4& a0, const f32x4& a1, const u
 // (first decoder layer of a training step).  The wave draws its fragments from the encoder head of the row's image and the
 // step's noise, stores them (they ARE the P-layout rows of z, which the weight gradient needs) and sums the row's prior and
 // posterior log-densities on the way -- the separate sampling pass over the rows (42 MB, 14 us) disappears.
-template <int EPI, int KTC, int G, int NWV = (G == 2 ? 4 : 8), bool ZIN = false>   // KTC > 0: compile-time k-step count (<= 8, single window), straight-line MFMA phase; NWV waves
+// HOLES (EPI_BERN only): the pixel rows XB carry the hole code of unobserved pixels (launch_masked_code_bf16) and the epilogue is bern8<.., HOLES>;
+// a template parameter, not a flag: the G = 1 shape sits at its 128 registers and the unmasked instantiations must not carry one more live value.
+template <int EPI, int KTC, int G, int NWV = (G == 2 ? 4 : 8), bool ZIN = false, bool HOLES = false>   // KTC > 0: compile-time k-step count (<= 8, single window), straight-line MFMA phase; NWV waves
 __global__ __launch_bounds__(64 * NWV, G == 1 ? 4 : ((EPI == EPI_BERN && KTC > 0) ? 2 : 1)) void dense_kernel(DenseArgs a) {   // 2nd = waves per SIMD (the run-time-K Bernoulli fallback -- hidden widths without an instantiation -- spilled 50 registers at two)
 #ifdef IWAE_DENSE_STAMPS
     unsigned long long ds_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ds_prev = 0;
@@ -366,7 +374,7 @@ __global__ __launch_bounds__(64 * NWV, G == 1 ? 4 : ((EPI == EPI_BERN && KTC > 0
                             t0 += (f32x4){bias_of(2 * p, 0), bias_of(2 * p, 1), bias_of(2 * p, 2), bias_of(2 * p, 3)};
                             t1 += (f32x4){bias_of(2 * p + 1, 0), bias_of(2 * p + 1, 1), bias_of(2 * p + 1, 2), bias_of(2 * p + 1, 3)};
                         }
-                        rowacc[g] += bern8<decltype(masked)::value, decltype(keep)::value>(t0, t1, pre[p][g], 64 * mg + 32 * p + 4 * q, a.Xdim, stP[p][g]);
+                        rowacc[g] += bern8<decltype(masked)::value, decltype(keep)::value, HOLES>(t0, t1, pre[p][g], 64 * mg + 32 * p + 4 * q, a.Xdim, stP[p][g]);
                     }
             };
             const bool full = 64 * mg + 64 <= a.Xdim;
@@ -3136,9 +3144,24 @@ bool bern_lse_ok(const DenseArgs& a) {
     return bern_pipe_ok(a) && a.pre_img1 && a.pipe >= 2 && (198 + a.k) / a.k + 1 <= 8 && a.k >= 13 && 200 % a.k == 0 &&
            (!a.zhead || (a.lse.term[1] == a.zlp && a.lse.term[2] == a.zlq && (!a.lse.lq_dreg || a.lse.lq_dreg == a.zlq_dreg))) && a.lse.n_px_part <= 1;
 }
-void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done) {
+// The output layer of a masked call (a.XB carries hole codes): dense_kernel<EPI_BERN, .., HOLES> in the shape launch_dense picks for the same
+// unmasked launch at pipe = 0 -- 8 waves x 16 rows at 7 k-steps from 8 192 rows on, 4 waves x 32 rows otherwise.  No run-time-K fallback.
+static void launch_bern_holes(const DenseArgs& a, dim3 grid, size_t lds, hipStream_t st, hipEvent_t done) {
+    if (a.KT == 7 && a.M >= 8192 && ((a.g1_mask >> EPI_BERN) & 1u)) {
+        LAUNCH_EV(done, (dense_kernel<EPI_BERN, 7, 1, 8, false, true>), grid, dim3(512), lds, st, a);
+        return;
+    }
+    switch (a.KT) {
+        case 7: LAUNCH_EV(done, (dense_kernel<EPI_BERN, 7, 2, 4, false, true>), grid, dim3(256), lds, st, a); break;
+        case 4: LAUNCH_EV(done, (dense_kernel<EPI_BERN, 4, 2, 4, false, true>), grid, dim3(256), lds, st, a); break;
+        case 2: LAUNCH_EV(done, (dense_kernel<EPI_BERN, 2, 2, 4, false, true>), grid, dim3(256), lds, st, a); break;
+        default: break;      // the host only asks where out_bwd_has_s_mode(KT) (masked_bf16_ok)
+    }
+}
+void launch_dense(int epi, const DenseArgs& a, hipStream_t st, hipEvent_t done, bool holes) {
     dim3 grid((a.M + 127) / 128, (a.MG + a.mg_per_block - 1) / a.mg_per_block);
     const size_t lds = 2 * DENSE_UNIT;
+    if (holes) { launch_bern_holes(a, grid, lds, st, done); return; }      // (EPI_BERN at pipe = 0: plan_step)
     if (epi == EPI_BERN && a.pipe && bern_pipe_ok(a)) {
         const size_t ldsb = 2 * (7 * 4096 + 1024) + (size_t)BERN_XIMG_MAX * a.ldXB * 4 + 128;
         if (a.pre_img1 && a.pipe >= 2 && (198 + a.k) / a.k + 1 <= 8) {       // 16-wave / 200-row shape (see QW)

@@ -6,12 +6,14 @@
 //   masked_code_kernel       fast route: xc = m ? x : HOLE, one float per pixel that carries value and mask (HOLE: a bit pattern, compared as bits)
 //   masked_out_f32_kernel    fast route: the output layer g2 W3 + b3 with the masked likelihood [+ s] in its epilogue, rows stationary; the
 //                            output-layer section of dec_fwd_f32_kernel (fp32_kernels.hip) with the mask as one more term of its `ok` predicate
+//   masked_code_bf16_kernel  the masked bf16 step: the same code at bf16 width, in the bf16 step's P-layout pixel rows
 // The two routes are the SAME float32 numbers: masked_out_f32_kernel forms each logit, each Bernoulli term, each row sum and each s with the
 // general route's operations in the general route's order (see the kernel), so which route a call takes shows in no result.
 // Every loop has a host-known trip count; workgroups never communicate; no atomics: results are bitwise repeatable.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <algorithm>
 #include "kernels.h"
 #include "device_helpers.h"
 
@@ -68,6 +70,38 @@ __global__ __launch_bounds__(256) void masked_code_kernel(const float* x, const 
         if (b == MO_HOLE) b = MO_HOLE - 1u;
     }
     xc[idx] = __uint_as_float(b);
+}
+
+// The masked bf16 step's pixel rows: prep_rows_kernel's block shape, chunks and P-layout, each pixel m ? bf16(x) :
+// BF16_HOLE.  The mask byte is tested first: x at an unobserved pixel is not loaded.  An observed x whose bf16 is exactly the hole's bits is
+// stored one bit off (still a NaN, still observed).  Pad pixels are 0 and pad rows are written too (0): the reader selects on bits alone.
+__global__ __launch_bounds__(256) void masked_code_bf16_kernel(const float* x, const uint8_t* mask, int B, int X, int Xp, int Bp, uint16_t* XC) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 64 + lane;
+    const int nchunk = Xp / 8;
+    if (b >= Bp) return;
+    for (int c = blockIdx.y * 4 + (threadIdx.x >> 6); c < nchunk; c += gridDim.y * 4) {
+        const int t = c >> 2, qq = c & 3;
+        uint32_t v[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int f0 = 32 * t + 16 * h + 4 * qq;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int f = f0 + i;
+                uint32_t bits = 0u;
+                if (b < B && f < X) {
+                    bits = BF16_HOLE;
+                    if (mask[(size_t)b * X + f] != 0) {
+                        bits = pack2(x[(size_t)b * X + f], 0.0f) & 0xffffu;
+                        if (bits == BF16_HOLE) bits = BF16_HOLE - 1u;
+                    }
+                }
+                v[4 * h + i] = bits;
+            }
+        }
+        *(uint4*)(XC + (size_t)b * Xp + 8 * c) = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -291,6 +325,10 @@ void launch_masked_s_f32(float* logits, size_t ld, const float* x, const uint8_t
 }
 void launch_masked_code(const float* x, const uint8_t* mask, long n, float* xc, hipStream_t st) {
     hipLaunchKernelGGL(masked_code_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, mask, n, xc);
+}
+void launch_masked_code_bf16(const float* x, const uint8_t* mask, int B, int X, int Xp, int Bp, uint16_t* XC, hipStream_t st) {
+    const int nchunk = Xp / 8;
+    hipLaunchKernelGGL(masked_code_bf16_kernel, dim3(Bp / 64, std::min(32, (nchunk + 3) / 4)), dim3(256), 0, st, x, mask, B, X, Xp, Bp, XC);
 }
 // widths and alignment masked_out_f32_kernel takes: the hidden width within one strip, pixel rows in whole 16-byte granules (W3's rows, b3 and
 // xc are read as float4 / by LDS-DMA)

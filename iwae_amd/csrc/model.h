@@ -64,7 +64,7 @@ struct FwdCall {
     int k_total = 0, s_off = 0;       // k_total > 0: the call holds samples [s_off, s_off + k) of k_total per image and draws the unchunked call's Philox rows
     bool log_w_only = false;          // forward-only call: no second (DReG) density per sample (round 5: ~14 % of the sampling pass); the log-mean-exp alone when no tensor is wanted
     bool no_ksplit = false;           // float32: no K split of few-row products (an image's result must not depend on how many images share the launch)
-    const uint8_t* mask = nullptr;    // the masked float32 step (iwae_*_masked): the caller's [B, x_dim] mask, host or device, non-zero = observed; null: every pixel observed
+    const uint8_t* mask = nullptr;    // the masked step of either precision (iwae_*_masked): the caller's [B, x_dim] mask, host or device, non-zero = observed; null: every pixel observed
 };
 
 // Every switch and tuning value iwae_set_option writes (defaults: the measured best).  plan_step reads the switches that choose kernels and streams; the
@@ -175,6 +175,7 @@ struct StepPlan {
     iwae::BlockFwdArgs dec_blk;       // ... of block_fwd_kernel on the decoder (DEC_BLOCK2, DEC_BLOCK_OUT)
     int px_parts = 1;           // > 1: log p(x|z) of this forward arrives in px_part as that many partial sums per row
     bool s_mode = false;        // the forward keeps s = x - sigmoid(l) in wdec1.dlP
+    bool holes = false;         // a masked call (FwdCall::mask): the output layer reads the hole-coded pixel rows xcP and selects unobserved pixels out (dense_kernel<EPI_BERN, .., HOLES>)
     bool early_wout = false;    // the output layer's weight gradient forks behind the decoder forward / lse_kernel, not behind out_bwd
     bool lse_fused = false;     // the decoder kernel does lse_kernel's work for its rows
     bool lse_dup = false;       // a second lse_kernel on the side stream makes the output layer's row weights
@@ -349,6 +350,8 @@ struct iwae_model {
     DevBuf dg2_part;            // small row counts: out_bwd_s_kernel's per-pixel-group partial sums
     DevBuf px_part;
     DevBuf xin, xP, epsbuf, zP[2];
+    // the masked bf16 step: the hole-coded pixel rows beside xP (which then holds xin = m ? x : 0), xin as float32, the caller's mask when it arrives on the host
+    struct MaskedWs { DevBuf xcP, xin, mask; } mk;
     DevBuf rows[6];            // lpxz, t1, t2, t3, t4, lq_dreg   (per data row)
     DevBuf logw, wn, gx, cf, per_b, dzdir;
     // lse_kernel's outputs once more, written by the copy of it that runs on the side stream (see forward_impl): the output layer's

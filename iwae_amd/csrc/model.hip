@@ -559,6 +559,11 @@ StepPlan plan_step(const iwae_model* m, int B, int k, int objective, bool bwd, c
     const int M = B * k, Mp = round_up(M, 128), X = m->X, Xp = m->Xp32;
     const Linear* d1 = m->dec1;
     const Linear& L = m->dec1[2];
+    // A masked call (a mask is staged: FwdCall::mask) takes the plan of the options no_bern_pipe + no_out_in_block: the output
+    // layer stays a dense_kernel<EPI_BERN> launch, the one kernel whose epilogue knows the hole code -- never bern_pipe_kernel (so no DEC_PIPE,
+    // lse_fused, g2w, Z_DEC_PROLOGUE), never block_fwd_kernel<.., OUT> (DEC_BLOCK_OUT).  Everything else follows from the predicates below.
+    p.holes = call.mask != nullptr;
+    const bool allow_bern_pipe = o.allow_bern_pipe && !p.holes, allow_out_in_block = o.allow_out_in_block && !p.holes;
     BlockFwdArgs bf;
     p.enc_takes_f32 = m->C == 0 && block_fwd_shape(m, m->enc1, B, bf);
     p.dec_rows = bwd && dec_rows_step(m, M, B);
@@ -566,7 +571,7 @@ StepPlan plan_step(const iwae_model* m, int B, int k, int objective, bool bwd, c
     // ---- the step's N(0,1) draws
     // (round 4: a forward-only call on many rows -- the k = 5000 evaluator on bf16 operands -- also takes its draws from eps_gen_kernel, so that the
     // decoder kernel makes z itself in its prologue instead of sample_kernel drawing inline and writing z out: option zin_eval, off by default -- measured slower)
-    p.zin_eval = !bwd && !two && m->C == 0 && o.allow_zin && o.allow_zin_eval && (int64_t)B * k >= 8192 && o.allow_dec_fused && o.allow_bern_pipe;
+    p.zin_eval = !bwd && !two && m->C == 0 && o.allow_zin && o.allow_zin_eval && (int64_t)B * k >= 8192 && o.allow_dec_fused && allow_bern_pipe;
     p.keep_eps = !host_eps && (bwd || two || p.zin_eval);
     // few data rows, training step, single-stream backward (dec_rows_step): the draws come from the multi-step buffers (one launch per EPSM_STEPS steps)
     p.eps_multi = p.keep_eps && bwd && !two && o.allow_eps_multi && call.k_total == 0 && p.dec_rows;
@@ -591,7 +596,7 @@ StepPlan plan_step(const iwae_model* m, int B, int k, int objective, bool bwd, c
     a.M = M; a.KT = L.KT; a.MG = L.MG; a.mg_per_block = L.MG; a.Np32 = L.Np32; a.g1_mask = o.dense_g1_mask;
     // few rows: the output layer runs inside block_fwd_kernel, behind the two tanh layers of the same 16-row tile (one launch for the
     // whole decoder; log p(x|z) per row comes out whole, not as per-group partial sums)
-    const bool out_in_block = o.allow_block_fused && o.allow_out_in_block && !fuse_z && M <= 4096 && !(want && want->logits) && !m->want_stamps &&
+    const bool out_in_block = o.allow_block_fused && allow_out_in_block && !fuse_z && M <= 4096 && !(want && want->logits) && !m->want_stamps &&
                               d1[1].Np32 == d1[0].Np32 && d1[1].Kp32 == d1[0].Np32 && L.Kp32 == d1[1].Np32 && L.KT == d1[1].KT && L.KT <= 8;
     // small row counts (the reference's default B = 20, k = 5): a handful of workgroups walking all 13 pixel groups
     // in turn is 40 us of latency -- one pixel group per block instead, log p(x|z) as per-group partial sums that
@@ -609,7 +614,7 @@ StepPlan plan_step(const iwae_model* m, int B, int k, int objective, bool bwd, c
         if (m->fake_s & 64) a.dbg |= 256;     //  behind both tanh layers,
         if (m->fake_s & 128) a.dbg |= 512;    //  behind the first)
     }
-    a.pipe = o.allow_bern_pipe ? 1 : 0;
+    a.pipe = allow_bern_pipe ? 1 : 0;
     if (a.pipe && o.bern_qw) {      // the 16-wave / 200-row shape is one workgroup per CU: only where its last round is nearly full
         const int nwg = (M + 199) / 200, ncu = std::max(1, m->num_cus);
         const int rounds = (nwg + ncu - 1) / ncu;
@@ -912,7 +917,19 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     if (eps) CHK(copy_in(m, m->epsbuf, eps, (size_t)M * (m->D[0] + (two ? m->D[1] : 0)) * 4));
     CHK(ensure(m->xP, (size_t)Bp * Xinp * 2, st));
     const float *xd, *xf_pending = nullptr;
-    CHK(stage_input(m, x, B, false, &xd));
+    CHK(stage_input(m, x, B, p.holes, &xd));
+    if (p.holes) {      // the masked step: the hole-coded pixel rows for the output layer; xin = m ? x : 0 is the call's x from here on (m->xP: the encoder, its backward and weight gradient)
+        if (!xd) return fail(IWAE_ERR_STATE, "forward: the masked step has no float32 rows of this batch");
+        const uint8_t* maskd;
+        CHK(staged_in(m, call.mask, m->mk.mask, (size_t)B * X, &maskd));
+        CHK(ensure(m->mk.xcP, (size_t)Bp * Xinp * 2, st));
+        CHK(ensure(m->mk.xin, (size_t)B * X * 4, st));
+        launch_masked_code_bf16(xd, maskd, B, X, Xinp, Bp, ptr<uint16_t>(m->mk.xcP), st);
+        launch_impute_mask(xd, maskd, (long)B * X, ptr<float>(m->mk.xin), st);
+        xd = ptr<float>(m->mk.xin);
+    }
+    if (p.holes && (p.dec_fwd == DEC_PIPE || p.dec_fwd == DEC_BLOCK_OUT || (bwd && !p.s_mode)))      // (masked_bf16_ok and plan_step rule all three out)
+        return fail(IWAE_ERR_STATE, "forward: the masked step was planned onto a kernel that knows no mask");
     if (xd) {      // (the resident set's rows are in m->xP already)
         if (p.enc_takes_f32) xf_pending = xd;      // the fused encoder kernel converts the rows itself
         else launch_prep_rows(xd, cond, B, X, m->C, Xinp, Bp, ptr<uint16_t>(m->xP), st);
@@ -1014,7 +1031,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         DenseArgs a = p.bern;      // the plan's shapes; the buffers follow
         a.X = ptr<uint16_t>(w.g2P);
         if (p.px_parts > 1) CHK(ensure(m->px_part, (size_t)p.px_parts * Mp * 4, st));
-        a.XB = ptr<uint16_t>(m->xP);
+        a.XB = ptr<uint16_t>(p.holes ? m->mk.xcP : m->xP);
         a.lpxz = p.px_parts > 1 ? ptr<float>(m->px_part) : lpxz;
         if (p.s_mode) {      // s = x - sigmoid(l) stays for the backward pass (out_bwd_s_kernel, output-layer weight gradient)
             CHK(ensure(m->wdec1.dlP, (size_t)Mp * Xp * 2, st));
@@ -1060,7 +1077,7 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
         // The side stream of an early output-layer weight gradient forks behind THIS kernel (event on its dispatch packet) where the row
         // weights come from it or from the side stream's own copy of lse_kernel
         const bool fork_here = p.lse_dup || (p.lse_fused && p.early_wout);
-        if (p.dec_fwd != DEC_BLOCK_OUT) { ScopedTimer tm(m, T_DEC_FWD); launch_dense(EPI_BERN, a, st, (fork_here && !m->time_this) ? m->ev_lse : nullptr); }
+        if (p.dec_fwd != DEC_BLOCK_OUT) { ScopedTimer tm(m, T_DEC_FWD); launch_dense(EPI_BERN, a, st, (fork_here && !m->time_this) ? m->ev_lse : nullptr, p.holes); }
         if (fork_here && m->time_this) HIPCHK(hipEventRecord(m->ev_lse, st));      // (a timed step: the timer's stop event sits behind the kernel)
         HIPCHK(hipGetLastError());
         // The NEXT step's noise (speculating step + 1 with the same batch shape; the tag is checked on use): drawn now, on the stream the plan
@@ -1746,6 +1763,7 @@ void iwae_destroy(iwae_handle m) {
     free_all(m->loc);
     free_all(m->imp);
     free_all(m->post);
+    free_all(m->mk);
     for (BlockWs* w : {&m->wenc1, &m->wenc2, &m->wdec2, &m->wprior}) free_all(*w);
     free_all(m->wdec1);
     free_all(m->f32);
@@ -2076,14 +2094,19 @@ int iwae_train_step(iwae_handle m, const float* x, int32_t B, int32_t k, float b
     return IWAE_OK;
 }
 
-// ---- the masked float32 step: the unmasked entry points' float32 branches with FwdCall::mask set
+// ---- the masked step (DESIGN.md sections 19, 20): the unmasked entry points' branches of either precision with FwdCall::mask set
 namespace {
+// A bf16 handle takes a mask where its backward pass starts from the stored s = m ? x - sigmoid(l) : 0: the kernels that recompute x - sigmoid(l)
+// from the pixel rows (out_bwd_kernel / out_bwd_pair_kernel) know no mask.  Padded hidden widths 64, 128 and 224, option out_recompute off.
+bool masked_bf16_ok(const iwae_model* m) { return m->opt.allow_s_mode && out_bwd_has_s_mode(m->dec1[2].KT); }
 // what a masked call takes; refused before anything of the handle changes
 int masked_scope(iwae_model* m, const char* who, const float* x, int B, int k, const iwae_tensors* want) {
     const std::string w(who);
-    if (m->cfg.precision != IWAE_PREC_FP32) return fail(IWAE_ERR_ARG, w + ": the masked step needs a handle created with precision = IWAE_PREC_FP32");
     if (m->cfg.n_layers != 1 || m->C > 0 || m->has_prior) return fail(IWAE_ERR_ARG, w + ": the masked step takes the 1-layer unconditional model only");
     if (m->comm_main) return fail(IWAE_ERR_ARG, w + ": the masked step is single-device (the handle has communicators)");
+    if (m->cfg.precision != IWAE_PREC_FP32 && !masked_bf16_ok(m))
+        return fail(IWAE_ERR_ARG, w + ": on a bf16 handle the masked step needs a hidden width that pads to 64, 128 or 224 and the stored-s backward pass (option out_recompute off); "
+                                      "other handles: precision = IWAE_PREC_FP32");
     if (want && want->logits) return fail(IWAE_ERR_ARG, w + ": the masked step hands out no logits");
     if (!x || B <= 0 || k <= 0) return fail(IWAE_ERR_ARG, w + ": need x, B > 0, k > 0");
     if ((int64_t)B * k > (int64_t)1 << 30) return fail(IWAE_ERR_ARG, w + ": B*k too large");
@@ -2099,7 +2122,8 @@ int iwae_forward_masked(iwae_handle m, const float* x, const uint8_t* mask, int3
     CHK(masked_scope(m, "forward_masked", x, B, k, want));
     FwdCall call{m->batch_offset};
     call.mask = mask;
-    CHK(forward_f32(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want, call));
+    if (m->cfg.precision == IWAE_PREC_FP32) CHK(forward_f32(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want, call));
+    else CHK(forward_impl(m, x, B, k, beta, eps, OBJ_IWAE_ELBO, false, want, call));
     CHK(fetch_outputs(m, scalars, want));
     m->noise_step += 1;
     return IWAE_OK;
@@ -2114,8 +2138,13 @@ int iwae_forward_backward_masked(iwae_handle m, const float* x, const uint8_t* m
     CHK(check_objective(m, objective));
     FwdCall call{m->batch_offset};
     call.mask = mask;
-    CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, call));
-    CHK(backward_f32(m, objective, END_GRAD));
+    if (m->cfg.precision == IWAE_PREC_FP32) {
+        CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, call));
+        CHK(backward_f32(m, objective, END_GRAD));
+    } else {
+        CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want, call));
+        CHK(backward_impl(m, objective, END_GRAD));
+    }
     CHK(fetch_outputs(m, scalars, want));
     m->noise_step += 1;
     return IWAE_OK;
@@ -2130,6 +2159,19 @@ int iwae_train_step_masked(iwae_handle m, const float* x, const uint8_t* mask, i
     CHK(check_objective(m, objective));
     FwdCall call{m->batch_offset};
     call.mask = mask;
+    if (m->cfg.precision != IWAE_PREC_FP32) {      // iwae_train_step's single-device bf16 branch
+        CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want, call));
+        if (want) {
+            CHK(backward_impl(m, objective, END_GRAD));
+            CHK(fetch_outputs(m, nullptr, want));   // tensors refer to the pre-update forward (src/iwae1.py:162)
+            CHK(adam_impl(m, lr, 1.0f));
+        } else {
+            CHK(backward_impl(m, objective, END_UPDATE, lr));   // Adam fused into the gradient reduction
+        }
+        CHK(fetch_outputs(m, scalars, nullptr));
+        m->noise_step += 1;
+        return IWAE_OK;
+    }
     CHK(forward_f32(m, x, B, k, beta, eps, objective, true, want, call));
     if (want) {
         CHK(backward_f32(m, objective, END_GRAD));

@@ -215,7 +215,9 @@ class NativeModel:
         return {n: float(getattr(s, n)) for n in _SCALAR_NAMES}
 
     def forward(self, x, k, beta=1.0, eps=None, want=(), mask=None):
-        """mask [B, x_dim], non-zero = observed (iwae_forward_masked: float32 handles, the 1-layer unconditional model); None: every pixel."""
+        """mask [B, x_dim], non-zero = observed (iwae_forward_masked: the 1-layer unconditional model; float32 handles of every width, bf16
+        handles whose hidden width pads to 64, 128 or 224 -- the two precisions compute different numbers: bf16 operands against float32);
+        None: every pixel."""
         x = _f32(x)
         B = x.shape[0]
         keep, ep = self._eps_arg(eps, B, k)

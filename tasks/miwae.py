@@ -1,9 +1,10 @@
 """Training on incomplete images (Mattei & Frellsen 2019, MIWAE): every training image gets one fixed missing-completely-at-random mask
-and a 1-layer model is trained in float32 on the (x, mask) batches with the masked train step (IWAE.train_step(..., mask=...)): the
+and a 1-layer model is trained (--precision fp32, the default, or bf16: the bf16 MFMA step) on the (x, mask) batches with the masked train step (IWAE.train_step(..., mask=...)): the
 encoder sees the observed pixels, the bound is that on log p(x_obs).  Beside it the same model trained on the same images with the holes
 filled by zeros and no mask -- what one can do without the masked step.  Reported for both, on held-out images masked at the same rate
 through IWAE.impute: the mean k-draw bound on log p(x_obs), and on the UNOBSERVED pixels the Bernoulli cross-entropy and the mean absolute
-error of the imputation.  Same flags as main.py, plus --images, --test-images, --steps, --rate, --draws, --mask-seed, --lr.
+error of the imputation.  Same flags as main.py, plus --images, --test-images, --steps, --rate, --draws, --mask-seed, --lr,
+--precision.
 
     python tasks/miwae.py --n_samples 5 --objective iwae_elbo --images 10000 --steps 2000 --rate 0.5
 """
@@ -28,7 +29,14 @@ def make_parser():
     p.add_argument("--draws", type=int, default=50, help="importance draws per image of the evaluation (1..65536)")
     p.add_argument("--mask-seed", type=int, default=0, help="seed of the masks")
     p.add_argument("--lr", type=float, default=1e-3, help="Adam's learning rate")
+    # (no attribute unless given: the namespace of a run without the flag is what it was before the flag existed; precision_of reads it)
+    p.add_argument("--precision", choices=("fp32", "bf16"), default=argparse.SUPPRESS,
+                   help="arithmetic of both models' train steps: fp32 (the default) or bf16 (bf16 operands, float32 accumulation)")
     return p
+
+
+def precision_of(args):
+    return getattr(args, "precision", "fp32")
 
 
 def load_images(n_train, n_test, seed=0):
@@ -50,10 +58,10 @@ def scores(x, p, hidden):
 
 
 def train(args, X, mask, masked, seed=123):
-    """A float32 1-layer model trained for args.steps steps on batches of X: masked, on (x, mask); else on the zero-filled images.
+    """A 1-layer model (--precision) trained for args.steps steps on batches of X: masked, on (x, mask); else on the zero-filled images.
     Returns (model, the objective's value at every step)."""
     seen = (mask != 0).astype(np.float64)      # the output bias: each pixel's mean over the images that show it (both models)
-    model = iwae1.IWAE(200, 100, device=int(str(args.gpu).split(",")[0]), precision="fp32", seed=seed,
+    model = iwae1.IWAE(200, 100, device=int(str(args.gpu).split(",")[0]), precision=precision_of(args), seed=seed,
                        output_bias=utils.bias_from_mean((X * seen).sum(0) / np.maximum(seen.sum(0), 1.0)))
     opt = Adam(args.lr, epsilon=1e-4)
     filled = np.where(mask != 0, X, np.float32(0.0)).astype(np.float32)
@@ -77,7 +85,7 @@ def main(argv=None):
     mask = utils.mcar_mask(X.shape, args.rate, seed=args.mask_seed)
     tmask = utils.mcar_mask(Xt.shape, args.rate, seed=args.mask_seed + 1)
     hidden = tmask == 0
-    print("images {0}  test images {1}  rate {2:.2f}  steps {3}  draws {4}".format(X.shape[0], Xt.shape[0], args.rate, args.steps, args.draws))
+    print("images {0}  test images {1}  rate {2:.2f}  steps {3}  draws {4}  precision {5}".format(X.shape[0], Xt.shape[0], args.rate, args.steps, args.draws, precision_of(args)))
     out = {}
     for name, masked in (("masked", True), ("zero_filled", False)):
         model, trace = train(args, X, mask, masked)
