@@ -573,6 +573,30 @@ int iwae_dataset_get_batch(iwae_handle h, int32_t start, int32_t B, float* x_out
  * iwae_dataset_get_labels returns the batch's one-hot rows [B, cond_dim] for inspection. */
 int iwae_dataset_set_labels(iwae_handle h, const uint8_t* labels, int32_t n);
 int iwae_dataset_get_labels(iwae_handle h, int32_t start, int32_t B, float* y_out);
+/* Incomplete images on the resident set (MIWAE, Mattei & Frellsen 2019; the 1-layer unconditional model): one fixed mask per image, kept
+ * resident bit-packed -- ceil(x_dim / 32) 32-bit words per image, pixel f = bit f & 31 of word f >> 5 (5.9 MB for 60 000 x 784).  The mask
+ * belongs to the IMAGE: row i is image i of the uploaded set, not position i of the epoch's order, and no epoch changes it.
+ * iwae_dataset_set_mask: mask [n, x_dim] bytes, host or device, non-zero = observed (the convention of iwae_impute_options.mask and
+ * iwae_*_masked); n must be the uploaded set's size.  mask == NULL drops the masks; a new iwae_dataset_upload drops them too.
+ * iwae_dataset_mcar_mask draws them on the device, missing completely at random: pixel f of image i is hidden iff
+ * (philox4x32_10(counter = (i, 0x4D41534B 'MASK', f >> 2, 0), key = (mask_seed lo, hi))[f & 3] >> 8) < thr, thr = floor(rate 2^24 + 0.5)
+ * computed once on the host in double (rate 0 hides nothing, rate 1 everything); keyed by the caller's mask_seed, not the handle's seed, so
+ * models with different weight seeds can share one incomplete set.  iwae_amd/utils.py::device_mcar_mask restates it bit for bit.
+ * iwae_dataset_get_mask returns the mask rows of a batch, [B, x_dim] bytes of 0 / 1 (host or device), rows order[start .. start + B), for
+ * inspection; iwae_dataset_get_batch stays what it is, the complete binarised rows.
+ * With masks set, iwae_train_step_dataset is exactly iwae_train_step_masked(h, x = what iwae_dataset_get_batch(start, B) returns, mask =
+ * what iwae_dataset_get_mask(start, B) returns, ..., eps = NULL, want = NULL) from the same handle state -- scalars, gradient, parameters,
+ * Adam moments, step count and noise step bitwise, in both precisions and on both routes of the float32 output layer -- with the batch
+ * fed by ONE input kernel (gather, binarisation and every masked form of the rows; timed name "masked_input") and no host traffic.  Its
+ * scope and refusals are iwae_train_step_masked's (IWAE_ERR_ARG before any launch, the handle unchanged): the 1-layer unconditional model,
+ * no communicators, on a bf16 handle a hidden width that pads to 64, 128 or 224 with option out_recompute off.  Without masks the call
+ * runs what it ran before masks existed, bit for bit.
+ * Errors of iwae_dataset_set_mask / iwae_dataset_mcar_mask: a 2-layer or conditional handle, or no uploaded set: IWAE_ERR_STATE (as
+ * iwae_dataset_set_labels); a wrong n, a rate outside [0, 1] or NaN: IWAE_ERR_ARG.  A bf16 handle of a width the masked step refuses may
+ * hold masks: the step is what refuses.  iwae_dataset_get_mask: a bad range IWAE_ERR_ARG, no masks IWAE_ERR_STATE. */
+int iwae_dataset_set_mask(iwae_handle h, const uint8_t* mask, int32_t n);
+int iwae_dataset_mcar_mask(iwae_handle h, double rate, uint64_t mask_seed);
+int iwae_dataset_get_mask(iwae_handle h, int32_t start, int32_t B, uint8_t* mask_out);
 int iwae_train_step_dataset(iwae_handle h, int32_t start, int32_t B, int32_t k, float beta, float lr, int32_t objective,
                             iwae_scalars* scalars);
 
@@ -581,7 +605,7 @@ int iwae_train_step_dataset(iwae_handle h, int32_t start, int32_t B, int32_t k, 
  * step (an event record costs a few us of stream bubble, so bench.py samples rather than timing every launch); 0 switches
  * it off.  name: "decoder_fwd" (whole decoder forward + log-likelihood), "out_bwd" (output-layer backward), "decoder_bwd" (the decoder's whole dX chain where it is one launch), "wgrad_out",
  * "dx_hidden", "dx_latent", "wgrad_hidden", "wgrad_latent" (the decoder's other backward kernels), "latent_bwd",
- * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel), "impute" (likewise both passes of iwae_impute's impute_rows_kernel, and pass (a) of iwae_posterior), "posterior" (likewise iwae_posterior's moments and merge launches), "masked_out" (likewise the masked float32 step's masked_out_f32_kernel).  A kernel a configuration does not launch reports 0 launches. */
+ * "encoder_fwd", "reduce_adam" (main-stream slab reduction + Adam), "ais_chain" (every launch of iwae_ais's chain kernel while timing is on), "local_q" (likewise iwae_local_posterior's local_q_kernel), "impute" (likewise both passes of iwae_impute's impute_rows_kernel, and pass (a) of iwae_posterior), "posterior" (likewise iwae_posterior's moments and merge launches), "masked_out" (likewise the masked float32 step's masked_out_f32_kernel), "masked_input" (likewise gather_binarize_masked_kernel, the input kernel of a masked iwae_train_step_dataset).  A kernel a configuration does not launch reports 0 launches. */
 int iwae_enable_timing(iwae_handle h, int32_t enable);
 int iwae_kernel_time(iwae_handle h, const char* name, double* avg_us, int64_t* launches);
 

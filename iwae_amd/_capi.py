@@ -154,6 +154,9 @@ SYMBOLS = {
     "iwae_dataset_get_batch": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "iwae_dataset_set_labels": (C.c_int, [_P, _P, C.c_int32]),
     "iwae_dataset_get_labels": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "iwae_dataset_set_mask": (C.c_int, [_P, _P, C.c_int32]),
+    "iwae_dataset_mcar_mask": (C.c_int, [_P, C.c_double, C.c_uint64]),
+    "iwae_dataset_get_mask": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "iwae_train_step_dataset": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.POINTER(Scalars)]),
     "iwae_set_condition": (C.c_int, [_P, _P, C.c_int32]),
     "iwae_enable_timing": (C.c_int, [_P, C.c_int32]),

@@ -155,12 +155,18 @@ class BaseIWAE:
         return out
 
     # ---- device-resident data pipeline (main.py:59-65,117-120 on the GPU) -----------------------
-    def set_dataset(self, X_gray):
-        """Keep the grey-level training set in HBM (uint8; float data in [0,1] is quantised to 1/255 steps)."""
+    def set_dataset(self, X_gray, mask=None):
+        """Keep the grey-level training set in HBM (uint8; float data in [0,1] is quantised to 1/255 steps).  mask [n, x_dim], non-zero =
+        observed: one fixed mask per image (training on incomplete images, as train_step's mask; the 1-layer unconditional model);
+        train_step_dataset then takes the masked step.  None: every pixel observed."""
+        if mask is not None:
+            self._check_mask(mask)
         X_gray = np.asarray(X_gray)
         if X_gray.dtype != np.uint8:
             X_gray = np.clip(np.rint(X_gray.reshape(X_gray.shape[0], -1) * 255.0), 0, 255).astype(np.uint8)
         self._net.dataset_upload(X_gray.reshape(X_gray.shape[0], -1))
+        if mask is not None:
+            self._net.dataset_set_mask(mask)
 
     def begin_epoch(self, epoch, order=None):
         """New dynamic binarisation (keyed by the epoch) and visiting order (tf.data shuffle) for this epoch."""

@@ -426,6 +426,23 @@ struct MaskedOutF32Args {
 };
 bool masked_out_f32_ok(const MaskedOutF32Args& a);      // reads H, X, k, W3, b3
 void launch_masked_out_f32(const MaskedOutF32Args& a, hipStream_t st);
+// ---- the resident per-image masks: bits [n][W], W = ceil(X / 32) words per image, pixel f = bit f & 31 of word f >> 5, set = observed
+inline int mask_words(int X) { return (X + 31) / 32; }
+void launch_mask_pack(const uint8_t* mask, int n, int X, uint32_t* bits, hipStream_t st);      // a device [n][X] byte mask (non-zero = observed) -> bits
+void launch_mask_mcar(int n, int X, uint32_t thr, uint64_t key, uint32_t* bits, hipStream_t st);      // pixel f of image i hidden iff (philox((i, 'MASK', f / 4, 0), key)[f % 4] >> 8) < thr
+// gather_binarize_masked_kernel: gather_binarize_kernel's batch (rows start.. of the order, the same binarised bits) under the images' masks, in
+// one launch every form of it a masked step reads; a null output is not written
+struct GatherMaskedArgs {
+    const uint8_t* data; const int32_t* order; const uint32_t* bits;      // the resident set [N][X], the epoch's order, the masks [N][W]
+    int start, B, X, Xp, Bp;
+    uint64_t seed; uint32_t epoch;
+    uint16_t* XP;                          // bf16 P-layout rows [B][Xp] of xin = m ? bit : 0 (the encoder's input)
+    uint16_t* XC;                          // bf16 P-layout rows [Bp][Xp] of m ? bf16(bit) : BF16_HOLE, pad pixels and pad rows 0 (launch_masked_code_bf16's)
+    float* xin;                            // float32 xin [B][X]
+    uint8_t* mask;                         // the batch's mask bytes [B][X], 0 / 1
+    float* xcode;                          // float32 m ? bit : the hole code [B][X] (launch_masked_code's)
+};
+void launch_gather_binarize_masked(const GatherMaskedArgs& a, hipStream_t st);
 void launch_sigmoid_f32(float* v, size_t n, hipStream_t st);
 void launch_export_mat(const float* in, int B, int k, int X, float* out, hipStream_t st);
 void launch_concat_f32(const float* a, int na, const float* b, int nb, int rows, float* out, hipStream_t st);

@@ -7,6 +7,9 @@
 //   masked_out_f32_kernel    fast route: the output layer g2 W3 + b3 with the masked likelihood [+ s] in its epilogue, rows stationary; the
 //                            output-layer section of dec_fwd_f32_kernel (fp32_kernels.hip) with the mask as one more term of its `ok` predicate
 //   masked_code_bf16_kernel  the masked bf16 step: the same code at bf16 width, in the bf16 step's P-layout pixel rows
+//   gather_binarize_masked_kernel   the masked step fed from the resident set: gather, binarisation and every masked form of
+//                            the batch's rows (xin as bf16 and float32, both hole codes, the mask bytes) in one launch, from the bit-packed
+//                            per-image masks mask_pack_kernel / mask_mcar_kernel leave
 // The two routes are the SAME float32 numbers: masked_out_f32_kernel forms each logit, each Bernoulli term, each row sum and each s with the
 // general route's operations in the general route's order (see the kernel), so which route a call takes shows in no result.
 // Every loop has a host-known trip count; workgroups never communicate; no atomics: results are bitwise repeatable.
@@ -101,6 +104,104 @@ __global__ __launch_bounds__(256) void masked_code_bf16_kernel(const float* x, c
             }
         }
         *(uint4*)(XC + (size_t)b * Xp + 8 * c) = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+    }
+}
+
+// ---- the resident per-image masks (iwae_dataset_set_mask / iwae_dataset_mcar_mask): one thread per (image, word)
+__global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* mask, int n, int X, int W, uint32_t* bits) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)n * W) return;
+    const int i = (int)(idx / W), w = (int)(idx - (size_t)i * W);
+    uint32_t v = 0u;
+    for (int j = 0; j < 32; ++j) {
+        const int f = 32 * w + j;
+        if (f < X && mask[(size_t)i * X + f] != 0) v |= 1u << j;
+    }
+    bits[idx] = v;
+}
+// missing completely at random, keyed like the binarisation (counter (image, 'MASK', pixel / 4, 0), the caller's key): integer work,
+// iwae_amd/utils.py::device_mcar_mask restates it bit for bit.  Bits past the last pixel stay 0.
+__global__ __launch_bounds__(256) void mask_mcar_kernel(int n, int X, int W, uint32_t thr, uint64_t key, uint32_t* bits) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)n * W) return;
+    const int i = (int)(idx / W), w = (int)(idx - (size_t)i * W);
+    uint32_t v = 0u;
+    for (int j = 0; j < 8; ++j) {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)i, 0x4D41534Bu /* 'MASK' */, (uint32_t)(8 * w + j), 0u, (uint32_t)key, (uint32_t)(key >> 32), r);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int f = 32 * w + 4 * j + e;
+            if (f < X && !((r[e] >> 8) < thr)) v |= 1u << (4 * j + e);
+        }
+    }
+    bits[idx] = v;
+}
+
+// The masked step's input from the resident set: gather_binarize_kernel's block shape, chunk walk, P-layout and Philox
+// call -- counter, key and threshold are its own, so a pixel's binarised bit is the bit iwae_dataset_get_batch returns -- under the image's
+// mask.  A chunk's 8 pixels lie in the 32-pixel group t = c >> 2: one word of the image's mask serves them.  Written, where the pointer is
+// not null: XP = bf16(m ? bit : 0) (prep_rows_kernel on impute_mask_kernel's rows), XC = m ? bf16(bit) : BF16_HOLE with pad pixels and pad rows
+// 0 (masked_code_bf16_kernel), and as [B][X] rows xin = m ? bit : 0 (impute_mask_kernel), the mask bytes and xcode = m ? bit : MO_HOLE
+// (masked_code_kernel).  The grey level of an unobserved pixel is loaded (the set is the library's own memory); the bit it binarises to reaches
+// an output only as the unchosen side of a select.  vec4 (X a multiple of 4: a group of 4 pixels is whole or absent): the [B][X] rows in 16-byte / 4-byte stores.
+__global__ __launch_bounds__(256) void gather_binarize_masked_kernel(GatherMaskedArgs a, int W, int vec4) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 64 + lane;
+    const int nchunk = a.Xp / 8;
+    if (b >= a.Bp) return;
+    const bool row = b < a.B;
+    const int img = row ? a.order[a.start + b] : 0;
+    for (int c = blockIdx.y * 4 + (threadIdx.x >> 6); c < nchunk; c += gridDim.y * 4) {
+        const int t = c >> 2, qq = c & 3;
+        const uint32_t word = (row && t < W) ? a.bits[(size_t)img * W + t] : 0u;
+        float v[8];
+        uint32_t hc[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int f0 = 32 * t + 16 * h + 4 * qq;
+            uint32_t r[4];
+            philox4x32_10((uint32_t)img, 0x42494E41u /* 'BINA' */, (uint32_t)(f0 >> 2), a.epoch, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), r);
+            float xi[4], xc[4];
+            uint32_t mb[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int f = f0 + i;
+                xi[i] = 0.0f; xc[i] = 0.0f; mb[i] = 0u;
+                uint32_t code = 0u;
+                if (row && f < a.X) {
+                    const bool obs = ((word >> (f & 31)) & 1u) != 0u;
+                    const uint32_t g = a.data[(size_t)img * a.X + f];
+                    const uint32_t thr = (uint32_t)(((uint64_t)g * 16777216ull * 2ull + 255ull) / 510ull);   // floor(g*2^24/255 + 0.5)
+                    const float bit = ((r[i] >> 8) < thr) ? 1.0f : 0.0f;
+                    xi[i] = obs ? bit : 0.0f;
+                    xc[i] = obs ? bit : __uint_as_float(MO_HOLE);
+                    mb[i] = obs ? 1u : 0u;
+                    code = obs ? (pack2(bit, 0.0f) & 0xffffu) : BF16_HOLE;
+                }
+                v[4 * h + i] = xi[i];
+                hc[4 * h + i] = code;
+            }
+            if (row && f0 < a.X) {
+                const size_t o = (size_t)b * a.X + f0;
+                if (vec4) {
+                    if (a.xin) *(float4*)(a.xin + o) = make_float4(xi[0], xi[1], xi[2], xi[3]);
+                    if (a.mask) *(uint32_t*)(a.mask + o) = mb[0] | (mb[1] << 8) | (mb[2] << 16) | (mb[3] << 24);
+                    if (a.xcode) *(float4*)(a.xcode + o) = make_float4(xc[0], xc[1], xc[2], xc[3]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        if (f0 + i < a.X) {
+                            if (a.xin) a.xin[o + i] = xi[i];
+                            if (a.mask) a.mask[o + i] = (uint8_t)mb[i];
+                            if (a.xcode) a.xcode[o + i] = xc[i];
+                        }
+                    }
+                }
+            }
+        }
+        if (a.XP && row) *(uint4*)(a.XP + (size_t)b * a.Xp + 8 * c) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+        if (a.XC) *(uint4*)(a.XC + (size_t)b * a.Xp + 8 * c) = make_uint4(hc[0] | (hc[1] << 16), hc[2] | (hc[3] << 16), hc[4] | (hc[5] << 16), hc[6] | (hc[7] << 16));
     }
 }
 
@@ -329,6 +430,18 @@ void launch_masked_code(const float* x, const uint8_t* mask, long n, float* xc, 
 void launch_masked_code_bf16(const float* x, const uint8_t* mask, int B, int X, int Xp, int Bp, uint16_t* XC, hipStream_t st) {
     const int nchunk = Xp / 8;
     hipLaunchKernelGGL(masked_code_bf16_kernel, dim3(Bp / 64, std::min(32, (nchunk + 3) / 4)), dim3(256), 0, st, x, mask, B, X, Xp, Bp, XC);
+}
+void launch_mask_pack(const uint8_t* mask, int n, int X, uint32_t* bits, hipStream_t st) {
+    const int W = mask_words(X);
+    hipLaunchKernelGGL(mask_pack_kernel, dim3((unsigned)(((size_t)n * W + 255) / 256)), dim3(256), 0, st, mask, n, X, W, bits);
+}
+void launch_mask_mcar(int n, int X, uint32_t thr, uint64_t key, uint32_t* bits, hipStream_t st) {
+    const int W = mask_words(X);
+    hipLaunchKernelGGL(mask_mcar_kernel, dim3((unsigned)(((size_t)n * W + 255) / 256)), dim3(256), 0, st, n, X, W, thr, key, bits);
+}
+void launch_gather_binarize_masked(const GatherMaskedArgs& a, hipStream_t st) {
+    const int nchunk = a.Xp / 8;
+    hipLaunchKernelGGL(gather_binarize_masked_kernel, dim3(a.Bp / 64, std::min(32, (nchunk + 3) / 4)), dim3(256), 0, st, a, mask_words(a.X), (a.X & 3) == 0 ? 1 : 0);
 }
 // widths and alignment masked_out_f32_kernel takes: the hidden width within one strip, pixel rows in whole 16-byte granules (W3's rows, b3 and
 // xc are read as float4 / by LDS-DMA)

@@ -54,7 +54,7 @@ template <class Ws> void free_all(Ws& ws) {
 }
 
 // kernels iwae_enable_timing brackets with HIP events (on the stream each is launched on); names: iwae_kernel_time
-enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_IMPUTE, T_POSTERIOR, T_MASKED_OUT, T_COUNT };
+enum TimedKernel { T_OUT_BWD = 0, T_DEC_FWD, T_WGRAD_OUT, T_DX_HID, T_DX_LAT, T_WGRAD_HID, T_WGRAD_LAT, T_LATENT_BWD, T_ENC_FWD, T_REDUCE, T_DEC_BWD, T_AR_ENC, T_AR_DEC, T_AIS_CHAIN, T_LOCAL_Q, T_IMPUTE, T_POSTERIOR, T_MASKED_OUT, T_MASKED_INPUT, T_COUNT };
 
 // What a forward pass is told by its caller beyond the ABI's arguments.  Ordinary calls: FwdCall{m->batch_offset}; iwae_eval_llh walks
 // images and samples in chunks and needs log_w only.
@@ -65,6 +65,17 @@ struct FwdCall {
     bool log_w_only = false;          // forward-only call: no second (DReG) density per sample (round 5: ~14 % of the sampling pass); the log-mean-exp alone when no tensor is wanted
     bool no_ksplit = false;           // float32: no K split of few-row products (an image's result must not depend on how many images share the launch)
     const uint8_t* mask = nullptr;    // the masked step of either precision (iwae_*_masked): the caller's [B, x_dim] mask, host or device, non-zero = observed; null: every pixel observed
+    bool mask_resident = false;       // ... or the masks of the resident set's images (iwae_train_step_dataset behind iwae_dataset_set_mask / _mcar_mask; `mask` is null then):
+                                      // stage_input writes every form of the batch the masked step reads in its one launch (MaskedStage)
+    bool masked() const { return mask != nullptr || mask_resident; }
+};
+// Where stage_input leaves a resident masked batch (FwdCall::mask_resident): the caller has sized the buffers its plan reads and leaves the rest null
+struct MaskedStage {
+    uint16_t* xP = nullptr;           // bf16 rows of xin = m ? x : 0 (m->xP)
+    uint16_t* xcP = nullptr;          // the hole-coded bf16 pixel rows (mk.xcP)
+    float* xin = nullptr;             // float32 xin [B][X] (f32.xmask)
+    uint8_t* mask = nullptr;          // the batch's mask bytes [B][X] (f32.mask)
+    float* xcode = nullptr;           // float32 hole-coded rows [B][X] (f32.xcode: the fused route of the output layer)
 };
 
 // Every switch and tuning value iwae_set_option writes (defaults: the measured best).  plan_step reads the switches that choose kernels and streams; the
@@ -364,6 +375,7 @@ struct iwae_model {
     // resident dataset (iwae_dataset_*): uint8 grey levels [N][X] + the epoch's visiting order
     DevBuf ds_data, ds_order;
     DevBuf ds_labels; bool ds_has_labels = false;   // class id per image of the resident set (iwae_dataset_set_labels; conditional models)
+    DevBuf ds_mask; bool ds_has_mask = false;       // one fixed mask per image of the resident set, bit-packed [ds_N][mask_words(X)] (iwae_dataset_set_mask / _mcar_mask): iwae_train_step_dataset takes the masked step
     int ds_N = 0;
     // N(0,1) draws of a step, fp32 [Mp][Dp] per latent layer, made by eps_gen_kernel and read by the sampling / decoder and
     // backward kernels.  A training step draws the NEXT step's noise during its forward pass on the side stream, idle then
@@ -440,7 +452,7 @@ int block_alloc(iwae_model* m, Linear* blk, BlockWs& w, int R, int Rp, bool bwd,
 int block_fwd(iwae_model* m, Linear* blk, BlockWs& w, const uint16_t* XP, int R, const float* xf = nullptr, int xdim = 0);
 // (the float32 step's share)
 int begin_forward(iwae_model* m, const float* x, int B, int k, float beta, const FwdCall& call, const float** cond);
-int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float** xd);
+int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float** xd, const MaskedStage* masked = nullptr);
 int draw_eps(iwae_model* m, int par, uint32_t step, int M, hipStream_t gs, int max_blocks = 0);
 iwae::EpsSrc eps_src(iwae_model* m, int layer);
 int build_descs(iwae_model* m);

@@ -76,7 +76,8 @@ static const char* const kTimedNames[T_COUNT] = {"out_bwd", "decoder_fwd", "wgra
                                                  "local_q",                              // (iwae_local_posterior: likewise local_q_kernel)
                                                  "impute",                               // (iwae_impute: likewise both passes of impute_rows_kernel)
                                                  "posterior",                            // (iwae_posterior: likewise its moments and merge launches)
-                                                 "masked_out"};                          // (the masked float32 step: likewise masked_out_f32_kernel)
+                                                 "masked_out",                           // (the masked float32 step: likewise masked_out_f32_kernel)
+                                                 "masked_input"};                        // (the masked step from the resident set: likewise gather_binarize_masked_kernel)
 
 namespace {      // (closed and reopened around each helper that model.h declares for step_f32.hip; what is added in between stays internal)
 
@@ -559,10 +560,10 @@ StepPlan plan_step(const iwae_model* m, int B, int k, int objective, bool bwd, c
     const int M = B * k, Mp = round_up(M, 128), X = m->X, Xp = m->Xp32;
     const Linear* d1 = m->dec1;
     const Linear& L = m->dec1[2];
-    // A masked call (a mask is staged: FwdCall::mask) takes the plan of the options no_bern_pipe + no_out_in_block: the output
+    // A masked call (a mask is staged, the caller's or the resident set's: FwdCall::masked(), DESIGN.md sections 20, 21) takes the plan of the options no_bern_pipe + no_out_in_block: the output
     // layer stays a dense_kernel<EPI_BERN> launch, the one kernel whose epilogue knows the hole code -- never bern_pipe_kernel (so no DEC_PIPE,
     // lse_fused, g2w, Z_DEC_PROLOGUE), never block_fwd_kernel<.., OUT> (DEC_BLOCK_OUT).  Everything else follows from the predicates below.
-    p.holes = call.mask != nullptr;
+    p.holes = call.masked();
     const bool allow_bern_pipe = o.allow_bern_pipe && !p.holes, allow_out_in_block = o.allow_out_in_block && !p.holes;
     BlockFwdArgs bf;
     p.enc_takes_f32 = m->C == 0 && block_fwd_shape(m, m->enc1, B, bf);
@@ -861,9 +862,24 @@ int begin_forward(iwae_model* m, const float* x, int B, int k, float beta, const
 // The batch on the device: rows ds_start.. of the resident set, gathered by the epoch's order and binarised on the fly (main.py:117-120) into the
 // bf16 rows m->xP -- and, keep_f32, into the float32 rows m->xin -- or the caller's x (host batches are staged in m->xin, device batches read in
 // place).  *xd: the float32 rows, null where none were kept.
-int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float** xd) {
+// masked (a resident masked batch, FwdCall::mask_resident): the same rows under the images' masks, in the one launch of
+// gather_binarize_masked_kernel every form of them the caller's plan reads (MaskedStage; *xd: its float32 xin, null where the caller kept none).
+int stage_input(iwae_model* m, const float* x, int B, bool keep_f32, const float** xd, const MaskedStage* masked) {
     *xd = x;
-    if (m->ds_start >= 0) {
+    if (masked) {
+        if (m->ds_start < 0 || !m->ds_has_mask) return fail(IWAE_ERR_STATE, "forward: a resident masked batch without a resident set and its masks");
+        GatherMaskedArgs g;
+        memset(&g, 0, sizeof(g));
+        g.data = ptr<uint8_t>(m->ds_data); g.order = ptr<int32_t>(m->ds_order); g.bits = ptr<uint32_t>(m->ds_mask);
+        g.start = m->ds_start; g.B = B; g.X = m->X; g.Xp = m->Xinp; g.Bp = m->Bp; g.seed = m->cfg.seed; g.epoch = m->ds_epoch;
+        g.XP = masked->xP; g.XC = masked->xcP; g.xin = masked->xin; g.mask = masked->mask; g.xcode = masked->xcode;
+        {
+            ScopedTimer tm(m, T_MASKED_INPUT);
+            launch_gather_binarize_masked(g, m->stream);
+        }
+        m->ds_start = -1;
+        *xd = masked->xin;
+    } else if (m->ds_start >= 0) {
         CHK(ensure(m->xP, (size_t)m->Bp * m->Xinp * 2, m->stream));
         if (keep_f32) CHK(ensure(m->xin, (size_t)B * m->X * 4, m->stream));
         float* xf = keep_f32 ? ptr<float>(m->xin) : nullptr;
@@ -917,8 +933,13 @@ int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const 
     if (eps) CHK(copy_in(m, m->epsbuf, eps, (size_t)M * (m->D[0] + (two ? m->D[1] : 0)) * 4));
     CHK(ensure(m->xP, (size_t)Bp * Xinp * 2, st));
     const float *xd, *xf_pending = nullptr;
-    CHK(stage_input(m, x, B, p.holes, &xd));
-    if (p.holes) {      // the masked step: the hole-coded pixel rows for the output layer; xin = m ? x : 0 is the call's x from here on (m->xP: the encoder, its backward and weight gradient)
+    if (call.mask_resident) {      // the masked step from the resident set: xin as bf16 in m->xP and the hole-coded pixel rows, one launch
+        CHK(ensure(m->mk.xcP, (size_t)Bp * Xinp * 2, st));
+        MaskedStage ms;
+        ms.xP = ptr<uint16_t>(m->xP); ms.xcP = ptr<uint16_t>(m->mk.xcP);
+        CHK(stage_input(m, x, B, false, &xd, &ms));      // (xd: null -- the rows are in m->xP already)
+    } else CHK(stage_input(m, x, B, p.holes, &xd));
+    if (p.holes && !call.mask_resident) {      // the masked step on the caller's mask: the hole-coded pixel rows for the output layer; xin = m ? x : 0 is the call's x from here on (m->xP: the encoder, its backward and weight gradient)
         if (!xd) return fail(IWAE_ERR_STATE, "forward: the masked step has no float32 rows of this batch");
         const uint8_t* maskd;
         CHK(staged_in(m, call.mask, m->mk.mask, (size_t)B * X, &maskd));
@@ -1752,7 +1773,7 @@ void iwae_destroy(iwae_handle m) {
     DevBuf* bufs[] = {&m->xin, &m->xP, &m->epsbuf, &m->zP[0], &m->zP[1], &m->rows[0], &m->rows[1],
                       &m->rows[2], &m->rows[3], &m->rows[4], &m->rows[5], &m->logw, &m->wn, &m->gx, &m->cf, &m->per_b, &m->logw2, &m->wn2, &m->gx2, &m->cf2, &m->per_b2,
                       &m->dzdir, &m->scratch, &m->ds_data, &m->ds_order, &m->dstamps, &m->px_part, &m->dg2_part, &m->cond, &m->condP, &m->epsc[0][0], &m->epsc[0][1], &m->epsc[1][0], &m->epsc[1][1], &m->epsc[2][0], &m->epsc[2][1], &m->eval_lme,
-                      &m->ds_labels, &m->epsm[0][0], &m->epsm[0][1], &m->epsm[1][0], &m->epsm[1][1], &m->stamps};
+                      &m->ds_labels, &m->ds_mask, &m->epsm[0][0], &m->epsm[0][1], &m->epsm[1][0], &m->epsm[1][1], &m->stamps};
     for (DevBuf* b : bufs) free_buf(*b);
     free_all(m->ev);
     free_all(m->grid);
@@ -2100,7 +2121,7 @@ namespace {
 // from the pixel rows (out_bwd_kernel / out_bwd_pair_kernel) know no mask.  Padded hidden widths 64, 128 and 224, option out_recompute off.
 bool masked_bf16_ok(const iwae_model* m) { return m->opt.allow_s_mode && out_bwd_has_s_mode(m->dec1[2].KT); }
 // what a masked call takes; refused before anything of the handle changes
-int masked_scope(iwae_model* m, const char* who, const float* x, int B, int k, const iwae_tensors* want) {
+int masked_scope(iwae_model* m, const char* who, const float* x, int B, int k, const iwae_tensors* want, bool resident = false) {
     const std::string w(who);
     if (m->cfg.n_layers != 1 || m->C > 0 || m->has_prior) return fail(IWAE_ERR_ARG, w + ": the masked step takes the 1-layer unconditional model only");
     if (m->comm_main) return fail(IWAE_ERR_ARG, w + ": the masked step is single-device (the handle has communicators)");
@@ -2108,10 +2129,12 @@ int masked_scope(iwae_model* m, const char* who, const float* x, int B, int k, c
         return fail(IWAE_ERR_ARG, w + ": on a bf16 handle the masked step needs a hidden width that pads to 64, 128 or 224 and the stored-s backward pass (option out_recompute off); "
                                       "other handles: precision = IWAE_PREC_FP32");
     if (want && want->logits) return fail(IWAE_ERR_ARG, w + ": the masked step hands out no logits");
-    if (!x || B <= 0 || k <= 0) return fail(IWAE_ERR_ARG, w + ": need x, B > 0, k > 0");
+    if ((!x && !resident) || B <= 0 || k <= 0) return fail(IWAE_ERR_ARG, w + ": need x, B > 0, k > 0");
     if ((int64_t)B * k > (int64_t)1 << 30) return fail(IWAE_ERR_ARG, w + ": B*k too large");
     return IWAE_OK;
 }
+int train_step_masked_call(iwae_model* m, const float* x, int B, int k, float beta, float lr, int objective, const float* eps, iwae_scalars* scalars,
+                           const iwae_tensors* want, const FwdCall& call);
 }  // namespace
 
 int iwae_forward_masked(iwae_handle m, const float* x, const uint8_t* mask, int32_t B, int32_t k, float beta, const float* eps, iwae_scalars* scalars,
@@ -2159,6 +2182,13 @@ int iwae_train_step_masked(iwae_handle m, const float* x, const uint8_t* mask, i
     CHK(check_objective(m, objective));
     FwdCall call{m->batch_offset};
     call.mask = mask;
+    return train_step_masked_call(m, x, B, k, beta, lr, objective, eps, scalars, want, call);
+}
+
+namespace {
+// the masked train step behind its checks: the caller's mask (iwae_train_step_masked) or the resident set's (iwae_train_step_dataset)
+int train_step_masked_call(iwae_model* m, const float* x, int B, int k, float beta, float lr, int objective, const float* eps, iwae_scalars* scalars,
+                           const iwae_tensors* want, const FwdCall& call) {
     if (m->cfg.precision != IWAE_PREC_FP32) {      // iwae_train_step's single-device bf16 branch
         CHK(forward_impl(m, x, B, k, beta, eps, objective, true, want, call));
         if (want) {
@@ -2185,6 +2215,7 @@ int iwae_train_step_masked(iwae_handle m, const float* x, const uint8_t* mask, i
     m->noise_step += 1;
     return IWAE_OK;
 }
+}  // namespace
 
 int iwae_comm_unique_id(void* id_out, size_t cap, size_t* id_bytes) {
     if (!id_out || !id_bytes || cap < 2 * sizeof(ncclUniqueId)) return fail(IWAE_ERR_ARG, "comm_unique_id: need a buffer of >= 256 bytes");
@@ -2456,6 +2487,7 @@ int iwae_dataset_upload(iwae_handle m, const uint8_t* gray, int32_t n) {
     m->ds_N = n;
     m->ds_epoch = 0;
     m->ds_has_labels = false;      // (a new set: its labels, if any, follow)
+    m->ds_has_mask = false;        // (... and its masks)
     return IWAE_OK;
 }
 
@@ -2519,12 +2551,89 @@ int iwae_dataset_get_labels(iwae_handle m, int32_t start, int32_t B, float* y_ou
     return IWAE_OK;
 }
 
+// The resident per-image masks: one fixed mask per image of the uploaded set, bit-packed; with one set
+// iwae_train_step_dataset takes the masked step.  The 1-layer unconditional model only (a bf16 handle of a width the masked step refuses may
+// hold a mask: the step refuses, options can change in between).
+namespace {
+int dataset_mask_scope(iwae_model* m, const char* who) {
+    const std::string w(who);
+    if (m->cfg.n_layers != 1 || m->C > 0 || m->has_prior) return fail(IWAE_ERR_STATE, w + ": per-image masks belong to the 1-layer unconditional model (the masked step's)");
+    if (m->ds_N <= 0) return fail(IWAE_ERR_STATE, w + ": no dataset uploaded");
+    return IWAE_OK;
+}
+}  // namespace
+
+int iwae_dataset_set_mask(iwae_handle m, const uint8_t* mask, int32_t n) {
+    if (!m) return fail(IWAE_ERR_ARG, "null handle");
+    if (!mask) { m->ds_has_mask = false; return IWAE_OK; }
+    CHK(dataset_mask_scope(m, "dataset_set_mask"));
+    if (n != m->ds_N) return fail(IWAE_ERR_ARG, "dataset_set_mask: one mask row per image of the uploaded set");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    const int W = mask_words(m->X);
+    CHK(ensure(m->ds_mask, (size_t)n * W * 4, m->stream));
+    if (is_device_ptr(mask, m->cfg.device)) {
+        launch_mask_pack(mask, n, m->X, ptr<uint32_t>(m->ds_mask), m->stream);
+        HIPCHK(hipGetLastError());
+    } else {
+        std::vector<uint32_t> bits((size_t)n * W, 0u);
+        for (int i = 0; i < n; ++i)
+            for (int f = 0; f < m->X; ++f)
+                if (mask[(size_t)i * m->X + f] != 0) bits[(size_t)i * W + (f >> 5)] |= 1u << (f & 31);
+        HIPCHK(hipMemcpyAsync(m->ds_mask.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->ds_has_mask = true;
+    return IWAE_OK;
+}
+
+int iwae_dataset_mcar_mask(iwae_handle m, double rate, uint64_t mask_seed) {
+    if (!m) return fail(IWAE_ERR_ARG, "null handle");
+    CHK(dataset_mask_scope(m, "dataset_mcar_mask"));
+    if (!(rate >= 0.0 && rate <= 1.0)) return fail(IWAE_ERR_ARG, "dataset_mcar_mask: rate must lie in [0, 1]");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    const uint32_t thr = (uint32_t)floor(rate * 16777216.0 + 0.5);
+    CHK(ensure(m->ds_mask, (size_t)m->ds_N * mask_words(m->X) * 4, m->stream));
+    launch_mask_mcar(m->ds_N, m->X, thr, mask_seed, ptr<uint32_t>(m->ds_mask), m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->ds_has_mask = true;
+    return IWAE_OK;
+}
+
+int iwae_dataset_get_mask(iwae_handle m, int32_t start, int32_t B, uint8_t* mask_out) {
+    if (!m || !mask_out || m->ds_N <= 0 || start < 0 || B <= 0 || start + B > m->ds_N) return fail(IWAE_ERR_ARG, "dataset_get_mask: bad range");
+    if (!m->ds_has_mask) return fail(IWAE_ERR_STATE, "dataset_get_mask: no masks (iwae_dataset_set_mask / iwae_dataset_mcar_mask)");
+    HIPCHK(hipSetDevice(m->cfg.device));
+    CHK(ensure(m->scratch, (size_t)B * m->X, m->stream));
+    GatherMaskedArgs g;
+    memset(&g, 0, sizeof(g));
+    g.data = ptr<uint8_t>(m->ds_data); g.order = ptr<int32_t>(m->ds_order); g.bits = ptr<uint32_t>(m->ds_mask);
+    g.start = start; g.B = B; g.X = m->X; g.Xp = m->Xinp; g.Bp = round_up(B, 128); g.seed = m->cfg.seed; g.epoch = m->ds_epoch;
+    g.mask = ptr<uint8_t>(m->scratch);      // (the mask bytes alone: no row of the step's buffers is touched)
+    launch_gather_binarize_masked(g, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(mask_out, m->scratch.p, (size_t)B * m->X, hipMemcpyDefault, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return IWAE_OK;
+}
+
 int iwae_train_step_dataset(iwae_handle m, int32_t start, int32_t B, int32_t k, float beta, float lr, int32_t objective, iwae_scalars* scalars) {
     if (!m) return fail(IWAE_ERR_ARG, "null handle");
     if (m->ds_N <= 0) return fail(IWAE_ERR_STATE, "train_step_dataset: no dataset uploaded");
     if (start < 0 || B <= 0 || start + B > m->ds_N) return fail(IWAE_ERR_ARG, "train_step_dataset: batch range outside the dataset");
-    m->ds_start = start;
-    int rc = iwae_train_step(m, nullptr, B, k, beta, lr, objective, nullptr, scalars, nullptr);
+    int rc;
+    if (m->ds_has_mask) {      // iwae_train_step_masked on (iwae_dataset_get_batch, iwae_dataset_get_mask) of these rows, fed on the device
+        HIPCHK(hipSetDevice(m->cfg.device));
+        CHK(masked_scope(m, "train_step_dataset", nullptr, B, k, nullptr, true));
+        CHK(check_objective(m, objective));
+        FwdCall call{m->batch_offset};
+        call.mask_resident = true;
+        m->ds_start = start;
+        rc = train_step_masked_call(m, nullptr, B, k, beta, lr, objective, nullptr, scalars, nullptr, call);
+    } else {
+        m->ds_start = start;
+        rc = iwae_train_step(m, nullptr, B, k, beta, lr, objective, nullptr, scalars, nullptr);
+    }
     m->ds_start = -1;
     return rc;
 }

@@ -147,6 +147,16 @@ int f32_block_bwd(iwae_model* m, int base, iwae_model::F32Block& w, const float*
     return IWAE_OK;
 }
 
+// the masked step's output layer as masked_out_f32_kernel (the fused route): options, row count and the kernel's own predicate -- nothing of the staged input
+bool masked_out_fused(const iwae_model* m, int M, int k) {
+    const StepOptions& o = m->opt;
+    const KerasLayer* d3 = &m->klayers[m->dec1[0].sub[0]] + 2;
+    MaskedOutF32Args mo;
+    memset(&mo, 0, sizeof(mo));
+    mo.H = d3->Kin; mo.X = m->X; mo.k = k; mo.W3 = m->param + d3->offW; mo.b3 = m->param + d3->offb;
+    return o.allow_masked_out_fused && M >= o.masked_out_min_rows && masked_out_f32_ok(mo);
+}
+
 // Which kernels a float32 call launches and on which streams, decided once from the options, the layer tables, the call's shape and the staged
 // input xd.  As pure as plan_step: it touches no buffer, stream or event and fills p in place.  forward_f32 calls it behind stage_input:
 // dec_fwd_f32_ok also asks for the alignment of x, and a caller's device pointer is read in place.
@@ -185,10 +195,7 @@ void plan_step_f32(const iwae_model* m, int B, int k, int objective, bool bwd, c
     if (fuse_bern) p.px_parts = 2 * ((X + 127) / 128);
     p.keeps_s = bwd && (fused_dec || fuse_bern);
     if (maskd) {      // (never F32_DEC_ONE_LAUNCH / F32_PX_GEMM_EPILOGUE: neither kernel knows the mask; never dl_f32_kernel: it reads x at every pixel)
-        MaskedOutF32Args mo;
-        memset(&mo, 0, sizeof(mo));
-        mo.H = d3->Kin; mo.X = X; mo.k = k; mo.W3 = m->param + d3->offW; mo.b3 = m->param + d3->offb;
-        const bool fast = o.allow_masked_out_fused && M >= o.masked_out_min_rows && masked_out_f32_ok(mo);
+        const bool fast = masked_out_fused(m, M, k);
         p.dec_fwd = F32_DEC_GEMMS;
         p.px_from = fast ? F32_PX_MASKED_OUT : F32_PX_MASKED_PASS;
         p.px_parts = 1;
@@ -249,8 +256,24 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
         CHK(copy_in(m, m->epsbuf, eps, (size_t)M * (m->D[0] + (two ? m->D[1] : 0)) * 4));
     }
     const float* xd;
-    CHK(stage_input(m, x, B, true, &xd));
     const uint8_t* maskd = nullptr;
+    bool xcode_staged = false;
+    if (call.mask_resident) {      // the masked step from the resident set: xin, the mask bytes and, on the fused route, the hole-coded rows, one launch
+        CHK(ensure(m->f32.xmask, (size_t)B * X * 4, st));
+        CHK(ensure(m->f32.mask, (size_t)B * X, st));
+        MaskedStage ms;
+        ms.xin = ptr<float>(m->f32.xmask); ms.mask = ptr<uint8_t>(m->f32.mask);
+        if (masked_out_fused(m, M, k)) {
+            CHK(ensure(m->f32.xcode, (size_t)B * X * 4, st));
+            ms.xcode = ptr<float>(m->f32.xcode);
+            xcode_staged = true;
+        }
+        m->time_this = m->timing > 0;
+        const int rc = stage_input(m, x, B, true, &xd, &ms);
+        m->time_this = false;
+        CHK(rc);
+        maskd = ms.mask;
+    } else CHK(stage_input(m, x, B, true, &xd));
     if (call.mask) {      // the masked step: xin = m ? x : 0 is the call's x from here on (the encoder, and the backward pass's encoder weight gradient)
         CHK(staged_in(m, call.mask, m->f32.mask, (size_t)B * m->X, &maskd));
         CHK(ensure(m->f32.xmask, (size_t)B * m->X * 4, m->stream));
@@ -367,7 +390,7 @@ int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const f
         launch_gemm_f32(m->opt.gemm_f32, ga, 1, st);
     } else if (p.px_from == F32_PX_MASKED_OUT) {      // the masked step's fast route: no logits in memory, s stored once (training calls only)
         CHK(ensure(m->f32.xcode, (size_t)B * X * 4, st));
-        launch_masked_code(xd, p.mask, (long)B * X, ptr<float>(m->f32.xcode), st);
+        if (!xcode_staged) launch_masked_code(xd, p.mask, (long)B * X, ptr<float>(m->f32.xcode), st);      // (a resident batch: stage_input wrote them)
         MaskedOutF32Args mo;
         memset(&mo, 0, sizeof(mo));
         mo.G2 = ptr<float>(m->f32.g2); mo.ldg = H; mo.M = M; mo.H = H; mo.X = X;

@@ -613,6 +613,32 @@ class NativeModel:
         check(self.lib.iwae_dataset_get_labels(self.h, int(start), int(B), out.ctypes.data))
         return out
 
+    def dataset_set_mask(self, mask):
+        """One fixed mask per image of the uploaded set, [n, x_dim], non-zero = observed (iwae_dataset_set_mask): train_step_dataset then takes
+        the masked step on (dataset_get_batch, dataset_get_mask) of its rows.  A NumPy array, or a torch uint8 tensor on the handle's device
+        (packed in place); None drops the masks."""
+        if mask is None:
+            check(self.lib.iwae_dataset_set_mask(self.h, None, 0))
+            return
+        if hasattr(mask, "data_ptr") and getattr(mask, "is_cuda", False):
+            if mask.dim() != 2 or mask.shape[1] != self.x_dim or mask.element_size() != 1 or not mask.is_contiguous():
+                raise ValueError("dataset_set_mask: a device mask must be a contiguous [n, %d] uint8 tensor" % self.x_dim)
+            check(self.lib.iwae_dataset_set_mask(self.h, C.c_void_p(mask.data_ptr()), int(mask.shape[0])))
+            return
+        mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1, self.x_dim)
+        check(self.lib.iwae_dataset_set_mask(self.h, mk.ctypes.data, mk.shape[0]))
+
+    def dataset_mcar_mask(self, rate, seed=0):
+        """Masks drawn on the device, each pixel hidden with probability `rate` independently (iwae_dataset_mcar_mask; keyed by `seed`, not
+        the handle's seed); utils.device_mcar_mask(n, x_dim, rate, seed) is the same array on the host."""
+        check(self.lib.iwae_dataset_mcar_mask(self.h, float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def dataset_get_mask(self, start, B):
+        """The mask rows of the batch dataset_get_batch(start, B) returns: [B, x_dim] uint8, 1 = observed."""
+        out = np.empty((B, self.x_dim), dtype=np.uint8)
+        check(self.lib.iwae_dataset_get_mask(self.h, int(start), int(B), out.ctypes.data))
+        return out
+
     def train_step_dataset(self, start, B, k, beta=1.0, lr=1e-3, objective="iwae_elbo", scalars=True):
         s = Scalars()
         check(self.lib.iwae_train_step_dataset(self.h, int(start), int(B), int(k), float(beta), float(lr), OBJECTIVES[objective],

@@ -181,3 +181,39 @@ def mcar_mask(shape, rate, seed=0):
     if not 0.0 <= rate <= 1.0:
         raise ValueError("mcar_mask: rate must lie in [0, 1], got %r" % (rate,))
     return (np.random.default_rng(seed).random(shape) >= rate).astype(np.uint8)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11) over arrays of uint32 counters under one key; four uint32 arrays."""
+    c0, c1, c2, c3 = [np.array(c, dtype=np.uint32) for c in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    lo32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c0.astype(np.uint64)
+        p1 = np.uint64(0xCD9E8D57) * c2.astype(np.uint64)
+        hi0, lo0 = (p0 >> np.uint64(32)).astype(np.uint32), (p0 & lo32).astype(np.uint32)
+        hi1, lo1 = (p1 >> np.uint64(32)).astype(np.uint32), (p1 & lo32).astype(np.uint32)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ np.uint32(k0), lo1, hi0 ^ c3 ^ np.uint32(k1), lo0
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def mcar_threshold(rate):
+    """The integer threshold of the device mask generator: floor(rate 2^24 + 0.5), in double."""
+    rate = float(rate)
+    if not 0.0 <= rate <= 1.0:      # (NaN fails both comparisons)
+        raise ValueError("mcar mask: rate must lie in [0, 1], got %r" % (rate,))
+    return int(np.floor(rate * 16777216.0 + 0.5))
+
+
+def device_mcar_mask(n, x_dim, rate, seed=0):
+    """The masks iwae_dataset_mcar_mask draws for an n-image set, bit for bit: uint8 [n, x_dim], 1 = observed.  Pixel f of image i is
+    hidden iff (philox4x32_10(counter = (i, 'MASK', f >> 2, 0), key = (seed lo, seed hi))[f & 3] >> 8) < floor(rate 2^24 + 0.5)."""
+    thr = mcar_threshold(rate)
+    n, x_dim, seed = int(n), int(x_dim), int(seed) & 0xFFFFFFFFFFFFFFFF
+    nq = (x_dim + 3) // 4
+    c0 = np.broadcast_to(np.arange(n, dtype=np.uint32)[:, None], (n, nq))
+    c2 = np.broadcast_to(np.arange(nq, dtype=np.uint32)[None, :], (n, nq))
+    r = _philox4x32_10(c0, np.uint32(0x4D41534B), c2, np.uint32(0), seed & 0xFFFFFFFF, seed >> 32)
+    u = np.stack([w >> np.uint32(8) for w in r], axis=-1).reshape(n, 4 * nq)[:, :x_dim]
+    return (u.astype(np.int64) >= thr).astype(np.uint8)
