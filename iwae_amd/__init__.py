@@ -1,7 +1,8 @@
 """iwae_amd -- MI355X-native (gfx950) drop-in for the train / eval step of nbip/IWAE.
 
 Layout (only what the hot path needs):
-  csrc/        hand-written HIP kernels + the C ABI (libiwae_amd.so, include/iwae_amd.h)
+  csrc/        hand-written HIP kernels + the C ABI (libiwae_amd.so, include/iwae_amd.h): model.hip the handle, the step driver and
+               the ABI, step_bf16.hip / step_f32.hip the two steps' host paths, analysis.hip the analyses, *_kernels.hip the kernels
   _capi.py     ctypes binding of the C ABI
   native.py    numpy-in / numpy-out wrapper over the ABI
   iwae1.py     reference API of src/iwae1.py   (IWAE, train_step, val_step, sample)

@@ -167,7 +167,7 @@ SYMBOLS = {
 
 _lib = None
 
-_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "device_helpers.h", "fp32_kernels.hip", "grid_kernels.hip", "impute_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "local_kernels.hip", "masked_kernels.hip", "model.h", "model.hip", "moments_kernels.hip", "posterior_kernels.hip", "row_kernels.hip", "step_f32.hip", "step_helpers.h", "update_kernels.hip", "wgrad_kernels.hip",
+_ID_SOURCES = ("activity_kernels.hip", "aggregate_kernels.hip", "ais_kernels.hip", "analysis.hip", "build.sh", "device_helpers.h", "fp32_kernels.hip", "grid_kernels.hip", "impute_kernels.hip", "kernels.h", "kernels.hip", "layout.h", "local_kernels.hip", "masked_kernels.hip", "model.h", "model.hip", "moments_kernels.hip", "posterior_kernels.hip", "row_kernels.hip", "step_bf16.hip", "step_f32.hip", "step_helpers.h", "update_kernels.hip", "wgrad_kernels.hip",
                os.path.join("..", "..", "include", "iwae_amd.h"))
 
 

@@ -1,6 +1,6 @@
 // What the host translation units of libiwae_amd.so share: the handle (iwae_model), its workspaces, the helpers model.hip defines and
-// analysis.hip and step_f32.hip call, and the float32 step's entry points (step_f32.hip).  Internal to the library -- everything here has
-// hidden visibility, the exported surface is include/iwae_amd.h alone.
+// analysis.hip, step_bf16.hip and step_f32.hip call, and the two steps' entry points (step_bf16.hip, step_f32.hip).  Internal to the
+// library -- everything here has hidden visibility, the exported surface is include/iwae_amd.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -459,12 +459,29 @@ int build_descs(iwae_model* m);
 float adam_alpha(iwae_model* m, float lr);
 void adam_blocks(iwae_model* m, hipStream_t st, int first, int count, float alpha, float grad_scale, hipEvent_t done = nullptr, bool update = true);
 int adam_impl(iwae_model* m, float lr, float gscale);
+// (the bf16 step's share)
+void reduce_blocks(iwae_model* m, hipStream_t st, BlockRange a, BlockRange b, float alpha, bool update, hipEvent_t done, bool with_means);
+int attach_dense_stamps(iwae_model* m, int epi, iwae::DenseArgs& a);
+bool block_fwd_shape(const iwae_model* m, const Linear* blk, int R, iwae::BlockFwdArgs& a);
+// row stride of the cached draws: the latent width rounded to 4, NOT the 32-padded operand width -- D = 100: 400 B instead of 512 B per row,
+// 5.7 MB less per pass over the k = 50, B = 1 024 step's draws (written once, read by the decoder kernel and by latent_bwd_kernel)
+inline int eps_ld(const iwae_model* m, int layer) { return 4 * ((m->D[layer] + 3) / 4); }
+inline hipStream_t on_stream(const iwae_model* m, OnStream s) { return s == ON_SIDE2 ? m->side2 : s == ON_SIDE ? m->side : m->stream; }
+// (the step driver: the forward / backward pass of the given / the handle's precision -- nothing else chooses between forward_f32 / forward_impl
+// and backward_f32 / backward_impl)
+int step_forward(iwae_model* m, int precision, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd, const iwae_tensors* want,
+                 const FwdCall& call);
+int step_backward(iwae_model* m, int objective, StepEnd end, float lr = 0.0f);
 
 // ---- defined in step_f32.hip
 int f32_fwd(iwae_model* m, const KerasLayer& kl, const float* X, long ldx, int rows, float* Y, long ldy, int epi, bool no_ksplit);
 int f32_block_fwd(iwae_model* m, int base, iwae_model::F32Block& w, const float* X, long ldx, int R, float* head, int Dp, bool no_ksplit);
 int forward_f32(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd, const iwae_tensors* want, const FwdCall& call);
 int backward_f32(iwae_model* m, int objective, StepEnd end, float lr = 0.0f);
+
+// ---- defined in step_bf16.hip
+int forward_impl(iwae_model* m, const float* x, int B, int k, float beta, const float* eps, int objective, bool bwd, const iwae_tensors* want, const FwdCall& call);
+int backward_impl(iwae_model* m, int objective, StepEnd end, float lr = 0.0f);
 
 // ---- a caller's array may live on the host or on the handle's device.  Input: a device pointer is read in place, host memory is uploaded into ws
 template <class T> int staged_in(iwae_model* m, const T* user, DevBuf& ws, size_t bytes, const T** dev) {

@@ -26,7 +26,7 @@ SEED = 123            # the handles' noise seed
 # layout.h / model.hip (iwae_create): Hp = round_up(H, 32), Dp = round_up(D, 32), Xp32 = round_up(X, 32); a GEMM over K features has
 # KT = round_up(K, 32) / 32 k-steps; the row-evaluation kernels count 16-feature tiles (kernels.h: AIS_NT = 13 hidden, AIS_DT = 8 latent).
 A_TILE = (16, 128, 48)       # one hidden 32-step under the widest latent: the head GEMM is 2 Dp = 256 wide out of Kp32 = 32 (lat_in_block_ok,
-#                              model.hip: Dp == blk[2].Np32 / 2 at Dp = 128); d1[0].KT == 4 && d1[0].Kp32 == Dp (plan_step fuse_z / dec_fused)
+#                              step_bf16.hip: Dp == blk[2].Np32 / 2 at Dp = 128); d1[0].KT == 4 && d1[0].Kp32 == Dp (plan_step fuse_z / dec_fused)
 #                              from 8 192 rows; ais_kernels.hip e[AIS_DT][4], p[AIS_DT][4] with all 8 tiles live; Dp > Hp
 A_ODD = (33, 127, 17)        # every width odd, D > H > X; H one past a 32-step (Hp = 64 holds 31 pad lanes); the last latent quad cut at 3 of 4
 A_REF = (48, 100, 784)       # the reference's latent and pixels over a narrow hidden layer: hidden KT 2 < latent KT 4 (d1[0].Np32 != d1[0].Kp32)
@@ -94,7 +94,7 @@ def layers_of(c):
     return 2 if c.shape in SHAPES_2L else 1
 
 
-# -- few rows (B k <= 40, B no multiple of 4): block_fwd / block_bwd with lat_in_block (model.hip: Dp == blk[2].Np32 / 2) and
+# -- few rows (B k <= 40, B no multiple of 4): block_fwd / block_bwd with lat_in_block (step_bf16.hip: Dp == blk[2].Np32 / 2) and
 #    dec_bwd_rows_kernel; the five objectives spread over the shapes, one beta != 1
 FEW_1L = [
     case("A_TILE", 5, 3, "iwae_elbo"),            # heads 256 wide out of one 32-step (blk[2].KT == blk[1].KT == 1, blk[1].Np32 == blk[0].Np32 == 32)

@@ -45,7 +45,7 @@ BF16_1L = [
     case(1, 1, "vae_elbo"),                  # B = 1, M = 1: one workgroup in every per-image kernel, invB = 1
     case(1, 1, "iwae_elbo"),                 # the same through the softmax (al = 1)
     case(1, 65, "iwae_elbo"),                # one image over five 16-row workgroups, each recomputing it; lse_image `single = k <= 64` false: second pass
-    case(7, 16, "iwae_elbo"),                # plan_step `lat_fuse` (model.hip: k <= 16): latent_image_part fused into block_bwd_kernel
+    case(7, 16, "iwae_elbo"),                # plan_step `lat_fuse` (step_bf16.hip: k <= 16): latent_image_part fused into block_bwd_kernel
     case(7, 17, "iwae_elbo"),                # ... and one past it: latent_bwd_kernel on its own
     case(3, 63, "iwae_eq14"),                # lse_image `single`: the last lane idle
     case(3, 64, "dreg"),                     # lse_image `single`: every lane holds a sample

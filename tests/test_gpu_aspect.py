@@ -2,7 +2,7 @@
 
 Every other model of the suite has n_hidden >= n_latent, the large row-count kernels only ever run at the reference's widths +-1, and the
 row-evaluation kernels (ais_chain_kernel, local_q_kernel, impute_rows_kernel, posterior_moments_kernel) never at the widths that fill
-their arrays.  The step plan's shape predicates are equalities of padded widths (model.hip plan_step, kernels.hip *_ok), some of which hold
+their arrays.  The step plan's shape predicates are equalities of padded widths (step_bf16.hip plan_step, kernels.hip *_ok), some of which hold
 trivially at H >= D; the row-evaluation kernels size their LDS strips by max(Hp, Dp).  Here the SAME operations run against the SAME
 oracle at the SAME tolerances (tests/_parity_common.py; the run-time rule of tests/test_gpu_ais.py: 8 x the float32 restatement's deviation
 from float64, floor 1e-5) at the shapes of tests/_aspect_cases.py -- each names the predicate or array bound it cuts, and

@@ -248,7 +248,7 @@ def test_float32_step_2layer_spread_weights_matches_exact_oracle(gpu, c):
 
 
 # ---------------------------------------------------------------- 4. the multi-step noise buffers of the few-row step
-# A 1-layer bf16 training step on few rows (dec_rows_step, model.hip) on the device's own noise takes its draws from two buffers that hold
+# A 1-layer bf16 training step on few rows (dec_rows_step, step_bf16.hip) on the device's own noise takes its draws from two buffers that hold
 # EPSM_STEPS = 8 consecutive steps each (plan_step: eps_multi; draw_eps_multi / epsm_find): one launch per 8 steps.  Option no_eps_multi
 # draws every step on its own.  Both must see the same numbers: Philox is keyed by (seed, step, row), not by the launch.
 EPSM_B, EPSM_K, EPSM_S0 = 20, 5, 41
@@ -262,7 +262,7 @@ def _epsm_inputs():
 
 def test_multi_step_noise_buffers_are_bitwise_the_per_step_draws(gpu):
     """20 consecutive train steps from iwae_set_step(41) on a default handle and on one with no_eps_multi: parameters and Adam state
-    bitwise equal after EVERY call.  Read off forward_impl (model.hip): calls 0-2 take steps 41-43 from the group [41, 49) drawn at the
+    bitwise equal after EVERY call.  Read off forward_impl (step_bf16.hip): calls 0-2 take steps 41-43 from the group [41, 49) drawn at the
     first call; before call 3 iwae_set_step jumps into the middle of that group (step 46 = slot 5, no multiple of 8: a hit); step 48, the
     group's last, draws [49, 57) into the other buffer (a hand-over); call 12 runs at B = 12 (step 55, another batch shape: a miss that
     redraws the first buffer); call 13 returns to B = 20 at step 56 and hits slot 7 of the buffer the B = 12 call left alone, then hands
