@@ -446,6 +446,37 @@ typedef struct {
 int iwae_local_posterior(iwae_handle h, const float* x, int32_t N,        /* [N, x_dim], host or device, any values in [0,1] */
                          const iwae_local_options* opt, const iwae_local_outputs* out);
 
+/* iwae_ais and iwae_local_posterior for incomplete images (Mattei & Frellsen 2019): the AIS estimate of log p(x_obs), HMC draws from
+ * p(z | x_obs), and the best factorised Gaussian for p(z | x_obs) -- the tight counterparts of iwae_impute's k-sample bound.  mask
+ * [N, x_dim] marks the observed pixels (non-zero): exactly iwae_impute_options.mask.  The option and output structs are the unmasked calls'.
+ * mask == NULL hands on to the unmasked call before any check of its own, bit for bit (the convention of the iwae_*_masked step calls).
+ * Encoder: wherever the unmasked call uses the encoder heads (the encoder init of AIS; the encoder start and q_mu / q_sigma of the local
+ * posterior) they are the heads of xin_nj = m_nj ? x_nj : 0 in the eval precision, as in iwae_impute.
+ * Definitions: every formula of iwae_ais and iwae_local_posterior holds with
+ *   log p(x|z)  ->  sum_{j: m_nj != 0} [x_nj l_j - softplus(l_j)]        and its gradient started from  s_j = m_nj ? x_nj - sigmoid(l_j) : 0
+ * so the HMC target is p(z | x_obs) ~ p(x_obs | z) p(z), log_px estimates log p(x_obs), and the Adam ascent finds the factorised Gaussian
+ * closest to p(z | x_obs).
+ * Unobserved pixels are SELECTED out, not multiplied out (iwae_impute's contract): what x holds at a pixel with m = 0, NaN or garbage,
+ * reaches no output, bitwise.  The kernels read rows xc = m ? x : a hole code (all ones, compared as bits; an observed x with exactly those
+ * bits is stored one bit off, still a NaN) and the value of an unobserved pixel is only ever the unchosen side of a select.
+ * An image with nothing observed has log p(x_obs|z) = 0 and a zero likelihood gradient: its AIS target is the prior and log p(x_obs) = 0;
+ * its local posterior moves towards N(0, I).
+ * Noise and determinism: the noise keys, the step advance (T + 1; T + E), the caller-noise rules, the chunking options (ais_t_chunk,
+ * local_t_chunk), determinism and the reduction orders are the unmasked calls'; a chain's or image's outputs additionally depend on that
+ * image's mask row and on nothing else.  With a mask of ones every output equals the unmasked call's, bitwise.
+ * Hence: T = 1, betas = {0, 1}, encoder init: log_px is iwae_impute's log_px at k = C on the same step and offset (both draw
+ * iwae_debug_eps(N, C, 0)); iwae_local_posterior_masked with T = 0, E = 1 from the encoder start: iwae[n] is iwae_impute's log_px at k = S
+ * (each up to the other call's float32 kernels).
+ * Models and refusals: the unmasked calls' (1-layer unconditional, n_hidden <= 208, n_latent <= 128, the same argument checks):
+ * IWAE_ERR_ARG before any launch, the noise step unchanged.
+ * Workspace: the unmasked calls', plus 4 N x_dim bytes for xin, 4 N x_dim for the coded rows and N x_dim for the mask's copy when it
+ * arrives on the host.
+ * mask: host or device. */
+int iwae_ais_masked(iwae_handle h, const float* x, const uint8_t* mask, int32_t N,   /* x, mask [N, x_dim], host or device */
+                    const iwae_ais_options* opt, const iwae_ais_outputs* out);
+int iwae_local_posterior_masked(iwae_handle h, const float* x, const uint8_t* mask, int32_t N,
+                                const iwae_local_options* opt, const iwae_local_outputs* out);
+
 /* Masked importance-weighted bound on log p(x_obs) and the self-normalised importance-sampling (SNIS) estimate of E[x | x_obs] (Mattei &
  * Frellsen 2019, "MIWAE: Deep Generative Modelling and Imputation of Incomplete Data Sets"; the snis_z idea of src/iwae1.py:139 carried
  * through the decoder; no reference counterpart).  m [N, x_dim] marks the observed pixels (non-zero), NULL = every pixel observed: the call

@@ -146,6 +146,8 @@ SYMBOLS = {
     "iwae_aggregate_posterior": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _P, _P]),
     "iwae_ais": (C.c_int, [_P, _P, C.c_int32, C.POINTER(AisOptions), C.POINTER(AisOutputs)]),
     "iwae_local_posterior": (C.c_int, [_P, _P, C.c_int32, C.POINTER(LocalOptions), C.POINTER(LocalOutputs)]),
+    "iwae_ais_masked": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(AisOptions), C.POINTER(AisOutputs)]),
+    "iwae_local_posterior_masked": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(LocalOptions), C.POINTER(LocalOutputs)]),
     "iwae_impute": (C.c_int, [_P, _P, C.c_int32, C.POINTER(ImputeOptions), C.POINTER(ImputeOutputs)]),
     "iwae_posterior": (C.c_int, [_P, _P, C.c_int32, C.POINTER(PosteriorOptions), C.POINTER(PosteriorOutputs)]),
     "iwae_grad_moments": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -55,6 +55,9 @@ __global__ __launch_bounds__(AIS_THREADS) void ais_init_kernel(AisInitArgs a) {
     }
 }
 
+// HOLES (iwae_ais_masked): a.x holds launch_masked_code's rows m ? x : MO_HOLE; a pixel with the hole's bits is selected
+// out of log p(x|z) and of s like a pad column
+template <bool HOLES>
 __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem_ais[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -157,12 +160,13 @@ __global__ __launch_bounds__(AIS_THREADS, 1) void ais_chain_kernel(AisChainArgs 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float x1 = in ? xrow[r][col] : 0.0f;
-                        const float l = in ? acc[t][r] + b : 0.0f, xm = in ? x1 - 0.5f : 0.0f;
+                        const bool ob = in && (!HOLES || __float_as_uint(x1) != MO_HOLE);      // counts: inside the image and observed
+                        const float l = ob ? acc[t][r] + b : 0.0f, xm = ob ? x1 - 0.5f : 0.0f;
                         const float ex = __builtin_amdgcn_exp2f(-fabsf(l) * LOG2E_F);      // exp(-|l|)
                         s_xl[r] = fmaf(xm, l, s_xl[r]);
                         s_al[r] += fabsf(l);
-                        prod[r] = in ? fmaf(prod[r], ex, prod[r]) : prod[r];
-                        zs[(4 * q + r) * PZ + 16 * t + n16] = in ? xm - __builtin_copysignf(__builtin_amdgcn_rcpf(1.0f + ex) - 0.5f, l) : 0.0f;
+                        prod[r] = ob ? fmaf(prod[r], ex, prod[r]) : prod[r];
+                        zs[(4 * q + r) * PZ + 16 * t + n16] = ob ? xm - __builtin_copysignf(__builtin_amdgcn_rcpf(1.0f + ex) - 0.5f, l) : 0.0f;
                     }
                 }
             }
@@ -363,7 +367,9 @@ void launch_ais_init(const AisInitArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(ais_init_kernel, dim3((unsigned)((a.R + AIS_THREADS - 1) / AIS_THREADS)), dim3(AIS_THREADS), 0, st, a);
 }
 void launch_ais_chain(const AisChainArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(ais_chain_kernel, dim3((unsigned)((a.R + 63) / 64)), dim3(AIS_THREADS), ais_chain_lds_bytes(a.Dp, a.Hp), st, a);
+    const dim3 grid((unsigned)((a.R + 63) / 64));
+    if (a.holes) hipLaunchKernelGGL(ais_chain_kernel<true>, grid, dim3(AIS_THREADS), ais_chain_lds_bytes(a.Dp, a.Hp), st, a);
+    else hipLaunchKernelGGL(ais_chain_kernel<false>, grid, dim3(AIS_THREADS), ais_chain_lds_bytes(a.Dp, a.Hp), st, a);
 }
 void launch_ais_finish(const AisFinishArgs& a, hipStream_t st) {
     if (a.z) hipLaunchKernelGGL(ais_z_kernel, dim3((unsigned)((a.R * a.D + AIS_THREADS - 1) / AIS_THREADS)), dim3(AIS_THREADS), 0, st, a);

@@ -1,4 +1,4 @@
-// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior, iwae_ais, iwae_local_posterior, iwae_impute and iwae_posterior: the analyses that start
+// iwae_grid_posterior, iwae_latent_activity, iwae_aggregate_posterior, iwae_ais, iwae_local_posterior (both with their _masked forms), iwae_impute and iwae_posterior: the analyses that start
 // from the encoder heads of N images (host code; kernels in the seven *_kernels.hip).  Each reads in five parts: argument checks, eval_begin, its own buffers and launches, its own copy-outs, eval_end.
 #include <math.h>
 #include <string.h>
@@ -112,6 +112,24 @@ int pad_decoder(iwae_model* m, hipStream_t st, int Dp, int Hp, int Xp, DecPad& p
     for (const AisPrepArgs& j : jobs) launch_ais_pad(j, st);
     HIPCHK(hipGetLastError());
     p = DecPad{W1, W1T, W2, W2T, W3, W3T, b1, b2, b3};
+    return IWAE_OK;
+}
+
+// The pixel rows of a masked chain call (iwae_ais_masked, iwae_local_posterior_masked): the mask on the device (the
+// caller's, or a copy in maskbuf), xin = m ? x : 0 for the encoder (c.xd points there from here on) and xc = m ? x : the hole code, which the
+// HOLES instantiations of the row evaluation read in place of x (*xcode).
+int mask_rows(EvalCall& c, int N, const uint8_t* mask, DevBuf& maskbuf, DevBuf& xin, DevBuf& xc, const float** xcode) {
+    iwae_model* m = c.m;
+    const long n = (long)N * m->X;
+    const uint8_t* maskd = nullptr;
+    CHK(staged_in(m, mask, maskbuf, (size_t)n, &maskd));
+    CHK(ensure(xin, (size_t)n * 4, c.st));
+    CHK(ensure(xc, (size_t)n * 4, c.st));
+    launch_impute_mask(c.xd, maskd, n, ptr<float>(xin), c.st);
+    launch_masked_code(c.xd, maskd, n, ptr<float>(xc), c.st);
+    HIPCHK(hipGetLastError());
+    c.xd = ptr<float>(xin);
+    *xcode = ptr<float>(xc);
     return IWAE_OK;
 }
 
@@ -505,7 +523,8 @@ int iwae_aggregate_posterior(iwae_handle m, const float* x, int32_t N, int32_t S
 }
 
 // Annealed importance sampling with HMC chains (Neal 2001; Wu et al. 2017): DESIGN.md section 15
-int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o, const iwae_ais_outputs* out) {
+// (mask null: iwae_ais; else iwae_ais_masked -- the same checks, launches and copy-outs, the pixel rows coded and the HOLES kernel)
+static int ais_call(iwae_handle m, const float* x, const uint8_t* mask, int32_t N, const iwae_ais_options* o, const iwae_ais_outputs* out) {
     if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "ais: need x, options and outputs");
     if (o->struct_size != sizeof(iwae_ais_options)) return fail(IWAE_ERR_ARG, "ais: iwae_ais_options.struct_size must be sizeof(iwae_ais_options) = " + std::to_string(sizeof(iwae_ais_options)));
     if (!out->log_px || !o->betas) return fail(IWAE_ERR_ARG, "ais: betas and log_px are required");
@@ -530,6 +549,8 @@ int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o
     hipStream_t st = c.st;
     iwae_model::AisWs& w = m->ais;
     const bool user_noise = given == 3, prior = o->init == IWAE_AIS_INIT_PRIOR;
+    const float* xrows = c.xd;        // what the chains read: the images, or their coded rows
+    if (mask) CHK(mask_rows(c, N, mask, w.mask, w.xin, w.xc, &xrows));
     // ---- base density: the encoder heads in the eval precision, or N(0, I) (head stays null)
     if (!prior) {
         CHK(eval_heads(c, N));
@@ -575,7 +596,7 @@ int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o
     if (out->dH) CHK(staged_out(m, out->dH, w.dH, (size_t)T * R * 4, &dHd));
     if (out->accepted || out->accept_rate) CHK(staged_out(m, out->accepted, w.acc, (size_t)T * R, &accd));      // (the rates alone: the flags stay in the workspace)
     ca.D = D; ca.H = H; ca.X = X; ca.Dp = Dp; ca.Hp = Hp; ca.Xp = Xp;
-    ca.x = c.xd; ca.head = head; ca.ldh = ldh; ca.soff = Dh; ca.N = N; ca.C = C; ca.R = R;
+    ca.x = xrows; ca.holes = mask != nullptr; ca.head = head; ca.ldh = ldh; ca.soff = Dh; ca.N = N; ca.C = C; ca.R = R;
     ca.betas = ptr<float>(w.betas); ca.L = o->L; ca.adapt = o->adapt != 0;
     ca.mom = momd; ca.unif = unifd;
     ca.seed = m->cfg.seed; ca.row_offset = (uint64_t)m->batch_offset * (uint64_t)C; ca.step0 = m->noise_step;
@@ -614,9 +635,15 @@ int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o
     if (!user_noise) m->noise_step += (uint32_t)T + 1u;
     return IWAE_OK;
 }
+int iwae_ais(iwae_handle m, const float* x, int32_t N, const iwae_ais_options* o, const iwae_ais_outputs* out) { return ais_call(m, x, nullptr, N, o, out); }
+// AIS estimate of log p(x_obs) of incomplete images: DESIGN.md section 22
+int iwae_ais_masked(iwae_handle m, const float* x, const uint8_t* mask, int32_t N, const iwae_ais_options* o, const iwae_ais_outputs* out) {
+    return ais_call(m, x, mask, N, o, out);
+}
 
 // Per-image optimisation of a factorised Gaussian q and its evaluation (Cremer, Li & Duvenaud 2018): DESIGN.md section 16
-int iwae_local_posterior(iwae_handle m, const float* x, int32_t N, const iwae_local_options* o, const iwae_local_outputs* out) {
+// (mask null: iwae_local_posterior; else iwae_local_posterior_masked, as ais_call)
+static int local_call(iwae_handle m, const float* x, const uint8_t* mask, int32_t N, const iwae_local_options* o, const iwae_local_outputs* out) {
     if (!m || !x || !o || !out) return fail(IWAE_ERR_ARG, "local_posterior: need x, options and outputs");
     if (o->struct_size != sizeof(iwae_local_options)) return fail(IWAE_ERR_ARG, "local_posterior: iwae_local_options.struct_size must be sizeof(iwae_local_options) = " + std::to_string(sizeof(iwae_local_options)));
     if (!out->elbo) return fail(IWAE_ERR_ARG, "local_posterior: elbo is required");
@@ -638,6 +665,8 @@ int iwae_local_posterior(iwae_handle m, const float* x, int32_t N, const iwae_lo
     CHK(eval_begin(m, x, N, c));
     hipStream_t st = c.st;
     iwae_model::LocalWs& w = m->loc;
+    const float* xrows = c.xd;        // what the rows read: the images, or their coded rows
+    if (mask) CHK(mask_rows(c, N, mask, w.mask, w.xin, w.xc, &xrows));
     // ---- the start: the caller's, or the encoder heads in the eval precision
     const float *mu0d = nullptr, *sg0d = nullptr;
     if (o->mu0) {
@@ -677,7 +706,7 @@ int iwae_local_posterior(iwae_handle m, const float* x, int32_t N, const iwae_lo
     if (out->grad && T > 0) CHK(staged_out(m, out->grad, w.grad, (size_t)N * 2 * D * 4, &gradd));
     if (out->log_w) CHK(staged_out(m, out->log_w, w.logw, (size_t)E * S * N * 4, &logwd));
     la.D = D; la.H = H; la.X = X; la.Dp = Dp; la.Hp = Hp; la.Xp = Xp;
-    la.x = c.xd; la.N = N; la.S = S; la.ipw = 64 / S; la.T = T; la.objective = o->objective;
+    la.x = xrows; la.holes = mask != nullptr; la.N = N; la.S = S; la.ipw = 64 / S; la.T = T; la.objective = o->objective;
     la.alpha = ptr<float>(w.alpha); la.beta1 = o->beta_1; la.beta2 = o->beta_2; la.epsilon = o->epsilon;
     la.inv_S = 1.0f / (float)S; la.log_S = logf((float)S);
     la.eps = epsd; la.seed = m->cfg.seed; la.row_offset = (uint64_t)m->batch_offset * (uint64_t)S; la.step0 = m->noise_step;
@@ -709,6 +738,11 @@ int iwae_local_posterior(iwae_handle m, const float* x, int32_t N, const iwae_lo
     CHK(eval_end(c));
     if (!o->eps) m->noise_step += (uint32_t)(T + E);
     return IWAE_OK;
+}
+int iwae_local_posterior(iwae_handle m, const float* x, int32_t N, const iwae_local_options* o, const iwae_local_outputs* out) { return local_call(m, x, nullptr, N, o, out); }
+// The best factorised Gaussian for p(z | x_obs) of incomplete images: DESIGN.md section 22
+int iwae_local_posterior_masked(iwae_handle m, const float* x, const uint8_t* mask, int32_t N, const iwae_local_options* o, const iwae_local_outputs* out) {
+    return local_call(m, x, mask, N, o, out);
 }
 
 // Masked importance-weighted bound on log p(x_obs) and the SNIS estimate of E[x | x_obs] (Mattei & Frellsen 2019): DESIGN.md section 17

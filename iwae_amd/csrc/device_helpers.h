@@ -39,6 +39,10 @@ __device__ __forceinline__ uint32_t bf_bits_at(const uint4& u, int j) {
 // The code of an unobserved pixel in the bf16 pixel rows of a masked call (masked_code_bf16_kernel writes it, bern8<.., HOLES> compares against it):
 // all ones, a NaN no arithmetic produces -- the float32 step's MO_HOLE at bf16 width (DESIGN.md sections 19, 20)
 constexpr uint32_t BF16_HOLE = 0xFFFFu;
+// The code of an unobserved pixel in float32 pixel rows (masked_code_kernel writes xc = m ? x : the code; masked_out_f32_kernel and the HOLES
+// instantiations of the row evaluation compare against it, as bits): all ones, a NaN no arithmetic produces.  An observed x with exactly these
+// bits is stored one bit off, still a NaN: it stays observed and poisons its image as any observed NaN does.
+constexpr uint32_t MO_HOLE = 0xFFFFFFFFu;
 __device__ __forceinline__ f32x4 mfma16(const uint4& a, const uint4& b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
@@ -270,7 +274,9 @@ __device__ __forceinline__ void dec_row_tanh_layers(const Args& a, const float* 
 // xrow[r]: the image of row 4q + r.  Reads a.W1 .. a.W3T, a.b1 .. a.b3, a.Hp, a.Xp, a.X, a.Dp.  Whole workgroup.
 // ais_chain_kernel's eval_kick lambda is the single deliberate restatement of this function: called from there it cost that kernel, which
 // sits at the register limit, 12 bytes of scratch per lane (256 VGPR / 246 AGPR / 0 -> 256 / 256 / 12).
-template <class Args>
+// HOLES (the masked calls): xrow[r] is a row of launch_masked_code's xc = m ? x : MO_HOLE.  A pixel whose bits are the
+// hole code is SELECTED out like a pad column: it adds exactly nothing to lp and its residual is exactly 0, whatever x held there.
+template <bool HOLES, class Args>
 __device__ __forceinline__ void dec_row_eval(const Args& a, float* zs, float* g1s, float* g2s, float* slab, int PZ, int PH, int dt, int ht, int xt,
                                              int npass, const float* const (&xrow)[4], f32x4 (&acc)[AIS_NT], float (&lp)[4], int tid, int n16, int q) {
     f32x4 dg2[AIS_NT];
@@ -295,12 +301,13 @@ __device__ __forceinline__ void dec_row_eval(const Args& a, float* zs, float* g1
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float x1 = in ? xrow[r][col] : 0.0f;
-                    const float l = in ? acc[t][r] + b : 0.0f, xm = in ? x1 - 0.5f : 0.0f;
+                    const bool ob = in && (!HOLES || __float_as_uint(x1) != MO_HOLE);      // counts: inside the image and observed
+                    const float l = ob ? acc[t][r] + b : 0.0f, xm = ob ? x1 - 0.5f : 0.0f;
                     const float ex = __builtin_amdgcn_exp2f(-fabsf(l) * LOG2E_F);      // exp(-|l|)
                     s_xl[r] = fmaf(xm, l, s_xl[r]);
                     s_al[r] += fabsf(l);
-                    prod[r] = in ? fmaf(prod[r], ex, prod[r]) : prod[r];
-                    zs[(4 * q + r) * PZ + 16 * t + n16] = in ? xm - __builtin_copysignf(__builtin_amdgcn_rcpf(1.0f + ex) - 0.5f, l) : 0.0f;
+                    prod[r] = ob ? fmaf(prod[r], ex, prod[r]) : prod[r];
+                    zs[(4 * q + r) * PZ + 16 * t + n16] = ob ? xm - __builtin_copysignf(__builtin_amdgcn_rcpf(1.0f + ex) - 0.5f, l) : 0.0f;
                 }
             }
         }

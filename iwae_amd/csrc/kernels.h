@@ -601,6 +601,7 @@ struct AisChainArgs {
     uint64_t seed, row_offset; uint32_t step0;
     float* e; double* log_w; float* h; int* nacc;
     float* dH; uint8_t* accepted;     // [T][R] or null
+    int holes;                        // != 0 (iwae_ais_masked): x holds launch_masked_code's rows m ? x : the hole code, the launch takes ais_chain_kernel<true>
 };
 struct AisFinishArgs {                // ais_finish_kernel: z = mu + sigma e; per image log_px = LSE_c log_w - log C and the effective sample size
     const float* head; int ldh, soff;
@@ -641,6 +642,7 @@ struct LocalArgs {
     float* bound;                     // [T][N] or null
     float* grad;                      // [N][2 D] or null: the ascent direction of iteration T - 1
     float* log_w;                     // [E S][N] or null
+    int holes;                        // != 0 (iwae_local_posterior_masked): x holds launch_masked_code's rows m ? x : the hole code, the launch takes local_q_kernel<true>
 };
 struct LocalFinishArgs {              // local_finish_kernel: mu, sigma = exp(rho); elbo = sum / (E S), iwae = max + log(sum exp) - log(E S)
     const float* st; const double* acc;

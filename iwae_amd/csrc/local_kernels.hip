@@ -38,6 +38,8 @@ __global__ __launch_bounds__(LQ_THREADS) void local_init_kernel(LocalInitArgs a)
     if (d == 0) { a.acc[3 * (size_t)n] = 0.0; a.acc[3 * (size_t)n + 1] = -INFINITY; a.acc[3 * (size_t)n + 2] = 0.0; }
 }
 
+// HOLES (iwae_local_posterior_masked): a.x holds launch_masked_code's rows m ? x : MO_HOLE, which dec_row_eval<true> selects out
+template <bool HOLES>
 __global__ __launch_bounds__(LQ_THREADS, 1) void local_q_kernel(LocalArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem_lq[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(LQ_THREADS, 1) void local_q_kernel(LocalArgs a) {
                 }
             }
         }
-        dec_row_eval(a, zs, g1s, g2s, slab, PZ, PH, dt, ht, xt, npass, xrow, acc, lp, tid, n16, q);      // acc: dz = grad_z log p(x|z)
+        dec_row_eval<HOLES>(a, zs, g1s, g2s, slab, PZ, PH, dt, ht, xt, npass, xrow, acc, lp, tid, n16, q);      // acc: dz = grad_z log p(x|z)
         // ---- g = dz - z and g sigma e into the wave's own (now dead) strips, the row's log_w beside them
 #pragma unroll
         for (int k = 0; k < AIS_DT; ++k) {
@@ -217,7 +219,9 @@ void launch_local_init(const LocalInitArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(local_init_kernel, dim3((unsigned)((n + LQ_THREADS - 1) / LQ_THREADS)), dim3(LQ_THREADS), 0, st, a);
 }
 void launch_local_q(const LocalArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(local_q_kernel, dim3((unsigned)((a.N + a.ipw - 1) / a.ipw)), dim3(LQ_THREADS), local_q_lds_bytes(a.Dp, a.Hp), st, a);
+    const dim3 grid((unsigned)((a.N + a.ipw - 1) / a.ipw));
+    if (a.holes) hipLaunchKernelGGL(local_q_kernel<true>, grid, dim3(LQ_THREADS), local_q_lds_bytes(a.Dp, a.Hp), st, a);
+    else hipLaunchKernelGGL(local_q_kernel<false>, grid, dim3(LQ_THREADS), local_q_lds_bytes(a.Dp, a.Hp), st, a);
 }
 void launch_local_finish(const LocalFinishArgs& a, hipStream_t st) {
     const long n = (long)a.N * a.D;

@@ -23,9 +23,7 @@
 namespace iwae {
 namespace {
 
-// the code of an unobserved pixel: all ones (a NaN no arithmetic produces).  An observed x with exactly these bits is stored one bit off,
-// still a NaN: it stays observed and poisons its image as any observed NaN does.
-constexpr uint32_t MO_HOLE = 0xFFFFFFFFu;
+// (the code of an unobserved pixel, MO_HOLE, is device_helpers.h's: the row evaluation of the masked analyses compares against it too)
 
 // s = x - sigmoid(l) = (x - 1/2) - sign(l) (1 / (1 + e^-|l|) - 1/2) through one hardware exp2 and one reciprocal (dec_fwd_f32_kernel's form; absolute
 // error ~1e-7).  Both routes call this one function: adds and single products only, nothing for the compiler to contract differently in two places.

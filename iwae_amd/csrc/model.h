@@ -326,11 +326,11 @@ struct iwae_model {
     // the per-sample densities (log_qzd transposed [Dpad][S N]) and the double sums
     struct AggWs { DevBuf eps, mu, inv, invd, nls, nls_sum, zT, shT, dim_part, jmax, jsum, lqz, lqzdT, lqzd, part, out; } agg;
     // iwae_ais's buffers: the decoder's padded weights, the schedule, the chain state (e, log_w, h, accept counts), the
-    // caller's noise and initial states when they arrive on the host, and the outputs
-    struct AisWs { DevBuf wpad, betas, e, logw, h, nacc, z0, mom, unif, dH, acc, rate, z, lpx, ess; } ais;
+    // caller's noise and initial states when they arrive on the host, and the outputs; iwae_ais_masked's mask copy, masked input and coded rows
+    struct AisWs { DevBuf wpad, betas, e, logw, h, nacc, z0, mom, unif, dH, acc, rate, z, lpx, ess, mask, xin, xc; } ais;
     // iwae_local_posterior's buffers (the padded weights are ais.wpad): the per-image state and double sums, Adam's step sizes, the
-    // caller's start and noise when they arrive on the host, and the outputs
-    struct LocalWs { DevBuf st, acc, alpha, mu0, sg0, eps, qmu, qsg, mu, sg, elbo, iwae, bound, grad, logw; } loc;
+    // caller's start and noise when they arrive on the host, and the outputs; iwae_local_posterior_masked's mask copy, masked input and coded rows
+    struct LocalWs { DevBuf st, acc, alpha, mu0, sg0, eps, qmu, qsg, mu, sg, elbo, iwae, bound, grad, logw, mask, xin, xc; } loc;
     // iwae_impute's buffers (the padded weights are ais.wpad): the masked input, the caller's mask and noise when they arrive on the host,
     // the log-weights, per image (max, 1 / sum), the chunk sums of xhat (more than 64 draws per image) and the outputs
     struct ImputeWs { DevBuf xin, mask, eps, logw, wstat, part, lpx, ess, xhat; } imp;

@@ -81,18 +81,23 @@ class IWAE(BaseIWAE):
         if self._net.cond_dim:
             raise NotImplementedError("annealed importance sampling covers the unconditional 1-layer model only")
 
-    def ais_log_likelihood(self, X, n_chains=16, n_temps=1000, **kwargs):
+    def ais_log_likelihood(self, X, mask=None, n_chains=16, n_temps=1000, **kwargs):
         """Test-set log p(x) by annealed importance sampling with HMC transitions (iwae_ais): a stochastic lower bound that tightens
-        with n_temps where the k-sample bound of the evaluator is limited by the encoder.  Returns (mean, the binding's dict)."""
+        with n_temps where the k-sample bound of the evaluator is limited by the encoder.  mask [N, x_dim] (non-zero = observed): the
+        images are incomplete and the estimate is of log p(x_obs) (iwae_ais_masked), the tight counterpart of impute()'s bound; what X
+        holds at an unobserved pixel is never read.  Returns (mean, the binding's dict)."""
         self._ais_scope()
-        res = self._net.ais(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), n_chains=n_chains, n_temps=n_temps, **kwargs)
+        res = self._net.ais(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), n_chains=n_chains, n_temps=n_temps, mask=mask, **kwargs)
         return float(np.mean(res["log_px"])), res
 
-    def bdmc(self, n, n_chains=16, n_temps=1000, seed=0, schedule="sigmoid", **kwargs):
+    def bdmc(self, n, n_chains=16, n_temps=1000, seed=0, schedule="sigmoid", mask=None, **kwargs):
         """Bidirectional Monte Carlo on n images simulated from the model: z ~ N(0, I), x ~ Bernoulli(decode(z)) (a seeded host generator),
         so z is an exact posterior sample of x.  The forward run (ascending betas) gives a stochastic lower bound of log p(x), the reverse
         run (descending betas, every chain started at the exact sample) a stochastic upper bound, upper = -(LSE_c log_w_rev - log C).
-        kwargs (leapfrog, step_size, adapt, init) go to both runs.  Returns {"x", "z", "lower", "upper" [n] float64, "gap": mean(upper - lower), "forward", "reverse": the two runs' dicts}."""
+        kwargs (leapfrog, step_size, adapt, init) go to both runs.  mask: an [n, x_dim] array (non-zero = observed) or a callable on the
+        simulated x that returns one; both runs then bracket log p(x_obs).  The simulated z is still an exact posterior sample given x_obs
+        alone -- x_obs is a marginal of x, so (z, x_obs) is a joint draw of p(z) p(x_obs|z) -- and the reverse run stays valid.
+        Returns {"x", "z", "lower", "upper" [n] float64, "gap": mean(upper - lower), "forward", "reverse": the two runs' dicts}, with a mask also "mask"."""
         self._ais_scope()
         rng = np.random.default_rng(seed)
         D = self._net.n_latent[0]
@@ -100,6 +105,9 @@ class IWAE(BaseIWAE):
         probs = self._net.decode(z)
         x = (rng.random(probs.shape) < probs).astype(np.float32)
         betas = ais_schedule(n_temps, schedule)
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask(x) if callable(mask) else mask) != 0, dtype=np.uint8).reshape(x.shape)
+            kwargs = dict(kwargs, mask=mask)
         fwd = self._net.ais(x, n_chains=n_chains, betas=betas, **kwargs)
         z0 = np.ascontiguousarray(np.broadcast_to(z[None], (int(n_chains),) + z.shape))
         rev = self._net.ais(x, n_chains=n_chains, betas=betas[::-1].copy(), z0=z0, **kwargs)
@@ -107,32 +115,37 @@ class IWAE(BaseIWAE):
         m = lw.max(axis=0)
         upper = -(m + np.log(np.mean(np.exp(lw - m[None]), axis=0)))
         lower = fwd["log_px"]
-        return {"x": x, "z": z, "lower": lower, "upper": upper, "gap": float(np.mean(upper - lower)), "forward": fwd, "reverse": rev}
+        out = {"x": x, "z": z, "lower": lower, "upper": upper, "gap": float(np.mean(upper - lower)), "forward": fwd, "reverse": rev}
+        if mask is not None:
+            out["mask"] = mask
+        return out
 
     # ---- per-image posterior optimisation and the inference-gap split (Cremer, Li & Duvenaud 2018)
     def _local_scope(self):
         if self._net.cond_dim:
             raise NotImplementedError("per-image posterior optimisation covers the unconditional 1-layer model only")
 
-    def local_posterior(self, X, n_samples=16, n_iters=200, n_eval=8, **kwargs):
+    def local_posterior(self, X, mask=None, n_samples=16, n_iters=200, n_eval=8, **kwargs):
         """The best factorised Gaussian q*(z|x) of every image of X found by n_iters Adam iterations on (mu, log sigma) from the encoder's
-        q(z|x) (iwae_local_posterior; kwargs: objective, lr, start, noise, trace, beta_1, beta_2, epsilon).  Returns the binding's dict."""
+        q(z|x) (iwae_local_posterior; kwargs: objective, lr, start, noise, trace, beta_1, beta_2, epsilon).  mask [N, x_dim] (non-zero =
+        observed): q* is fitted to p(z | x_obs) from the encoder's q(z | x_obs) (iwae_local_posterior_masked).  Returns the binding's dict."""
         self._local_scope()
         return self._net.local_posterior(np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim), n_samples=n_samples, n_iters=n_iters,
-                                         n_eval=n_eval, **kwargs)
+                                         n_eval=n_eval, mask=mask, **kwargs)
 
-    def inference_gaps(self, X, n_samples=16, n_iters=200, n_eval=64, lr=0.05, ais=None):
+    def inference_gaps(self, X, mask=None, n_samples=16, n_iters=200, n_eval=64, lr=0.05, ais=None):
         """log p(x) - ELBO[q_enc] of every image of X split into the approximation gap log p(x) - ELBO[q*] (what no factorised Gaussian
         can close) and the amortisation gap ELBO[q*] - ELBO[q_enc] (what the encoder loses against the best one).  log p(x): annealed
         importance sampling (ais: the arguments of ais_log_likelihood); ELBO[q_enc]: n_eval passes of n_samples draws from the encoder's
         q (no iterations); ELBO[q*]: the same after n_iters ELBO iterations.  Returns per-image float64 arrays log_px, elbo_amortized,
         elbo_local, approximation_gap, amortization_gap, the standard errors elbo_amortized_se and elbo_local_se of the two means (from the
-        evaluation log-weights), log_px_se (delta method over the chains) and the three runs' dicts (ais, amortized, local)."""
+        evaluation log-weights), log_px_se (delta method over the chains) and the three runs' dicts (ais, amortized, local).  mask
+        [N, x_dim] (non-zero = observed): all three runs take it, and the split is of log p(x_obs) - ELBO[q_enc(z | x_obs)]."""
         self._local_scope()
         X = np.asarray(X, dtype=np.float32).reshape(-1, self._net.x_dim)
-        _, a = self.ais_log_likelihood(X, **(ais or {}))
-        amort = self._net.local_posterior(X, n_samples=n_samples, n_iters=0, n_eval=n_eval, objective="elbo")
-        local = self._net.local_posterior(X, n_samples=n_samples, n_iters=n_iters, n_eval=n_eval, objective="elbo", lr=lr)
+        _, a = self.ais_log_likelihood(X, mask=mask, **(ais or {}))
+        amort = self._net.local_posterior(X, n_samples=n_samples, n_iters=0, n_eval=n_eval, objective="elbo", mask=mask)
+        local = self._net.local_posterior(X, n_samples=n_samples, n_iters=n_iters, n_eval=n_eval, objective="elbo", lr=lr, mask=mask)
         out = utils.inference_gap_split(a["log_px"], amort["elbo"], local["elbo"])
         out["elbo_amortized_se"], out["elbo_local_se"] = utils.mean_se(amort["log_w"]), utils.mean_se(local["log_w"])
         out["log_px_se"] = utils.log_mean_exp_se(a["log_w"])

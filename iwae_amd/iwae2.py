@@ -43,14 +43,14 @@ class IWAE(BaseIWAE):
         raise NotImplementedError("the aggregate posterior covers the 1-layer model only: q(z2|x) of the 2-layer model is not Gaussian and "
                                   "its p(z1) is not N(0,1)")
 
-    def ais_log_likelihood(self, X, n_chains=16, n_temps=1000, **kwargs):
+    def ais_log_likelihood(self, X, mask=None, n_chains=16, n_temps=1000, **kwargs):
         raise NotImplementedError("annealed importance sampling covers the 1-layer model only: the 2-layer chain would have to move (z1, z2) "
                                   "jointly under p(z1|z2) p(z2)")
 
     def bdmc(self, n, n_chains=16, n_temps=1000, seed=0, **kwargs):
         self.ais_log_likelihood(None)
 
-    def local_posterior(self, X, n_samples=16, n_iters=200, n_eval=8, **kwargs):
+    def local_posterior(self, X, mask=None, n_samples=16, n_iters=200, n_eval=8, **kwargs):
         raise NotImplementedError("per-image posterior optimisation covers the 1-layer model only: the 2-layer q(z2|z1) q(z1|x) is not one "
                                   "factorised Gaussian per image")
 

@@ -398,13 +398,22 @@ class NativeModel:
             out["log_qz"], out["log_qzd"] = lqz, lqzd
         return out
 
+    def _mask_of(self, who, mask, x):
+        """mask as the uint8 [N, x_dim] array the masked analyses take (non-zero = observed)"""
+        mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1, self.x_dim)
+        if mk.shape != x.shape:
+            raise ValueError("%s: mask must be [N, x_dim] = %s, got %s" % (who, x.shape, mk.shape))
+        return mk
+
     def ais(self, x, n_chains=16, n_temps=1000, leapfrog=10, step_size=0.1, adapt=True, init="encoder", betas=None, z0=None, noise=None,
-            trace=False, schedule="sigmoid"):
+            trace=False, schedule="sigmoid", mask=None):
         """iwae_ais: annealed importance sampling log p(x) of the images x [N, x_dim] with n_chains HMC chains each through the
         temperatures betas [T + 1] (default: ais_schedule(n_temps, schedule)); init "encoder" (q(z|x)) or "prior" (N(0, I)); z0 [C, N, D]
         starts the chains there (the reverse run of bidirectional Monte Carlo); noise = (eps0 [C, N, D], mom [T, C, N, D], unif [T, C, N])
         replaces the device generator.  Returns log_px [N] and log_w [C, N] (float64), ess [N], accept_rate [T], z [C, N, D] (final
-        states), step_size [C, N], q_mu, q_sigma [N, D], betas; with trace=True also dH [T, C, N] and accepted [T, C, N] (uint8)."""
+        states), step_size [C, N], q_mu, q_sigma [N, D], betas; with trace=True also dH [T, C, N] and accepted [T, C, N] (uint8).
+        mask [N, x_dim] (non-zero = observed; iwae_ais_masked): the images are incomplete, log_px estimates log p(x_obs), the chains target
+        p(z | x_obs) and the encoder sees mask ? x : 0; what x holds at an unobserved pixel is never read."""
         x = _f32(x).reshape(-1, self.x_dim)
         N, D, Cn = x.shape[0], self.n_latent[0], int(n_chains)
         b = ais_schedule(n_temps, schedule) if betas is None else _f32(betas).ravel()
@@ -440,18 +449,24 @@ class NativeModel:
         outs = AisOutputs()
         for name, arr in res.items():
             setattr(outs, name, arr.ctypes.data)
-        check(self.lib.iwae_ais(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
+        if mask is None:
+            check(self.lib.iwae_ais(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
+        else:
+            mk = self._mask_of("ais", mask, x)
+            check(self.lib.iwae_ais_masked(self.h, x.ctypes.data, mk.ctypes.data, N, C.byref(o), C.byref(outs)))
         res["step_size"] = res.pop("step_out")
         res["betas"] = b
         return res
 
     def local_posterior(self, x, n_samples=16, n_iters=200, n_eval=8, objective="elbo", lr=0.05, start=None, noise=None, trace=False,
-                        beta_1=0.9, beta_2=0.999, epsilon=1e-4):
+                        beta_1=0.9, beta_2=0.999, epsilon=1e-4, mask=None):
         """iwae_local_posterior: a factorised Gaussian q per image of x [N, x_dim], moved by n_iters Adam iterations that ascend the
         n_samples-draw bound `objective` ("elbo" or "iwae") from start = (mu0, sigma0) [N, D] each (None: the encoder heads), then scored
         on n_eval passes of n_samples fresh draws.  noise [n_iters + n_eval, n_samples, N, D] replaces the device generator (and leaves
         the noise step alone).  Returns elbo, iwae [N] (float64), mu, sigma (optimised), q_mu, q_sigma (the start) [N, D], log_w
-        [n_eval n_samples, N]; with trace=True also bound [n_iters, N] and grad [N, 2 D] (the last iteration's; absent at n_iters = 0)."""
+        [n_eval n_samples, N]; with trace=True also bound [n_iters, N] and grad [N, 2 D] (the last iteration's; absent at n_iters = 0).
+        mask [N, x_dim] (non-zero = observed; iwae_local_posterior_masked): q is fitted to p(z | x_obs), the encoder start is the heads of
+        mask ? x : 0, and what x holds at an unobserved pixel is never read."""
         x = _f32(x).reshape(-1, self.x_dim)
         N, D, S, T, E = x.shape[0], self.n_latent[0], int(n_samples), int(n_iters), int(n_eval)
         if objective not in LOCAL_OBJECTIVES:
@@ -484,7 +499,11 @@ class NativeModel:
         outs = LocalOutputs()
         for name, arr in res.items():
             setattr(outs, name, arr.ctypes.data)
-        check(self.lib.iwae_local_posterior(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
+        if mask is None:
+            check(self.lib.iwae_local_posterior(self.h, x.ctypes.data, N, C.byref(o), C.byref(outs)))
+        else:
+            mk = self._mask_of("local_posterior", mask, x)
+            check(self.lib.iwae_local_posterior_masked(self.h, x.ctypes.data, mk.ctypes.data, N, C.byref(o), C.byref(outs)))
         return res
 
     def impute(self, x, mask=None, n_samples=50, noise=None, outputs=IMPUTE_OUTPUT_FIELDS):
