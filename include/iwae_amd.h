@@ -593,7 +593,9 @@ int iwae_posterior(iwae_handle h, const float* x, int32_t N,               /* [N
  * fresh dynamic binarisation, x = 1 iff (philox(seed, epoch, image, pixel/4) >> 8) < floor(g*2^24/255 + 0.5),
  * i.e. Bernoulli(g/255), one draw per image per epoch like the reference's per-epoch bernoullisample.
  * iwae_train_step_dataset takes rows [start, start+B) of the current order; gather + binarise are fused
- * into the input kernel, no host traffic.  iwae_dataset_get_batch returns the same batch for inspection. */
+ * into the input kernel, no host traffic.  iwae_dataset_get_batch returns the same batch for inspection.
+ * The step and the inspection calls (get_batch, get_labels, get_mask): no uploaded set IWAE_ERR_STATE; a range outside
+ * [0, n] (compared in 64 bits), B <= 0 or a null pointer IWAE_ERR_ARG.  A refused call launches nothing. */
 int iwae_dataset_upload(iwae_handle h, const uint8_t* gray, int32_t n);
 int iwae_dataset_begin_epoch(iwae_handle h, uint32_t epoch, const int32_t* order /* NULL keeps the order */, int32_t n);
 int iwae_dataset_get_batch(iwae_handle h, int32_t start, int32_t B, float* x_out);

@@ -1400,7 +1400,9 @@ int iwae_dataset_begin_epoch(iwae_handle m, uint32_t epoch, const int32_t* order
 }
 
 int iwae_dataset_get_batch(iwae_handle m, int32_t start, int32_t B, float* x_out) {
-    if (!m || !x_out || m->ds_N <= 0 || start < 0 || B <= 0 || start + B > m->ds_N) return fail(IWAE_ERR_ARG, "dataset_get_batch: bad range");
+    if (!m || !x_out) return fail(IWAE_ERR_ARG, "dataset_get_batch: null argument");
+    if (m->ds_N <= 0) return fail(IWAE_ERR_STATE, "dataset_get_batch: no dataset uploaded");
+    if (start < 0 || B <= 0 || (int64_t)start + B > (int64_t)m->ds_N) return fail(IWAE_ERR_ARG, "dataset_get_batch: bad range");
     HIPCHK(hipSetDevice(m->cfg.device));
     const int Bp = round_up(B, 128);
     CHK(ensure(m->xP, (size_t)Bp * m->Xinp * 2, m->stream));
@@ -1414,7 +1416,9 @@ int iwae_dataset_get_batch(iwae_handle m, int32_t start, int32_t B, float* x_out
 }
 
 int iwae_dataset_get_labels(iwae_handle m, int32_t start, int32_t B, float* y_out) {
-    if (!m || !y_out || m->ds_N <= 0 || start < 0 || B <= 0 || start + B > m->ds_N) return fail(IWAE_ERR_ARG, "dataset_get_labels: bad range");
+    if (!m || !y_out) return fail(IWAE_ERR_ARG, "dataset_get_labels: null argument");
+    if (m->ds_N <= 0) return fail(IWAE_ERR_STATE, "dataset_get_labels: no dataset uploaded");
+    if (start < 0 || B <= 0 || (int64_t)start + B > (int64_t)m->ds_N) return fail(IWAE_ERR_ARG, "dataset_get_labels: bad range");
     if (m->C <= 0 || !m->ds_has_labels) return fail(IWAE_ERR_STATE, "dataset_get_labels: no labels (iwae_dataset_set_labels on a conditional model)");
     HIPCHK(hipSetDevice(m->cfg.device));
     CHK(join_side(m));
@@ -1480,7 +1484,9 @@ int iwae_dataset_mcar_mask(iwae_handle m, double rate, uint64_t mask_seed) {
 }
 
 int iwae_dataset_get_mask(iwae_handle m, int32_t start, int32_t B, uint8_t* mask_out) {
-    if (!m || !mask_out || m->ds_N <= 0 || start < 0 || B <= 0 || start + B > m->ds_N) return fail(IWAE_ERR_ARG, "dataset_get_mask: bad range");
+    if (!m || !mask_out) return fail(IWAE_ERR_ARG, "dataset_get_mask: null argument");
+    if (m->ds_N <= 0) return fail(IWAE_ERR_STATE, "dataset_get_mask: no dataset uploaded");
+    if (start < 0 || B <= 0 || (int64_t)start + B > (int64_t)m->ds_N) return fail(IWAE_ERR_ARG, "dataset_get_mask: bad range");
     if (!m->ds_has_mask) return fail(IWAE_ERR_STATE, "dataset_get_mask: no masks (iwae_dataset_set_mask / iwae_dataset_mcar_mask)");
     HIPCHK(hipSetDevice(m->cfg.device));
     CHK(ensure(m->scratch, (size_t)B * m->X, m->stream));
@@ -1499,7 +1505,7 @@ int iwae_dataset_get_mask(iwae_handle m, int32_t start, int32_t B, uint8_t* mask
 int iwae_train_step_dataset(iwae_handle m, int32_t start, int32_t B, int32_t k, float beta, float lr, int32_t objective, iwae_scalars* scalars) {
     if (!m) return fail(IWAE_ERR_ARG, "null handle");
     if (m->ds_N <= 0) return fail(IWAE_ERR_STATE, "train_step_dataset: no dataset uploaded");
-    if (start < 0 || B <= 0 || start + B > m->ds_N) return fail(IWAE_ERR_ARG, "train_step_dataset: batch range outside the dataset");
+    if (start < 0 || B <= 0 || (int64_t)start + B > (int64_t)m->ds_N) return fail(IWAE_ERR_ARG, "train_step_dataset: batch range outside the dataset");
     HIPCHK(hipSetDevice(m->cfg.device));
     FwdCall call{m->batch_offset};
     if (m->ds_has_mask) {      // iwae_train_step_masked on (iwae_dataset_get_batch, iwae_dataset_get_mask) of these rows, fed on the device
